@@ -28,14 +28,6 @@ Extra objects on the same JSON line:
   cpu_baseline  the CPU oracle (oracle/, a port: the reference's env is not in its tree) on the
                 host cores, bounded sample of the same workload, rank 0 only
 """
-# HIP maps its streams onto at most GPU_MAX_HW_QUEUES hardware queues (ROCm default 4). The step interleaves an acting stream, one
-# learner stream per agent and, data-parallel, RCCL's stream; which of them share a hardware queue changes the step time by up to
-# 3x (measured r02, one MI355X: multi-rank update path 0.47 ms per step with 4 queues, 0.17 ms with 2; single-rank path 0.144 ms
-# with either; 3 or 8 queues are pathological for one path or the other: profiles/r02/hw_queues.txt). Must be set before the HIP
-# runtime initialises; an explicit setting in the environment wins.
-import os as _os
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "2")
-
 import argparse
 import json
 import os
@@ -100,6 +92,9 @@ def _parse():
     ap.add_argument("--stream-per-agent", type=int, default=-1, help="1: one learner stream per agent, 0: one shared, -1: default")
     ap.add_argument("--unpacked-obs", action="store_true",
                     help="int8 [N, obs_len] observations end to end (the reference's layout) instead of the bit-packed rows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (env outputs, actions, losses, "
+                         "weights) as DIR/<name>.npy in float32, at most 64 MB in all (rank 0)")
     ap.add_argument("--launch-check", action="store_true",
                     help="only rendezvous the ranks and all-reduce one number (works without a GPU: gloo); tests the launcher")
     return ap.parse_args()
@@ -227,6 +222,58 @@ def cpu_baseline_learner(args, obs_len, n_actions):
             "ms_per_update": dt / k * 1e3,
             "sample": f"{k} update() calls of the torch-CPU fp32 learner (DQNLearning.loss + torch.optim.Adam, NoisyMLP "
                       f"{obs_len}->512->{n_actions}x51, batch 256, uniform replay), torch.set_num_threads({cores})"}
+
+
+def dump_outputs(out_dir, env, session, actions, budget=60_000_000, game_sample=2048):
+    """--dump-outputs: the arrays a caller of the timed path holds after its last step, one float32 .npy file each, so that two
+    builds run with the same arguments (same seeds, hence the same inputs) can be compared output for output (under 64 MB in
+    all: `budget` counts the array data, the .npy headers add about 128 B per file). Per-game arrays
+    keep a fixed, seeded sample of `game_sample` games (the rows are written as game_rows.npy); should the whole still exceed
+    `budget`, the largest arrays keep a fixed, seeded sample of their flattened elements (the indices: <name>_elems.npy)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = env.n
+    rows = np.arange(n) if n <= game_sample else np.sort(np.random.default_rng(0).choice(n, game_sample, replace=False))
+    rows_dev = torch.as_tensor(rows, device=env.device)
+    out = {"game_rows": rows}
+    per_game = {"obs": env.obs, "legal": env.legal, "reward": env.reward, "terminal": env.terminal, "score": env.score,
+                "agent_reward": env.agent_reward, "agent_step_type": env.agent_step_type, "actions": actions}
+    for k, t in per_game.items():
+        out[k] = t.index_select(0, rows_dev)
+    if session is not None:
+        for s, a in enumerate(session.agents):
+            if not hasattr(a, "online"):
+                continue
+            loss = a.last_loss
+            if loss is not None:
+                out[f"agent{s}_loss"] = loss if isinstance(loss, torch.Tensor) else torch.tensor(float(loss))
+            for name, p in a.online.named_parameters():
+                out[f"agent{s}_{name.replace('.', '_')}"] = p.detach()
+    out = {k: (v.detach().float().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float32)
+           for k, v in out.items()}
+    # largest per-array element count `cap` that fits: a sampled array costs 4 B per kept value plus 8 B per index
+    sizes = [v.size for v in out.values()]
+    cost = lambda c: sum(4 * z if z <= c else 12 * c for z in sizes)
+    cap = max(sizes)
+    if cost(cap) > budget:
+        lo, hi = 1, cap
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if cost(mid) <= budget else (lo, mid - 1)
+        cap = lo
+    files = []
+    for k, v in out.items():
+        if v.size > cap:
+            elems = np.sort(np.random.default_rng(1).choice(v.size, cap, replace=False))
+            files.append(os.path.join(out_dir, f"{k}_elems.npy"))
+            np.save(files[-1], elems.astype(np.float64))
+            v = v.reshape(-1)[elems]
+        files.append(os.path.join(out_dir, f"{k}.npy"))
+        np.save(files[-1], v)
+    total = sum(os.path.getsize(f) for f in files)
+    assert total <= 64_000_000, total
+    return {"dir": out_dir, "arrays": len(out), "files": len(files), "bytes": total}
 
 
 def sum_tree_baseline(device):
@@ -430,6 +477,11 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        last = act if session is None else session.last_actions[(session.t - 1) % env.players]
+        dumped = dump_outputs(args.dump_outputs, env, session, last)
+
     kernel_ms = sorted(a.elapsed_time(b) for a, b in ev[::args.event_every])
     kernel_avg_s = sum(kernel_ms) / len(kernel_ms) / 1e3
     # Which form of the kernel the loop ran. Round 3: the one-kernel actor picks the moves itself (hb_actor_fused_act), so the
@@ -492,6 +544,8 @@ def main():
                      "avg_launch_us": kernel_avg_s * 1e6, "median_launch_us": kernel_ms[len(kernel_ms) // 2] * 1e3,
                      "kernel_only_env_steps_per_sec": n / kernel_avg_s},
     }
+    if dumped is not None:
+        line["dump_outputs"] = dumped
     if session is not None:
         line["host_calls"] = {"steps_through_hb_chain_run": session.native_steps - native0, "of": args.steps,
                               "note": "steps issued by ONE host call (csrc/chain.hip) instead of ~25"}

@@ -1,6 +1,6 @@
-"""Generates tests/golden/sumtree_ref.json from the REFERENCE SumTree<float>
-(sum_tree/sum_tree/include/sum_tree.h compiled into oracle/_ref/libsumtree_ref.so by
-oracle/Makefile). Runs in this container only; only the vectors are committed.
+"""Generates tests/golden/sumtree_ref.json and tests/golden/sumtree_live_ref.json from the REFERENCE
+SumTree<float> (sum_tree/sum_tree/include/sum_tree.h compiled into oracle/_ref/libsumtree_ref.so by
+oracle/Makefile). Runs where the reference is present; only the vectors are committed.
 
 Leaf values are dyadic (k/16) so every float sum in the tree is exact and the reference's
 running-difference internals (sum_tree.h:80-90) equal an exact rebuild; the quantile grids
@@ -47,6 +47,30 @@ def main():
     with open(os.path.join(HERE, "sumtree_ref.json"), "w") as f:
         json.dump(dict(cases=cases, gtest=gtest, c8=c8), f)
     print("wrote sumtree_ref.json", gtest, c8)
+    live()
+
+
+def live():
+    """The reference's answers to tests/test_oracle_tree.py::test_against_live_reference_build, same draws in the same order,
+    so that the test holds without the reference build. Leaf values are multiples of 1/32 (exact sums)."""
+    rng = np.random.default_rng(11)
+    caps = []
+    for cap in (16, 1000, 4096):
+        ref = RefTree(cap)
+        c = dict(requested_capacity=cap, capacity=int(ref.cap), rounds=[])
+        for _ in range(5):
+            n = int(rng.integers(1, ref.cap))
+            idx = rng.permutation(ref.cap)[:n]
+            val = (rng.integers(0, 1000, n) / 32.0).astype(np.float32)
+            ref.update(idx, val)
+            q = rng.random(257).astype(np.float32)
+            ri, rv = ref.sample(q)
+            c["rounds"].append(dict(n=n, total=ref.total(), sample_idx=ri.tolist(), sample_val=rv.tolist()))
+        c["leaves"] = ref.get(np.arange(ref.cap)).tolist()
+        caps.append(c)
+    with open(os.path.join(HERE, "sumtree_live_ref.json"), "w") as f:
+        json.dump(dict(seed=11, caps=caps), f)
+    print("wrote sumtree_live_ref.json")
 
 
 if __name__ == "__main__":

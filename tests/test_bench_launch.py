@@ -38,24 +38,19 @@ def test_bench_under_a_launcher_keeps_its_world():
     assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])["world"] == 1
 
 
-def test_bench_options_and_hardware_queue_default():
-    """The driver's flags and this round's additions parse; importing bench.py sets GPU_MAX_HW_QUEUES=2 unless the environment
-    already chose a value (with ROCm's default of 4 the multi-rank update path ran 3x slower); without a GPU the
-    benchmark itself refuses to run instead of falling back to anything."""
+def test_bench_options_parse_and_no_cpu_fallback():
+    """The driver's flags and this round's additions parse; without a GPU the benchmark itself refuses to run instead of
+    falling back to anything."""
     code = ("import os, sys; sys.argv=['bench.py','--gpus','1','--steps','20','--warmup','5','--actor-lag','1','--event-every','4',"
-            "'--no-async-variant','--vanilla']; import bench; a=bench.parse(); "
-            "print(os.environ['GPU_MAX_HW_QUEUES'], a.steps, a.warmup, a.actor_lag, a.event_every, a.prime, a.vanilla)")
-    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+            "'--no-async-variant','--vanilla','--dump-outputs','out']; import bench; a=bench.parse(); "
+            "print(a.steps, a.warmup, a.actor_lag, a.event_every, a.prime, a.vanilla, a.dump_outputs)")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
-    assert r.stdout.split() == ["2", "20", "5", "1", "4", "24", "True"]
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(env, GPU_MAX_HW_QUEUES="4"), capture_output=True, text=True,
-                       timeout=300)
-    assert r.stdout.split()[0] == "4"
+    assert r.stdout.split() == ["20", "5", "1", "4", "24", "True", "out"]
     import torch
 
     if not torch.cuda.is_available():
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"], env=env,
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"],
                            capture_output=True, text=True, timeout=300)
         assert r.returncode != 0 and "no CPU fallback" in (r.stderr + r.stdout)
 
@@ -89,3 +84,82 @@ def test_bench_line_keeps_the_measurement_contract():
     c = d["cpu_baseline"]
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0 and "sample" in c
     assert d["async_actor"]["actor_lag"] == 1 and d["async_actor"]["env_steps_per_sec"] > 0
+
+
+def _fake_run(n, hidden):
+    """What dump_outputs reads after the timed steps, as CPU tensors: an env's per-game outputs and one agent's network."""
+    import types
+
+    import torch
+
+    g = torch.Generator().manual_seed(5)
+    env = types.SimpleNamespace(n=n, players=2, device=torch.device("cpu"),
+                                obs=torch.randint(0, 2, (n, 658), generator=g, dtype=torch.int8),
+                                legal=torch.randint(0, 2, (n, 20), generator=g, dtype=torch.int8), reward=torch.randn(n, generator=g),
+                                terminal=torch.zeros(n, dtype=torch.int8), score=torch.randint(0, 25, (n,), generator=g, dtype=torch.int8),
+                                agent_reward=torch.randn(n, generator=g), agent_step_type=torch.ones(n, dtype=torch.int8))
+    with torch.random.fork_rng():
+        torch.manual_seed(5)
+        net = torch.nn.Linear(658, hidden)
+    agent = types.SimpleNamespace(online=net, last_loss=torch.tensor(0.25))
+    return env, types.SimpleNamespace(agents=[agent, object()]), torch.randint(0, 20, (n,), generator=g, dtype=torch.int32)
+
+
+def test_dump_outputs_files_budget_and_repeatability(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy files within the budget; per-game arrays keep the same seeded game sample and
+    arrays too large for the budget the same seeded element sample, so two runs write identical files."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    budget = 4_000_000
+    dumps = []
+    for d in ("a", "b"):
+        env, session, actions = _fake_run(5000, 1024)
+        info = bench.dump_outputs(str(tmp_path / d), env, session, actions, budget=budget)
+        files = sorted(os.listdir(tmp_path / d))
+        assert info["files"] == len(files) and info["bytes"] == sum(os.path.getsize(tmp_path / d / f) for f in files)
+        assert info["bytes"] <= budget + 128 * len(files)
+        dumps.append({f: np.load(tmp_path / d / f) for f in files})
+    a, b = dumps
+    assert a.keys() == b.keys()
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64), f
+        assert np.array_equal(a[f], b[f]), f
+    rows = a["game_rows.npy"].astype(np.int64)
+    assert len(rows) == 2048 and np.all(np.diff(rows) > 0) and rows[-1] < 5000
+    env, _, actions = _fake_run(5000, 1024)
+    assert np.array_equal(a["actions.npy"], actions.numpy()[rows].astype(np.float32))
+    assert np.array_equal(a["legal.npy"], env.legal.numpy()[rows].astype(np.float32))
+    assert a["agent0_loss.npy"] == np.float32(0.25)
+    # the 1024 x 658 weight does not fit: a sorted sample of its elements, with the indices beside it
+    el = a["agent0_weight_elems.npy"].astype(np.int64)
+    w = _fake_run(5000, 1024)[1].agents[0].online.weight.detach().numpy().reshape(-1)
+    assert len(el) < w.size and np.array_equal(a["agent0_weight.npy"], w[el])
+    assert "agent0_bias_elems.npy" not in a
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR` on the GPU: the timed path's last-step outputs as float32 files under 64 MB, the
+    result line still one JSON line whose `steps` is the requested count."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--games", "4096",
+                        "--no-cpu-baseline", "--no-async-variant", "--no-nstep-variant", "--no-fp16-variant",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 5 and d["ms_per_step"] > 0 and d["dump_outputs"]["dir"] == str(tmp_path)
+    files = os.listdir(tmp_path)
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64_000_000
+    out = {f[:-4]: np.load(tmp_path / f) for f in files}
+    assert all(v.dtype == np.float32 for k, v in out.items() if not k.endswith("_elems"))
+    assert out["obs"].shape == (2048, 658) and out["legal"].shape == (2048, 20) and out["actions"].shape == (2048,)
+    assert set(np.unique(out["obs"])) <= {0.0, 1.0}
+    assert out["actions"].min() >= 0 and out["actions"].max() < 20
+    assert "agent0_loss" in out and "agent1_loss" in out and np.isfinite(out["agent0_loss"]).all()

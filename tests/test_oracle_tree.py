@@ -2,7 +2,7 @@
  - the gtest known answers (sum_tree/sum_tree/src/test_sum_tree.cc:45-117),
  - the array-heap vectors of the reference's stale Python test (tests/rlax_dqn/test_sum_tree.py:26,38),
  - golden vectors captured from the reference build (tests/golden/gen_*_golden.py),
- - the live reference build oracle/_ref/libsumtree_ref.so when present.
+ - the live reference build oracle/_ref/libsumtree_ref.so when present, and its stored answers otherwise.
 """
 import json
 import os
@@ -71,24 +71,34 @@ def test_against_reference_golden():
     assert t8.sample([1.0])[0][0] == gold["c8"]["index_of_1"] == 7
 
 
-@pytest.mark.skipif(not O.RefTree.available(), reason="oracle/_ref not built")
 def test_against_live_reference_build():
-    rng = np.random.default_rng(11)
-    for cap in (16, 1000, 4096):
-        ref, mine = O.RefTree(cap), O.OracleTree(cap)
-        assert ref.cap == mine.cap
-        for _ in range(5):
+    """The oracle against the reference build, draw for draw: against oracle/_ref when it is built, and always against the
+    answers that build gave for the same draws (tests/golden/sumtree_live_ref.json, from gen_sumtree_golden.py)."""
+    gold = json.load(open(os.path.join(GOLD, "sumtree_live_ref.json")))
+    rng = np.random.default_rng(gold["seed"])
+    live = O.RefTree.available()
+    for cap, g in zip((16, 1000, 4096), gold["caps"]):
+        assert g["requested_capacity"] == cap
+        ref, mine = O.RefTree(cap) if live else None, O.OracleTree(cap)
+        assert mine.cap == g["capacity"] and (ref is None or ref.cap == mine.cap)
+        for r in g["rounds"]:
             n = int(rng.integers(1, mine.cap))
+            assert n == r["n"]   # the same draws as when the vectors were captured
             idx = rng.permutation(mine.cap)[:n]
             val = (rng.integers(0, 1000, n) / 32.0).astype(np.float32)
-            ref.update(idx, val)
             mine.update(idx, val)
-            assert ref.total() == mine.total()
+            assert mine.total() == r["total"]
             q = rng.random(257).astype(np.float32)
-            ri, rv = ref.sample(q)
             mi, mv = mine.sample(q)
-            assert np.array_equal(ri, mi) and np.array_equal(rv, mv)
-        assert np.array_equal(ref.get(np.arange(mine.cap)), mine.leaves())
+            assert list(mi) == r["sample_idx"] and np.array_equal(mv, np.array(r["sample_val"], np.float32))
+            if ref is not None:
+                ref.update(idx, val)
+                assert ref.total() == mine.total()
+                ri, rv = ref.sample(q)
+                assert np.array_equal(ri, mi) and np.array_equal(rv, mv)
+        assert np.array_equal(mine.leaves(), np.array(g["leaves"], np.float32))
+        if ref is not None:
+            assert np.array_equal(ref.get(np.arange(mine.cap)), mine.leaves())
 
 
 def test_fill_range_wraps():
