@@ -1,0 +1,133 @@
+// eval.hip — the evaluation tally (hb_eval_tally): issued once per turn after the env step of a fixed set of evaluation
+// games (auto-reset off), it records each game's final score and length on the turn it ends and keeps one small block
+// of int64 counters — games still live, the score histogram, bomb-outs, per-seat move kinds and misplays — on the
+// device, so the host only has to read the live count now and then.
+//
+// One lane per game. Every counter is reduced inside the wavefront first (__ballot over the 64 lanes), then inside the
+// workgroup (LDS), and added to HBM with ONE atomic per workgroup and counter from at most 128 workgroups: thousands of
+// atomics on one address cost ~12 ns each (env_kernel.hpp, the episode statistics). Measured: one atomic per wave and
+// counter cost 22-25 us per turn at 32 768 games (512 waves on the same few addresses) against 7 us at 4 096.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "../../include/hanabi_hip.h"
+#include "common.hpp"
+
+namespace {
+
+struct TallyArgs {
+  long long n;
+  int P, C, R, H, A, max_life, seat, turn, bins;
+  const int32_t* actions;
+  const float* reward;
+  const int8_t* terminal;
+  const int8_t* score;
+  uint8_t* done;
+  int8_t* final_score;
+  int16_t* length;
+  unsigned long long* counters;
+};
+
+constexpr int kMaxCounters = 2 + 5 * 5 + 1 + 5 * 5;   // hb_eval_counters() at its largest (5 colours, 5 ranks, 5 players)
+constexpr int kMaxBlocks = 128;                        // at most this many global atomics per counter and turn
+
+__device__ __forceinline__ void wave_add(unsigned int* c, unsigned long long mask, int lane) {
+  if (mask && lane == 0) atomicAdd(c, static_cast<unsigned int>(__popcll(mask)));
+}
+
+// Grid-stride over the games (the loop bound is uniform across the workgroup, so every lane takes part in every ballot).
+// Each wave adds its ballot counts into the workgroup's LDS copy of the counters; the workgroup then issues one global atomic
+// per nonzero counter.
+__global__ void __launch_bounds__(256) eval_tally_kernel(TallyArgs a) {
+  __shared__ unsigned int lc[kMaxCounters];
+  const int lane = threadIdx.x & 63;
+  const int B = a.bins, nc = 2 + B + 5 * a.P;
+  for (int i = threadIdx.x; i < nc; i += 256) lc[i] = 0;
+  __syncthreads();
+  for (long long base = static_cast<long long>(blockIdx.x) * 256; base < a.n; base += static_cast<long long>(gridDim.x) * 256) {
+    const long long g = base + threadIdx.x;
+    int kind = -1, bin = 0;
+    bool ended = false, misplay = false, bomb = false;
+    if (g < a.n) {
+      const uint8_t st = a.done[g];
+      if (!(st & 0x80u)) {   // a game counts only while it is live: finished games' env outputs are never read
+        const int u = a.actions[g];
+        if (u >= 0 && u < a.A) kind = u < a.H ? 0 : u < 2 * a.H ? 1 : u < 2 * a.H + (a.P - 1) * a.C ? 2 : 3;   // App. A.2 order
+        misplay = kind == 1 && a.reward[g] <= 0.f;   // a successful play always scores +1; a misplay 0, or -score at a bomb-out
+        const int lost = (st & 0x7f) + (misplay ? 1 : 0);
+        ended = a.terminal[g] != 0;
+        if (ended) {
+          const int sc = a.score[g];   // 0 after a bomb-out (hb_env_step)
+          bin = sc < 0 ? 0 : sc > B - 1 ? B - 1 : sc;
+          bomb = lost >= a.max_life;
+          a.final_score[g] = static_cast<int8_t>(sc);
+          a.length[g] = static_cast<int16_t>(a.turn + 1);
+          a.done[g] = static_cast<uint8_t>(0x80 | lost);
+        } else if (misplay) {
+          a.done[g] = static_cast<uint8_t>(lost);
+        }
+      }
+    }
+    unsigned long long m = __ballot(ended);
+    if (m) {
+      wave_add(lc, m, lane);   // (slot 0 counts the games that ended: subtracted from the live count below)
+      wave_add(lc + 1 + B, __ballot(bomb), lane);
+      while (m) {   // histogram: one ballot per score that occurs in this wave (wave-uniform loop)
+        const int b = __shfl(bin, __ffsll(static_cast<unsigned long long>(m)) - 1);
+        const unsigned long long mb = __ballot(ended && bin == b);
+        wave_add(lc + 1 + b, mb, lane);
+        m &= ~mb;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wave_add(lc + 2 + B + 4 * a.seat + k, __ballot(kind == k), lane);
+    wave_add(lc + 2 + B + 4 * a.P + a.seat, __ballot(misplay), lane);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nc; i += 256) {
+    const unsigned int v = lc[i];
+    if (v) atomicAdd(a.counters + i, i == 0 ? static_cast<unsigned long long>(-static_cast<long long>(v)) : static_cast<unsigned long long>(v));
+  }
+}
+
+}  // namespace
+
+extern "C" int hb_eval_counters(const hb_config* cfg) {
+  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  return 2 + cfg->colors * cfg->ranks + 1 + 5 * cfg->players;
+}
+
+extern "C" int hb_eval_tally(const hb_config* cfg, int64_t n_games, int32_t seat, int32_t turn, const int32_t* actions_dev,
+                             const float* reward_dev, const int8_t* terminal_dev, const int8_t* score_dev, uint8_t* done_dev,
+                             int8_t* final_score_dev, int16_t* length_dev, int64_t* counters_dev, void* stream) {
+  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  if (n_games < 0) return hb::fail(HB_ERR_INVALID, "n_games must be >= 0");
+  if (seat < 0 || seat >= cfg->players) return hb::fail(HB_ERR_INVALID, "seat %d out of range for %d players", seat, cfg->players);
+  if (turn < 0 || turn >= 32767) return hb::fail(HB_ERR_INVALID, "turn %d out of range 0..32766 (lengths are int16)", turn);
+  if (!actions_dev || !reward_dev || !terminal_dev || !score_dev || !done_dev || !final_score_dev || !length_dev || !counters_dev)
+    return hb::fail(HB_ERR_INVALID, "null argument");
+  if (n_games == 0) return HB_OK;
+  static const int ndev = [] {
+    int n = 0;
+    return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
+  }();
+  if (ndev <= 0) return hb::fail(HB_ERR_NO_DEVICE, "no HIP device available");
+  TallyArgs a{};
+  a.n = n_games;
+  a.P = cfg->players; a.C = cfg->colors; a.R = cfg->ranks; a.H = cfg->hand_size;
+  a.A = hb_num_actions(cfg);
+  a.max_life = cfg->max_life;
+  a.seat = seat;
+  a.turn = turn;
+  a.bins = cfg->colors * cfg->ranks + 1;
+  a.actions = actions_dev; a.reward = reward_dev; a.terminal = terminal_dev; a.score = score_dev;
+  a.done = done_dev; a.final_score = final_score_dev; a.length = length_dev;
+  a.counters = reinterpret_cast<unsigned long long*>(counters_dev);
+  const unsigned blocks = static_cast<unsigned>(std::min<int64_t>((n_games + 255) / 256, kMaxBlocks));
+  hipLaunchKernelGGL(eval_tally_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}

@@ -273,15 +273,10 @@ class DQNAgent:
     def _act_plain(self, obs, legal, epsilon):
         """Vanilla double-DQN head (rlax_dqn.py:26-33 MLP): q = relu(obs @ W1 + b1) @ W2 + b2, illegal moves masked, epsilon-greedy."""
         from hanabi_hip import _capi as K
-        from hanabi_hip.ops import ActorMFMA
 
         hidden = self.params.layers[0]
         kp = (self.obs_len + 63) // 64 * 64
-        pa = self._plain_actor
-        if pa is None:
-            pa = self._plain_actor = ActorMFMA(self.obs_len, hidden, self.n_actions, 2, kp, self.device)   # (only its hidden half is used)
-            pa.stale = True
-            pa.graph = pa.graph_seen = None
+        pa = self._plain_actor_obj()
         fv = self._fv
         if (fv is not None and fv.cd == torch.bfloat16 and self._graphs_enabled() and obs.is_contiguous()
                 and os.environ.get("HB_PLAIN_ACT_GRAPH", "1") != "0"):
@@ -319,6 +314,31 @@ class DQNAgent:
                 g.replay()
                 pa.stale, self._eff_cache = False, True
                 return self._plain_select(qbuf, legal, epsilon, n)
+        self._refresh_plain_weights(pa)
+        n = obs.shape[0]
+        if pa.h is None or pa.h.shape[0] != n:
+            pa.graph = pa.graph_seen = None   # (a captured forward holds the old pa.h)
+            pa.h = torch.empty(n, hidden, dtype=torch.bfloat16, device=self.device)
+        return self._plain_select(self._plain_q(obs, pa, pa.h), legal, epsilon, n)
+
+    def _plain_actor_obj(self):
+        from hanabi_hip.ops import ActorMFMA
+
+        pa = self._plain_actor
+        if pa is None:
+            kp = (self.obs_len + 63) // 64 * 64
+            pa = self._plain_actor = ActorMFMA(self.obs_len, self.params.layers[0], self.n_actions, 2, kp, self.device)   # (only its hidden half is used)
+            pa.stale = True
+            pa.graph = pa.graph_seen = None
+        return pa
+
+    def _refresh_plain_weights(self, pa):
+        """The vanilla actor's transposed first layer and fp32 output layer, refreshed when the weights changed."""
+        from hanabi_hip import _capi as K
+
+        hidden = self.params.layers[0]
+        kp = (self.obs_len + 63) // 64 * 64
+        fv = self._fv
         if (pa.stale or self._eff_cache is None) and fv is not None and fv.cd == torch.bfloat16:
             # the learner keeps bf16 copies of the online weights current: transpose W1 from there (one launch, cached job
             # table) and refresh the fp32 image of the bf16 output layer (two strided copies) — no allocation, no casts
@@ -352,15 +372,38 @@ class DQNAgent:
             pa.w2f, pa.b2f = w2.to(torch.bfloat16).float().contiguous(), b2.float().contiguous()
             pa.stale = False
             self._eff_cache = True
+
+    def _library_logits(self, obs, eff, x_buf):
+        """The network on the library GEMMs: (logits [N, >= A*K], the first GEMM's operand buffer — `x_buf`, or a new one when
+        it does not fit)."""
+        from hanabi_hip import ops
+
+        obs = self._obs_int8(obs)
+        cd = eff[0][0].dtype
+        kp = eff[0][0].shape[0]                     # first-layer K, possibly padded (FusedLearner keeps padded operands)
+        if obs.dtype == torch.int8 and cd != torch.float32:
+            if x_buf is None or x_buf.shape != (obs.shape[0], kp) or x_buf.dtype != cd or x_buf.device != obs.device:
+                x_buf = torch.zeros(obs.shape[0], kp, dtype=cd, device=self.device)   # pad columns stay zero
+            x = ops.obs_cast(obs.contiguous(), cd, out=x_buf)
+        else:
+            x = obs.to(cd)
+            if kp != x.shape[1]:
+                x = torch.nn.functional.pad(x, (0, kp - x.shape[1]))
+        for i, (w, b) in enumerate(eff):  # bias (+ ReLU) ride in the GEMM epilogue
+            x = torch._addmm_activation(b, x, w, use_gelu=False) if i < len(eff) - 1 else torch.addmm(b, x, w)
+        return x, x_buf
+
+    def _plain_q(self, obs, pa, h):
+        """Vanilla head on the hidden-layer MFMA kernel: hidden activations into `h` ([N, hidden] bf16), then q [N, A] fp32."""
+        from hanabi_hip import _capi as K
+
+        hidden, kp = self.params.layers[0], (self.obs_len + 63) // 64 * 64
         n = obs.shape[0]
-        if pa.h is None or pa.h.shape[0] != n:
-            pa.h = torch.empty(n, hidden, dtype=torch.bfloat16, device=self.device)
-        packed = obs.dtype == torch.int32
-        L, s = K.lib(), K.current_stream()
-        fn = L.hb_actor_hidden_packed if packed else L.hb_actor_hidden
-        K.check(fn(K.dptr(obs.contiguous()), n, self.obs_len, K.dptr(pa.w1t), kp, K.dptr(pa.b1), hidden, K.dptr(pa.h), s))
-        q = torch.addmm(pa.b2f, pa.h.float(), pa.w2f)                      # [N, A] fp32: a tiny GEMM
-        return self._plain_select(q, legal, epsilon, n)
+        assert h.shape == (n, hidden) and h.dtype == torch.bfloat16 and h.is_contiguous()
+        L = K.lib()
+        fn = L.hb_actor_hidden_packed if obs.dtype == torch.int32 else L.hb_actor_hidden
+        K.check(fn(K.dptr(obs.contiguous()), n, self.obs_len, K.dptr(pa.w1t), kp, K.dptr(pa.b1), hidden, K.dptr(h), K.current_stream()))
+        return torch.addmm(pa.b2f, h.float(), pa.w2f)                      # [N, A] fp32: a tiny GEMM
 
     def _plain_select(self, q, legal, epsilon, n):
         from hanabi_hip import _capi as K
@@ -401,19 +444,7 @@ class DQNAgent:
                                 self.params.seed + 0x9E3779B9, self._draws, self.first_game_id, s=wset)
         if self.actor_lag:
             raise RuntimeError("actor_lag=1: the MFMA actor takes int8 or bit-packed observations")
-        obs = self._obs_int8(obs)
-        cd = eff[0][0].dtype
-        kp = eff[0][0].shape[0]                     # first-layer K, possibly padded (FusedLearner keeps padded operands)
-        if obs.dtype == torch.int8 and cd != torch.float32:
-            if self._x_act is None or self._x_act.shape != (obs.shape[0], kp) or self._x_act.dtype != cd:
-                self._x_act = torch.zeros(obs.shape[0], kp, dtype=cd, device=self.device)   # pad columns stay zero
-            x = ops.obs_cast(obs.contiguous(), cd, out=self._x_act)
-        else:
-            x = obs.to(cd)
-            if kp != x.shape[1]:
-                x = torch.nn.functional.pad(x, (0, kp - x.shape[1]))
-        for i, (w, b) in enumerate(eff):  # bias (+ ReLU) ride in the GEMM epilogue
-            x = torch._addmm_activation(b, x, w, use_gelu=False) if i < len(eff) - 1 else torch.addmm(b, x, w)
+        x, self._x_act = self._library_logits(obs, eff, self._x_act)
         self._draws += 1
         return ops.policy_act(x, legal.to(torch.int8).contiguous(), self.atoms[0].contiguous(), epsilon,
                               self.params.seed + 0x9E3779B9, self._draws, self.first_game_id)
@@ -459,6 +490,73 @@ class DQNAgent:
         eps = float(self.params.epsilon(self.train_step)) if explore else 0.0
         return fl.actor.act(obs, legal, self._support0, eps, self.params.seed + 0x9E3779B9, self._draws, self.first_game_id, s=wset,
                             actions_out=actions_out)
+
+    @torch.no_grad()
+    def eval_moves(self, observations, seed, draw, actions_out, scratch=None):
+        """Greedy moves for an evaluation (hanabi_hip.evaluate): the weights and the tie rule of exploit(), but the caller's
+        Philox `seed` / `draw` and the caller's buffers. `scratch` is a dict the caller keeps for THIS agent (q, h, GEMM operand):
+        every buffer in it is checked against this call's full shape and dtype and replaced when it does not fit. `actions_out`
+        int32 [N] on the device receives the moves and is returned.
+
+        Nothing the agent acts or trains with moves: the draw counter stays, the actor's own q / h are neither read nor
+        re-allocated, no noise is resampled (with resample_noise=True evaluation uses the current effective weights), and
+        randomness off the Philox kernels (the torch path's tie breaks) comes from a generator seeded with (seed, draw), never the
+        device default generator or the agent's own. On an agent that has not acted yet, the first call builds its
+        FusedLearner from the current weights, exactly as the first explore() / exploit() would (that also switches its sum
+        tree to lazy top levels, which changes no result: include/hanabi_hip.h, hb_tree_set_lazy_top).
+
+        bf16 agents with bit-packed observations always act on the one-kernel actor here, at any row count; exploit() below
+        HB_ACTOR_FUSED_MIN_ROWS rows takes the two-kernel form. Same weights and greedy rule, but a different accumulation order:
+        where two legal moves' q values are within rounding of each other the two forms may pick different moves."""
+        obs, legal = observations[1]
+        obs = obs if isinstance(obs, torch.Tensor) else torch.as_tensor(np.asarray(obs))
+        legal = legal if isinstance(legal, torch.Tensor) else torch.as_tensor(np.asarray(legal))
+        n = obs.shape[0]
+        assert actions_out.dtype == torch.int32 and actions_out.is_contiguous() and actions_out.shape == (n,)
+        scratch = {} if scratch is None else scratch
+        seed, draw = int(seed), int(draw)
+
+        def buf(key, shape, dtype):
+            t = scratch.get(key)
+            if t is None or t.shape != shape or t.dtype != dtype or t.device != self.device:
+                t = scratch[key] = torch.empty(shape, dtype=dtype, device=self.device)
+            return t
+
+        if self._fused or self._plain_fast:
+            from hanabi_hip import _capi as K
+            from hanabi_hip import ops
+
+            obs, legal = obs.to(self.device).contiguous(), legal.to(device=self.device, dtype=torch.int8).contiguous()
+            if self._fused:
+                self._wait_for_weights()   # an update in flight on a learner stream writes the weights read here
+                eff = self._effective_weights()
+                fl = self._fused_learner() if self.actor_lag else self._fl
+                support = self.atoms[0]    # (this agent's own support, every call)
+                act = fl.actor if (fl is not None and self.use_mfma_actor) else None
+                if act is not None and (act.accepts(obs) or (act.fused and obs.dtype == torch.int32)):
+                    (qs, qd), (hs, hd) = act.scratch_shapes(n)
+                    return act.act(obs, legal, support, 0.0, seed, draw, self.first_game_id, s=fl.acting_set(), actions_out=actions_out,
+                                   bufs=(buf("q", qs, qd), buf("h", hs, hd)), one_kernel=True)
+                # library GEMMs + hb_policy_act, as _act_fused takes them
+                x, scratch["x"] = self._library_logits(obs, eff, scratch.get("x"))
+                return ops.policy_act(x, legal, support, 0.0, seed, draw, self.first_game_id, actions_out=actions_out)
+            # vanilla DQN (BASELINE config 2): the hidden-layer MFMA kernel into the caller's h, the output GEMM, hb_policy_select
+            pa = self._plain_actor_obj()
+            self._refresh_plain_weights(pa)
+            q = self._plain_q(obs, pa, buf("h", (n, self.params.layers[0]), torch.bfloat16))
+            K.check(K.lib().hb_policy_select(q.data_ptr(), legal.data_ptr(), n, self.n_actions, 0.0, seed, draw, self.first_game_id,
+                                             actions_out.data_ptr(), K.current_stream()))
+            return actions_out
+        # torch path (CPU, deeper nets, scalar head without the bf16 kernels)
+        gen = scratch.get("gen")
+        if gen is None or gen.device != torch.device(self.device):
+            gen = scratch["gen"] = torch.Generator(device=self.device)
+        gen.manual_seed((seed * 0x9E3779B1 + draw) & 0x7FFFFFFFFFFFFFFF)
+        obs, legal = obs.to(self.device), legal.to(self.device)
+        u = torch.rand(n, device=self.device, generator=gen)
+        actions = DQNPolicy.eval_policy(self.online, self.atoms, self._net_input(obs), legal, u, self.distributional)
+        actions_out.copy_(actions.to(torch.int32))
+        return actions_out
 
     # ---- acting (rlax_rainbow.py:277-290) ---------------------------------------------------------------
     @torch.no_grad()

@@ -51,6 +51,15 @@ class RulebasedAgent:
         self._hist += torch.bincount(self._fired, minlength=len(self.rules) + 1)
         return self._actions
 
+    def eval_moves(self, env, seed, draw, actions_out, fired=None):
+        """Moves for an evaluation (hanabi_hip.evaluate): one hb_rule_act with the caller's Philox seed / draw into the
+        caller's `actions_out` (int32 [N], device) and optional `fired` buffer. The call counter and `histogram` stay as
+        they are."""
+        L = K.lib()
+        K.check(L.hb_rule_act(C.byref(env.cfg), L.hb_env_state(env.h), env.n, env.first_game_id, self._tab, len(self.rules),
+                              int(seed), int(draw), K.dptr(actions_out), K.dptr(fired), K.current_stream()))
+        return actions_out
+
     def explore(self, observations):
         env = observations[0] if isinstance(observations, (tuple, list)) else observations
         if not hasattr(env, "h"):

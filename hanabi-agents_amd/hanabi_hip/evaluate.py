@@ -1,0 +1,205 @@
+"""Greedy evaluation on the GPU: a fixed set of evaluation games, played to the end.
+
+Every Hanabi result is quoted as the greedy policy's mean score over a fixed set of fresh games, with the score histogram
+and the perfect-game rate beside it (the reference: `DQNAgent.exploit`, hanabi_agents/rlax_dqn/rlax_rainbow.py:277-282, on
+the separate evaluation env of its external session). `Evaluator` does that without disturbing a training run:
+
+    ev = Evaluator("Hanabi-Full", players=2, n_games=32768, seed=7)
+    res = ev.run([agent, agent])          # or a mixed team: [agent, RulebasedAgent(piers_rules)]
+    res.mean, res.stderr, res.perfect_rate, res.histogram
+
+* It owns a packed `HanabiEnv` with auto-reset off and every buffer it uses. `run` re-imports the state rows dealt at
+  construction, so every call plays the SAME deals: deck(g) = Philox(seed, first_game_id + g, episode 1).
+* Lock-step: turn t is seat t mod P in every game. Per turn, all asynchronous on the current stream:
+  `agents[seat].eval_moves` -> `HanabiEnv.step` -> `hb_eval_tally` (include/hanabi_hip.h, csrc/eval.hip). The agents' moves use
+  Philox seed = the evaluator's `seed`, draw = turn + 1; no agent's own draw counter, histogram or buffers move.
+* The host reads the live-game counter every `check_every` turns and stops at 0; `max_turns(cfg)` bounds the loop.
+"""
+import ctypes as C
+import math
+import weakref
+
+import torch
+
+from . import _capi as K
+from .env import HanabiEnv
+
+
+def max_turns(cfg):
+    """Upper bound on the length of any game of configuration `cfg`.
+
+    Every discard or play draws a card while the deck lasts, so at most D - P*H of them happen before it runs dry; the game
+    then ends after P more turns. Each hint spends an information token: there are INFO at the start, one more per discard
+    (a discard is legal only below the maximum) and at most one more per completed colour (C). So before the deck runs dry
+    there are at most D - P*H discards / plays and INFO + (D - P*H) + C hints:
+
+        max_turns = (D - P*H) + (INFO + D - P*H + C) + P          (2-player full Hanabi: 40 + 53 + 2 = 95)
+    """
+    L = K.lib()
+    d = L.hb_deck_size(C.byref(cfg))
+    if d <= 0:
+        raise K.HbError(f"invalid configuration {cfg!r}: {L.hb_last_error().decode()}")
+    draws = d - cfg.players * cfg.hand_size
+    return draws + (cfg.max_info + draws + cfg.colors) + cfg.players
+
+
+MOVE_KINDS = ("discard", "play", "reveal_color", "reveal_rank")
+
+
+class EvalResult:
+    """Outcome of one evaluation: plain CPU tensors and ints.
+
+    scores [n] int32 final scores (0 after a bomb-out), lengths [n] int32 turns played, histogram [max_score + 1] int64,
+    bombouts (games that lost every life), moves [P, 4] int64 per seat and kind (MOVE_KINDS), misplays [P] int64 per seat,
+    actions [turns, n] int32 (record_actions only; rows of finished games hold moves the env ignored), turns = turns played."""
+
+    def __init__(self, scores, lengths, max_score, histogram=None, bombouts=0, moves=None, misplays=None, actions=None, turns=None):
+        self.scores = torch.as_tensor(scores).to("cpu", torch.int32)
+        self.lengths = torch.as_tensor(lengths).to("cpu", torch.int32)
+        n = self.scores.numel()
+        if n < 1 or self.lengths.shape != self.scores.shape:
+            raise ValueError("scores and lengths: equal, non-empty vectors")
+        self.max_score = int(max_score)
+        self.histogram = (torch.bincount(self.scores.long(), minlength=self.max_score + 1) if histogram is None
+                          else torch.as_tensor(histogram).to("cpu", torch.int64))
+        self.bombouts = int(bombouts)
+        self.moves = None if moves is None else torch.as_tensor(moves).to("cpu", torch.int64)
+        self.misplays = None if misplays is None else torch.as_tensor(misplays).to("cpu", torch.int64)
+        self.actions = None if actions is None else actions.cpu()
+        self.turns = int(turns) if turns is not None else int(self.lengths.max())
+
+    @property
+    def n_games(self):
+        return self.scores.numel()
+
+    @property
+    def mean(self):
+        return float(self.scores.double().mean())
+
+    @property
+    def stderr(self):
+        """Standard error of the mean: sample standard deviation (n - 1) / sqrt(n); 0 for one game."""
+        n = self.n_games
+        return float(self.scores.double().std(unbiased=True)) / math.sqrt(n) if n > 1 else 0.0
+
+    @property
+    def perfect_rate(self):
+        return float((self.scores == self.max_score).double().mean())
+
+    @property
+    def bombout_rate(self):
+        return self.bombouts / self.n_games
+
+    def cpu(self):
+        return self
+
+    def as_dict(self):
+        """JSON-able numbers (no per-game vectors)."""
+        d = dict(n_games=self.n_games, mean=self.mean, stderr=self.stderr, perfect_rate=self.perfect_rate,
+                 bombout_rate=self.bombout_rate, max_score=self.max_score, histogram=self.histogram.tolist(),
+                 mean_length=float(self.lengths.double().mean()), max_length=int(self.lengths.max()), turns=self.turns)
+        if self.moves is not None:
+            d["moves"] = [dict(zip(MOVE_KINDS, row)) for row in self.moves.tolist()]
+        if self.misplays is not None:
+            d["misplays"] = self.misplays.tolist()
+        return d
+
+    def __repr__(self):
+        return f"EvalResult(n_games={self.n_games}, mean={self.mean:.4f} +- {self.stderr:.4f}, perfect={self.perfect_rate:.4f})"
+
+
+class Evaluator:
+    """Plays the same `n_games` deals to the end every `run(agents)`; see the module docstring.
+
+    game / players: a preset of hanabi_hip.GAME_TYPES (or `config`: an HbConfig whose flags are ignored — evaluation games
+    never auto-reset and score without leniency). first_game_id: global id of game 0 (keys the deals and the agents' draws)."""
+
+    def __init__(self, game="Hanabi-Full", players=2, n_games=4096, seed=1, first_game_id=0, device=None, record_actions=False,
+                 config=None, check_every=8):
+        n_games = int(n_games)
+        if n_games < 1:
+            raise ValueError(f"n_games must be >= 1, got {n_games}")
+        if config is not None:
+            cfg = K.HbConfig(config.players, config.colors, config.ranks, config.hand_size, config.max_info, config.max_life, 0)
+        else:
+            cfg = K.make_config(game, players, 0)
+        if K.lib().hb_config_validate(C.byref(cfg)) != 0:
+            raise ValueError(f"invalid configuration {cfg!r}: {K.lib().hb_last_error().decode()}")
+        self.cfg = cfg
+        self.players = cfg.players
+        self.n = n_games
+        self.seed = int(seed)
+        self.first_game_id = int(first_game_id)
+        self.device = device
+        self.record_actions = bool(record_actions)
+        self.check_every = max(1, int(check_every))
+        self.max_turns = max_turns(cfg)
+        self.max_score = cfg.colors * cfg.ranks
+        self.n_counters = K.lib().hb_eval_counters(C.byref(cfg))
+        self.env = None      # created by the first run(): construction needs no GPU
+        # agent -> the buffers its eval_moves writes (q, h, GEMM operand); weak keys: a dead agent's buffers go with it and are
+        # never handed to another agent
+        self._scratch = weakref.WeakKeyDictionary()
+
+    def _setup(self):
+        if self.env is not None:
+            return
+        env = HanabiEnv(config=self.cfg, n_games=self.n, seed=self.seed, first_game_id=self.first_game_id, device=self.device,
+                        packed=True)
+        dev = env.device
+        self.env = env
+        self.rows0 = env.export_state()   # the deals every run starts from
+        self.done = torch.zeros(self.n, dtype=torch.uint8, device=dev)
+        self.final_score = torch.zeros(self.n, dtype=torch.int8, device=dev)
+        self.length = torch.zeros(self.n, dtype=torch.int16, device=dev)
+        self.counters = torch.zeros(self.n_counters, dtype=torch.int64, device=dev)
+        self.actions = (torch.zeros(self.max_turns, self.n, dtype=torch.int32, device=dev) if self.record_actions
+                        else torch.zeros(1, self.n, dtype=torch.int32, device=dev))
+
+    @torch.no_grad()
+    def run(self, agents):
+        agents = list(agents)
+        if len(agents) != self.players:
+            raise ValueError(f"one agent per seat: {self.players} players, {len(agents)} agents")
+        for a in agents:
+            if not hasattr(a, "eval_moves"):
+                raise TypeError(f"{type(a).__name__} has no eval_moves()")
+        self._setup()
+        env, L, cfg = self.env, K.lib(), self.cfg
+        env.import_state(self.rows0)
+        env.observe()
+        illegal0 = env.illegal_count()
+        self.done.zero_()
+        self.final_score.zero_()
+        self.length.zero_()
+        self.counters.zero_()
+        self.counters[0] = self.n
+        P, n = self.players, self.n
+        cfg_ref = C.byref(cfg)
+        bufs = tuple(K.dptr(t) for t in (env.reward, env.terminal, env.score, self.done, self.final_score, self.length, self.counters))
+        live, t = self.n, 0
+        while t < self.max_turns:
+            seat = t % P
+            agent = agents[seat]
+            act = self.actions[t if self.record_actions else 0]
+            if agent.requires_vectorized_observation():
+                agent.eval_moves((env, (env.net_obs, env.legal)), self.seed, t + 1, act, scratch=self._scratch.setdefault(agent, {}))
+            else:
+                agent.eval_moves(env, self.seed, t + 1, act)
+            env.step(act)
+            K.check(L.hb_eval_tally(cfg_ref, n, seat, t, K.dptr(act), *bufs, K.current_stream()))
+            t += 1
+            if t % self.check_every == 0 or t == self.max_turns:
+                live = int(self.counters[0].item())
+                if live == 0:
+                    break
+        if live != 0:
+            raise RuntimeError(f"{live} evaluation games still live after max_turns = {self.max_turns} turns")
+        illegal = env.illegal_count() - illegal0
+        if illegal:
+            raise RuntimeError(f"evaluation agents chose {illegal} illegal moves")
+        c = self.counters.cpu()
+        B = self.max_score + 1
+        return EvalResult(self.final_score, self.length, self.max_score, histogram=c[1:1 + B], bombouts=int(c[1 + B]),
+                          moves=c[2 + B:2 + B + 4 * P].view(P, 4), misplays=c[2 + B + 4 * P:2 + B + 5 * P],
+                          actions=self.actions[:t].clone() if self.record_actions else None, turns=t)

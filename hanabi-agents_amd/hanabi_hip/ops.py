@@ -209,22 +209,34 @@ class ActorMFMA:
         K.check(qfn(hp, n, self.hidden, w2p, b2p, sp, self.n_actions, self.n_atoms, qp, st))
         return self.q
 
-    def act(self, obs, legal, support, epsilon, seed, draw, first_game_id=0, s=0, actions_out=None):
+    def scratch_shapes(self, n):
+        """Shapes and dtypes of the (q, h) buffers act() needs for n rows."""
+        return ((n, self.n_actions), torch.float32), ((n if self.two_kernel else 1, self.hidden), self.dtype)
+
+    def act(self, obs, legal, support, epsilon, seed, draw, first_game_id=0, s=0, actions_out=None, bufs=None, one_kernel=False):
+        """bufs = (q, h): caller-owned scratch of scratch_shapes(n) instead of this object's own (which are then neither read nor
+        re-allocated); one_kernel: take the one-kernel form wherever it applies, whatever fused_min_rows says."""
         n = obs.shape[0]
         packed = obs.dtype == torch.int32
         assert obs.is_contiguous() and ((packed and obs.shape[1] == (self.obs_len + 31) // 32) or
                                         (obs.dtype == torch.int8 and obs.shape[1] == self.obs_len))
         assert legal.dtype == torch.int8 and legal.is_contiguous() and legal.shape == (n, self.n_actions)
-        if self.q is None or self.q.shape[0] != n:
-            self.h = torch.empty(n if self.two_kernel else 1, self.hidden, dtype=self.dtype, device=obs.device)
-            self.q = torch.empty(n, self.n_actions, dtype=torch.float32, device=obs.device)
-            self.tickets = torch.zeros((n + 255) // 256, dtype=torch.int32, device=obs.device)   # hb_actor_q_select
+        if bufs is not None:
+            q, h = bufs
+            for t, (shape, dt) in zip(bufs, self.scratch_shapes(n)):
+                assert t.shape == shape and t.dtype == dt and t.is_contiguous() and t.device == obs.device
+        else:
+            if self.q is None or self.q.shape[0] != n:
+                self.h = torch.empty(n if self.two_kernel else 1, self.hidden, dtype=self.dtype, device=obs.device)
+                self.q = torch.empty(n, self.n_actions, dtype=torch.float32, device=obs.device)
+                self.tickets = torch.zeros((n + 255) // 256, dtype=torch.int32, device=obs.device)   # hb_actor_q_select
+            q, h = self.q, self.h
         actions = actions_out if actions_out is not None else torch.empty(n, dtype=torch.int32, device=obs.device)
-        if self.fused and packed and n >= self.fused_min_rows and self.n_actions <= 64:
+        if self.fused and packed and (one_kernel or n >= self.fused_min_rows) and self.n_actions <= 64:
             # ONE launch: forward + C51 expectation + the epsilon-greedy selection on the rows each workgroup has just written
             f = self._fset_ptrs[s]
             K.check(K.lib().hb_actor_fused_act_dt(obs.data_ptr(), legal.data_ptr(), n, self.obs_len, f[0], f[1], f[2], f[3],
-                                                  support.data_ptr(), self.hidden, self.n_actions, self.n_atoms, self.q.data_ptr(),
+                                                  support.data_ptr(), self.hidden, self.n_actions, self.n_atoms, q.data_ptr(),
                                                   float(epsilon), int(seed), int(draw), int(first_game_id), actions.data_ptr(),
                                                   self._dt, K.current_stream()))
             return actions
@@ -234,8 +246,8 @@ class ActorMFMA:
             self._pack_two(s)
         w1p, b1p, w2p, b2p = self._set_ptrs[s]
         K.check(K.lib().hb_actor_act(obs.data_ptr(), 1 if packed else 0, legal.data_ptr(), n, self.obs_len, w1p, self.k_pad, b1p,
-                                     self.hidden, self.h.data_ptr(), w2p, b2p, support.data_ptr(), self.n_actions, self.n_atoms,
-                                     self.q.data_ptr(), float(epsilon), int(seed), int(draw), int(first_game_id),
-                                     actions.data_ptr(), self.tickets.data_ptr() if self.fuse_select else None,
+                                     self.hidden, h.data_ptr(), w2p, b2p, support.data_ptr(), self.n_actions, self.n_atoms,
+                                     q.data_ptr(), float(epsilon), int(seed), int(draw), int(first_game_id),
+                                     actions.data_ptr(), self.tickets.data_ptr() if (self.fuse_select and bufs is None) else None,
                                      K.current_stream()))   # hidden GEMM; q GEMM + C51 expectation + selection
         return actions

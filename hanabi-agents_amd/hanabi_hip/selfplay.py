@@ -102,6 +102,7 @@ class SelfPlaySession:
         self.select_in_env_steps = 0   # steps whose moves were picked inside the env kernel (hb_env_step_select_packed)
         self._chains = {}        # seat -> _Chain
         self.native_steps = 0
+        self._evaluators = {}    # (n_games, seed) -> hanabi_hip.evaluate.Evaluator
 
     # ---- one host call per step ----------------------------------------------------------------------------------------------
     def _chain_for(self, seat, agent, train, raw):
@@ -128,10 +129,18 @@ class SelfPlaySession:
         wset = fl.n_packed % 2 if lag else 0
         if lag and (fl.packed_ev[wset] is None or fl.actor._two_stale[wset]):
             return None   # (this weight set has not been through the ordinary path yet)
+        act = fl.actor
+        if act.q is None or act.q.shape[0] != env.n:
+            return None   # (the actor's q buffer is sized by the ordinary path's policy call)
+        if agent._support0 is None:
+            agent._support0 = agent.atoms[0].contiguous()
         ch = self._chains.get((seat, wset))
         ls = self._learner_stream_of(agent)
+        # (every address the command array holds is part of the key: a buffer re-allocated since — e.g. the actor's q after a
+        #  policy call on another row count — rebuilds the chain instead of leaving it writing into freed memory)
         key = (raw, ls.cuda_stream, wset, agent._dense_call[0], fl._sg_call[0], fl._sg_call[1], id(agent._graph1), buf.rows_per_insert,
-               self.last_actions[seat].data_ptr(), self._act_buf[seat].data_ptr(), agent._g_idx.data_ptr(), agent._g_prios.data_ptr())
+               self.last_actions[seat].data_ptr(), self._act_buf[seat].data_ptr(), agent._g_idx.data_ptr(), agent._g_prios.data_ptr(),
+               act.q.data_ptr(), agent._support0.data_ptr())
         if ch is None or ch.key != key:
             # the cached insert call must be the one the ordinary path would make NOW (same seven operands, add_experience_dense)
             now = (env.net_obs.data_ptr(), env.legal.data_ptr(), self.last_actions[seat].data_ptr(), env.agent_reward.data_ptr(),
@@ -348,6 +357,23 @@ class SelfPlaySession:
         for _ in range(steps):
             self.step(train=train)
         self.flush()
+
+    # ---- greedy evaluation (hanabi_hip.evaluate) -----------------------------------------------------------------
+    def evaluate(self, n_games=4096, seed=1, partners=None):
+        """Greedy mean score of the session's agents (or of `partners`: one agent per seat, DQN and rule-based mixed) over a
+        fixed set of `n_games` fresh deals keyed by `seed`: an EvalResult. Updates in flight are completed first (flush());
+        the session's env, counters, command arrays and agents are left exactly as they were, so training continues as if
+        the evaluation had not happened. The evaluator (its env and buffers) is kept for the next call of the same size."""
+        self.flush()
+        from .evaluate import Evaluator
+
+        key = (int(n_games), int(seed))
+        ev = self._evaluators.get(key)
+        if ev is None:
+            rank = self.env.first_game_id // self.env.n if self.env.n else 0   # (data-parallel: each rank its own deals)
+            ev = self._evaluators[key] = Evaluator(config=self.env.cfg, n_games=n_games, seed=seed, first_game_id=rank * int(n_games),
+                                                   device=self.env.device)
+        return ev.run(self.agents if partners is None else partners)
 
     # ---- checkpoint / resume (SURVEY §8(f)-4) -----------------------------------------------------------------
     def checkpoint_state(self, include_replay=True):

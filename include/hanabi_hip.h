@@ -620,6 +620,28 @@ int hb_actor_fused_act_dt(const uint32_t* obs_bits_dev, const int8_t* legal_dev,
                           const float* support_dev, int32_t hidden, int32_t n_actions, int32_t n_atoms, float* q_dev, float epsilon,
                           uint64_t seed, uint64_t draw, int64_t first_game_id, int32_t* actions_dev, int32_t dtype, void* stream);
 
+/* ---- greedy evaluation (csrc/eval.hip) ------------------------------------------------------------------------------------
+ * A fixed set of n_games evaluation games (auto-reset off, lock-step: turn t is seat t mod P in every game) is played to the
+ * end; hb_eval_tally is issued once per turn after hb_env_step on the same stream and tallies what that turn did.
+ *   actions_dev [n] int32 the moves just stepped; reward_dev [n] f32, terminal_dev [n] int8, score_dev [n] int8: that step's
+ *                         outputs (read only for games still live: a finished game's outputs are never relied on)
+ *   done_dev    [n] uint8 per-game status, zeroed by the caller before turn 0: bit 7 = finished, bits 0-6 = lives lost
+ *   final_score_dev [n] int8 / length_dev [n] int16: written once, on the turn a game ends (score 0 after a bomb-out, as
+ *                         score_dev reports it; length = turn + 1)
+ *   counters_dev [hb_eval_counters(cfg)] int64, set by the caller before turn 0 (live = n, the rest 0):
+ *     [0]                               games still live
+ *     [1 .. 1 + B)                      score histogram, B = colors * ranks + 1 bins (score 0 .. colors * ranks)
+ *     [1 + B]                           bomb-outs (games that ended with every life lost)
+ *     [2 + B + 4 * p + k]               moves of seat p of kind k: 0 discard, 1 play, 2 reveal colour, 3 reveal rank
+ *                                       (decoded from the uid, App. A.2 order)
+ *     [2 + B + 4 * P + p]               misplays of seat p (a play whose reward is <= 0)
+ * A game counts on the turn it ends and only then; games already marked in done_dev are ignored. Counters are reduced per
+ * wavefront (ballots) and per workgroup (LDS); each takes at most one global atomic per workgroup, from <= 128 workgroups. Without a device: HB_ERR_NO_DEVICE (arguments are checked first).                              */
+int hb_eval_counters(const hb_config* cfg); /* number of int64 counters: 2 + colors * ranks + 1 + 5 * players */
+int hb_eval_tally(const hb_config* cfg, int64_t n_games, int32_t seat, int32_t turn, const int32_t* actions_dev,
+                  const float* reward_dev, const int8_t* terminal_dev, const int8_t* score_dev, uint8_t* done_dev,
+                  int8_t* final_score_dev, int16_t* length_dev, int64_t* counters_dev, void* stream);
+
 /* ---- One host call per step: hb_chain_run (csrc/chain.hip, round 3) ------------------------------------------------------
  * The session that drives DQNAgent (rlax_rainbow.py:277-339: explore / add_experience / update once per env step) issues ~25
  * launches, event waits and event records per step. A host fills an array of hb_cmd ONCE with every pointer, size and stream of
