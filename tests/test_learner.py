@@ -221,3 +221,202 @@ def test_pending_tree_fills_are_coalesced_and_bounded():
     for _ in range(1000):               # a frozen seat in a long run
         agent._queue_fill(0, 64)
     assert len(agent._pending_fills) == 1
+
+
+# ---- the float64 oracle of the learner kernels (oracle/learner_oracle.py), pinned without torch -------------------------
+def _c51_case(rng, b=6, a=4, k=7, vmax=3.0):
+    support = np.linspace(-vmax, vmax, k)
+    l1, ls, lt = (rng.standard_normal((b, a, k)) for _ in range(3))
+    act = rng.integers(0, a, b)
+    rew = rng.uniform(-2, 2, b)
+    term = (rng.random(b) < 0.4).astype(float)
+    disc = 0.9 ** rng.integers(1, 4, b)
+    prios = 10.0 ** rng.uniform(-3, 0, b)
+    return support, l1, ls, lt, act, rew, term, disc, prios
+
+
+@pytest.mark.parametrize("mask", [True, False])
+@pytest.mark.parametrize("beta", [-0.5, 0.0, 0.4, 1.0])
+def test_c51_gradient_equals_finite_differences(mask, beta):
+    """dLoss/dlogits of c51_td_and_grad against central differences of loss = mean(w * td) in float64, over EVERY
+    logit of obs_tm1: the gradient is the returned [B, K] block in the taken action's atoms and zero elsewhere."""
+    rng = np.random.default_rng(11)
+    support, l1, ls, lt, act, rew, term, disc, prios = _c51_case(rng)
+    bias = rng.standard_normal(l1.shape[1] * l1.shape[2]) * 0.3
+    td, w, dl, _ = LO.c51_td_and_grad(l1, ls, lt, act, rew, term, disc, mask, support, prios, beta, bias, bias * 0.5)
+    assert np.allclose(w, LO.is_weights(prios, beta, f32_inverse=True)) and w.max() == 1.0
+
+    def loss(x):
+        t, ww, _, _ = LO.c51_td_and_grad(x, ls, lt, act, rew, term, disc, mask, support, prios, beta, bias, bias * 0.5)
+        return float(np.mean(ww * t))
+
+    assert np.isclose(loss(l1), float(np.mean(w * td)))
+    h = 1e-6
+    fd = np.zeros_like(l1)
+    for idx in np.ndindex(*l1.shape):
+        e = np.zeros_like(l1)
+        e[idx] = h
+        fd[idx] = (loss(l1 + e) - loss(l1 - e)) / (2 * h)
+    want = np.zeros_like(l1)
+    want[np.arange(len(act)), act] = dl
+    assert np.allclose(fd, want, atol=1e-9, rtol=1e-6)
+
+
+def test_dqn_gradient_equals_finite_differences():
+    rng = np.random.default_rng(12)
+    b, a = 9, 5
+    q1, qs, qt = (rng.standard_normal((b, a)) for _ in range(3))
+    act, rew = rng.integers(0, a, b), rng.uniform(-1, 1, b)
+    term = np.array([0, 1, 0, 0, 1, 0, 0, 0, 1.0])
+    disc, prios = 0.99 ** rng.integers(1, 4, b), 10.0 ** rng.uniform(-4, 0, b)
+    bo, bt = rng.standard_normal(a), rng.standard_normal(a)
+    td, w, dq, sel = LO.dqn_td_and_grad(q1, qs, qt, act, rew, term, disc, prios, -0.3, bo, bt)
+    qsb, qtb = qs + bo, np.where(term[:, None] != 0, 0.0, qt + bt)
+    assert np.array_equal(sel, qsb.argmax(1))
+    assert np.allclose(td, rew + disc * qtb[np.arange(b), sel] - (q1 + bo)[np.arange(b), act])
+
+    def loss(x):
+        t, ww, _, _ = LO.dqn_td_and_grad(x, qs, qt, act, rew, term, disc, prios, -0.3, bo, bt)
+        return float(np.mean(ww * 0.5 * t * t))
+
+    h, fd = 1e-6, np.zeros_like(q1)
+    for idx in np.ndindex(*q1.shape):
+        e = np.zeros_like(q1)
+        e[idx] = h
+        fd[idx] = (loss(q1 + e) - loss(q1 - e)) / (2 * h)
+    want = np.zeros_like(q1)
+    want[np.arange(b), act] = dq
+    assert np.allclose(fd, want, atol=1e-10, rtol=1e-6)
+
+
+def test_c51_backward_equals_finite_differences():
+    """c51_backward against central differences of L = sum(dlogits * logits), logits = relu(x + b1) @ w2 + b2, taken
+    with respect to x (dH), b1, w2 and b2; x stays clear of the ReLU kink."""
+    rng = np.random.default_rng(13)
+    b, hdim, a, k = 5, 6, 3, 4
+    x = rng.uniform(0.2, 1.0, (b, hdim)) * rng.choice([-1.0, 1.0], (b, hdim))
+    b1 = np.zeros(hdim)
+    w2, b2 = rng.standard_normal((hdim, a * k)), rng.standard_normal(a * k)
+    act = np.array([2, 0, 2, 2, 0])          # action 1 is never taken
+    dl = rng.standard_normal((b, k))
+    dense = np.zeros((b, a * k))
+    for i in range(b):
+        dense[i, act[i] * k:(act[i] + 1) * k] = dl[i]
+    L = lambda x_, b1_, w2_, b2_: float((dense * (np.maximum(x_ + b1_, 0) @ w2_ + b2_)).sum())
+    dh, db1, dw2, db2 = LO.c51_backward(dl, act, np.maximum(x, 0), w2, k)
+
+    def fd(f, v):
+        out, h = np.zeros_like(v), 1e-6
+        for idx in np.ndindex(*v.shape):
+            e = np.zeros_like(v)
+            e[idx] = h
+            out[idx] = (f(v + e) - f(v - e)) / (2 * h)
+        return out
+
+    assert np.allclose(dh, fd(lambda v: L(v, b1, w2, b2), x), atol=1e-8)
+    assert np.allclose(db1, fd(lambda v: L(x, v, w2, b2), b1), atol=1e-8)
+    assert np.allclose(dw2, fd(lambda v: L(x, b1, v, b2), w2), atol=1e-8)
+    assert np.allclose(db2, fd(lambda v: L(x, b1, w2, v), b2), atol=1e-8)
+    assert not dw2[:, k:2 * k].any() and not db2[k:2 * k].any()
+    # relu'(0) = 0 (aten::threshold_backward): a unit whose activation is exactly zero passes no gradient
+    h0 = np.maximum(x, 0)
+    h0[:, 0] = 0.0
+    assert not LO.c51_backward(dl, act, h0, w2, k)[0][:, 0].any()
+
+
+def test_c51_projection_hand_worked_atoms_and_clipping():
+    """Support [-2..2] (delta 1), the target distribution p and the online distribution q given as log-probabilities:
+    r = 1, gamma = 1 lands every atom on an atom (the top one clipped onto vmax); r = -5 / +5 clips everything onto
+    vmin / vmax; gamma = 0 (terminal, masked) puts all mass at r = 0.5 split half-half between atoms 0 and 1."""
+    support = np.linspace(-2, 2, 5)
+    p = np.array([0.1, 0.2, 0.3, 0.15, 0.25])
+    q = np.array([0.3, 0.1, 0.2, 0.25, 0.15])
+    lt = np.log(np.stack([p, p[::-1]]))[None].repeat(4, 0)      # [B=4, A=2, K=5]; action 1's target is p reversed
+    l1 = np.log(np.stack([q, q]))[None].repeat(4, 0)
+    ls = np.zeros((4, 2, 5))
+    ls[:, 0, 4] = 1.0                                            # the selector prefers action 0 (more mass on +2)
+    rew = np.array([1.0, -5.0, 5.0, 0.5])
+    term = np.array([0.0, 0.0, 0.0, 1.0])
+    td, w, dl, sel = LO.c51_td_and_grad(l1, ls, lt, np.zeros(4, int), rew, term, np.ones(4), True, support,
+                                        np.full(4, 0.25), 0.4)
+    assert sel.tolist() == [0, 0, 0, 0] and np.allclose(w, 1.0)
+    targets = [np.array([0, p[0], p[1], p[2], p[3] + p[4]]), np.array([1.0, 0, 0, 0, 0]), np.array([0, 0, 0, 0, 1.0]),
+               np.array([0, 0, 0.5, 0.5, 0])]
+    for i, t in enumerate(targets):
+        assert np.isclose(td[i], -(t * np.log(q)).sum(), atol=1e-12)
+        assert np.allclose(dl[i], (q - t) / 4, atol=1e-12)       # w = 1, B = 4, sum(t) = 1
+    # the same r = 0.5 transition with the mask off keeps gamma = 1: tz = z + 0.5, every atom split half-half
+    td2 = LO.c51_td_and_grad(l1, ls, lt, np.zeros(4, int), rew, term, np.ones(4), False, support, np.full(4, 0.25), 0.4)[0]
+    t = np.array([0.5 * p[0], 0.5 * (p[0] + p[1]), 0.5 * (p[1] + p[2]), 0.5 * (p[2] + p[3]), 0.5 * p[3] + p[4]])
+    assert np.isclose(td2[3], -(t * np.log(q)).sum(), atol=1e-12)
+
+
+def test_double_q_ties_select_the_lowest_action():
+    support = np.linspace(-2, 2, 5)
+    rng = np.random.default_rng(4)
+    row = rng.standard_normal(5) + np.arange(5.0)               # mass towards +2: the highest q
+    low = lambda: rng.standard_normal(5) - np.arange(5.0)
+    ls = np.stack([low(), row, low(), row])[None]                # actions 1 and 3 tie
+    lt = rng.standard_normal((1, 4, 5))
+    args = (np.zeros(1, int), np.zeros(1), np.zeros(1), np.full(1, 0.9), True, support, np.ones(1), 0.4)
+    assert LO.c51_td_and_grad(lt, ls, lt, *args)[3].tolist() == [1]
+    ls2 = ls.copy()
+    ls2[0, 3, 4] += 1e-9                                          # no longer a tie: action 3 wins
+    assert LO.c51_td_and_grad(lt, ls2, lt, *args)[3].tolist() == [3]
+    q = np.array([[0.5, 2.0, -1.0, 2.0], [3.0, 3.0, 3.0, 3.0]])
+    assert LO.dqn_td_and_grad(q, q, q, [0, 0], [0, 0], [0, 0], 0.9, [1, 1], 0.4)[3].tolist() == [1, 0]
+
+
+def test_is_weights_beta_edges():
+    """rlax_rainbow.py:188-189 for beta < 0, 0, 1: the maximum of (1/P) ** beta sits at the smallest P for beta > 0
+    and at the largest P for beta < 0."""
+    prios = np.array([0.5, 0.25, 0.125])
+    assert np.allclose(LO.is_weights(prios, -0.5), [1.0, 2 ** -0.5, 0.5])
+    assert np.allclose(LO.is_weights(prios, 0.0), [1.0, 1.0, 1.0])
+    assert np.allclose(LO.is_weights(prios, 1.0), [0.25, 0.5, 1.0])
+    p = np.array([1e-8, 0.3, 1.0])                               # 1/0.3 is not a float32: the cast is visible
+    w = LO.is_weights(p, 0.4, f32_inverse=True)
+    assert w[0] == 1.0 and w[2] == 1e-8 ** 0.4
+    assert w[1] == float(np.float32(1 / 0.3)) ** 0.4 / 1e8 ** 0.4 and w[1] != LO.is_weights(p, 0.4)[1]
+
+
+@pytest.mark.parametrize("shared", [False, True])
+def test_noisy_adam_first_step_and_gradient_routing(shared):
+    """t = 1 from zero moments: the step is lr * g / (|g| + eps) exactly (m-hat = g, v-hat = g^2); w_sigma sees
+    g * noise, the gradient of W = w + w_mu + w_sigma * noise; shared moments give the separate-moment result."""
+    rng = np.random.default_rng(6)
+    shape = (3, 5)
+    w, mu, sg, nz = (rng.standard_normal(shape) for _ in range(4))
+    g = rng.standard_normal(shape) * 1e-3
+    z = np.zeros(shape)
+    lr, eps = 1e-3, 3.125e-5
+    ow, omu, osg, mom, eff = LO.noisy_adam(w, mu, sg, nz, g, (z,) * 6, 0, lr=lr, eps=eps, step_offset=1, shared=shared)
+    assert np.allclose(ow, w - lr * g / (np.abs(g) + eps), rtol=0, atol=1e-15)
+    assert np.allclose(omu, mu - lr * g / (np.abs(g) + eps), rtol=0, atol=1e-15)
+    assert np.allclose(osg, sg - lr * g * nz / (np.abs(g * nz) + eps), rtol=0, atol=1e-15)
+    assert np.allclose(eff, ow + omu + osg * nz, rtol=0, atol=1e-15)
+    assert np.allclose(mom[0], 0.1 * g) and np.allclose(mom[1], 0.001 * g * g) and np.allclose(mom[4], 0.1 * g * nz)
+    if shared:
+        assert mom[2] is not None and not mom[2].any()            # m_mu is not touched
+    # later steps: step_offset moves the bias correction; shared == separate with equal moments
+    m0 = [rng.random(shape) * 1e-4 for _ in range(6)]
+    m0[2], m0[3] = m0[0], m0[1]
+    a = LO.noisy_adam(w, mu, sg, nz, g, m0, 4, step_offset=1.0, shared=False)
+    b = LO.noisy_adam(w, mu, sg, nz, g, m0, 4, step_offset=1.0, shared=True)
+    c = LO.noisy_adam(w, mu, sg, nz, g, m0, 5, step_offset=0.0, shared=shared)
+    assert np.allclose(a[1], b[1], rtol=0, atol=1e-15) and np.allclose(a[4], b[4], rtol=0, atol=1e-15)
+    assert all(np.array_equal(x, y) for x, y in zip(b[:3], c[:3]))
+    assert not np.allclose(LO.noisy_adam(w, mu, sg, nz, g, m0, 4, step_offset=0.0)[0], a[0], rtol=0, atol=1e-9)
+
+
+def test_per_priority_known_values():
+    """priority_buffer.py:49 on float32 |td|: (|td| + 1e-10) ** alpha, alpha taken as a float32."""
+    td = np.array([0.0, 1e-12, -1.0, 1e6, -0.25], np.float32)
+    assert np.array_equal(LO.per_priority(td, 0.0), np.ones(5, np.float32))
+    assert np.array_equal(LO.per_priority(td, 1.0), np.abs(td) + np.float32(1e-10))
+    p = LO.per_priority(td, 0.6)
+    assert p.dtype == np.float32
+    a = float(np.float32(0.6))
+    assert p[0] == np.float32(float(np.float32(1e-10)) ** a) and p[2] == 1.0
+    assert p[3] == np.float32(1e6 ** a) and p[4] == np.float32(0.25 ** a)
+    assert abs(p[0] - 1e-6) < 1e-12                                  # the 1e-10 keeps a zero TD sampleable
