@@ -28,10 +28,11 @@
 #include <hip/hip_fp16.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/hanabi_hip.h"
 #include "common.hpp"
-#include "env_kernel.hpp"  // philox4x32_10
+#include "env_kernel.hpp"  // philox4x32_10, env_wave_step
 
 using hb::fail;
 
@@ -153,8 +154,11 @@ __device__ __forceinline__ float vmax3(float a, float b, float c) {
 }
 __device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
 
-template <bool F16>
-__global__ __launch_bounds__(FNT) void actor_fused_kernel(const FusedArgs a) {
+// The kernel body. K = void: q values (and, with a.legal, the selected moves) only. K = an env Cfg (hb_actor_fused_act_step): the
+// workgroup then steps its own 128 games with the moves it has just selected (env_wave_step of env_kernel.hpp, EG games per
+// wavefront), in the LDS of H, which is dead by then. The K = void form compiles to exactly the kernel it was before.
+template <bool F16, class K, int EG>
+__device__ __forceinline__ void actor_fused_body(const FusedArgs& a) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_TOTAL];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform: everything derived from it lives in scalar registers)
@@ -534,9 +538,49 @@ __global__ __launch_bounds__(FNT) void actor_fused_kernel(const FusedArgs a) {
         pick = __ffsll(static_cast<long long>(pool)) - 1;
       }
       a.actions[g] = pick;
+      if constexpr (!std::is_void_v<K>) reinterpret_cast<int*>(lds + H_BYTES)[tid] = pick;
+    }
+  }
+  if constexpr (!std::is_void_v<K>) {
+    // ---- env tail: games [row0, row0 + 128) take their moves from LDS; wavefront w steps games row0 + EG w + [0, EG). The
+    // barrier also orders every read of `legal` and of the bit rows (done above) before the env's writes of the same rows.
+    constexpr int ENV_WORDS = hb::env_lds_words<K, EG>();
+    static_assert((FM / EG) * ENV_WORDS * 4 <= H_BYTES && FM / EG <= FNT / 64, "env tail: the LDS slices must fit in H");
+    __syncthreads();
+    if (wave < FM / EG) {
+      // The env arguments (the kernel's second parameter) are read from the kernel-argument segment only HERE: read through the
+      // parameter, the compiler loads them at the kernel's start and carries ~30 scalar registers through both layers, which
+      // spills scalars into a reserved vector register (233 VGPRs instead of 232: no room left for the learner's kernels beside
+      // this one). The opaque pointer keeps the loads in the tail. Explicit kernel arguments are laid out in declaration order
+      // at their natural alignment.
+#if defined(__HIP_DEVICE_COMPILE__)
+      typedef const __attribute__((address_space(4))) unsigned char KargByte;
+      typedef const __attribute__((address_space(4))) hb::EnvArgs KargEnv;
+      auto kargs = __builtin_amdgcn_kernarg_segment_ptr();
+      asm volatile("" : "+s"(kargs));
+      constexpr size_t ENV_OFF = (sizeof(FusedArgs) + alignof(hb::EnvArgs) - 1) / alignof(hb::EnvArgs) * alignof(hb::EnvArgs);
+      KargEnv& env = *(KargEnv*)((KargByte*)kargs + ENV_OFF);
+#else
+      const hb::EnvArgs env{};   // (host pass: never run)
+#endif
+      const long long g0 = row0 + EG * wave;
+      const int uid = lane < EG ? reinterpret_cast<const int*>(lds + H_BYTES)[EG * wave + lane] : 0;
+      hb::env_wave_step<K, EG>(env, g0, lane, reinterpret_cast<uint32_t*>(lds) + wave * ENV_WORDS, uid, g0 / EG);
     }
   }
   HB_FSTAMP_REAL(15);
+}
+
+template <bool F16>
+__global__ __launch_bounds__(FNT) void actor_fused_kernel(const FusedArgs a) {
+  actor_fused_body<F16, void, 16>(a);
+}
+
+// `env` is read by the body's env tail straight from the kernel-argument segment (see there)
+template <bool F16, class K, int EG>
+__global__ __launch_bounds__(FNT) void actor_env_fused_kernel(const FusedArgs a, const hb::EnvArgs env) {
+  (void)env;
+  actor_fused_body<F16, K, EG>(a);
 }
 
 // ---- packer: effective weights (bf16, row-major, possibly padded GEMM operands) -> the fragment-major copies
@@ -729,16 +773,19 @@ int hb_actor_fused_q_stamped(const uint32_t* obs_bits_dev, int64_t n_rows, int32
 }
 #endif
 
-static int fused_launch(const uint32_t* obs_bits_dev, int64_t n_rows, int32_t obs_len, const void* w1f_dev, const float* b1f_dev,
-                        const void* w2f_dev, const float* b2f_dev, const float* support_dev, int32_t hidden, int32_t n_actions,
-                        int32_t n_atoms, float* q_dev, unsigned long long* stamps_dev, const FusedSelect* sel, int32_t dtype, void* stream) {
+// Validates the arguments and fills the kernel's; *launch = false: nothing to do (no rows)
+static int fused_args(const uint32_t* obs_bits_dev, int64_t n_rows, int32_t obs_len, const void* w1f_dev, const float* b1f_dev,
+                      const void* w2f_dev, const float* b2f_dev, const float* support_dev, int32_t hidden, int32_t n_actions,
+                      int32_t n_atoms, float* q_dev, unsigned long long* stamps_dev, const FusedSelect* sel, int32_t dtype, FusedArgs& a,
+                      bool* launch) {
+  *launch = false;
   if (dtype != 1 && dtype != 2) return fail(HB_ERR_INVALID, "dtype must be 1 (bf16) or 2 (f16)");
   if (!obs_bits_dev || !w1f_dev || !b1f_dev || !w2f_dev || !b2f_dev || !support_dev || !q_dev) return fail(HB_ERR_INVALID, "null argument");
   if (!hb_actor_fused_supported(obs_len, hidden, n_actions, n_atoms)) return fail(HB_ERR_INVALID, "shape not covered by the fused actor kernel");
   if (n_rows <= 0) return HB_OK;
   if (!aligned16(w1f_dev) || !aligned16(w2f_dev) || !aligned16(b1f_dev) || !aligned16(b2f_dev))
     return fail(HB_ERR_ALIGN, "w1f / w2f / b1f / b2f must be 16-byte aligned");
-  FusedArgs a{};
+  a = FusedArgs{};
   a.obs = obs_bits_dev; a.m = n_rows; a.words = (obs_len + 31) / 32; a.s1 = 2 * ((obs_len + 63) / 64);
   a.w1f = static_cast<const uint4*>(w1f_dev); a.b1 = b1f_dev; a.w2f = static_cast<const uint4*>(w2f_dev); a.b2 = b2f_dev;
   a.support = support_dev; a.q = q_dev; a.n_actions = n_actions; a.n_pass = passes_for(n_actions);
@@ -747,6 +794,19 @@ static int fused_launch(const uint32_t* obs_bits_dev, int64_t n_rows, int32_t ob
     a.legal = sel->legal; a.actions = sel->actions; a.epsilon = sel->epsilon; a.seed = sel->seed; a.draw = sel->draw;
     a.first_gid = sel->first_gid;
   }
+  *launch = true;
+  return HB_OK;
+}
+
+static int fused_launch(const uint32_t* obs_bits_dev, int64_t n_rows, int32_t obs_len, const void* w1f_dev, const float* b1f_dev,
+                        const void* w2f_dev, const float* b2f_dev, const float* support_dev, int32_t hidden, int32_t n_actions,
+                        int32_t n_atoms, float* q_dev, unsigned long long* stamps_dev, const FusedSelect* sel, int32_t dtype, void* stream) {
+  FusedArgs a;
+  bool go = false;
+  if (int rc = fused_args(obs_bits_dev, n_rows, obs_len, w1f_dev, b1f_dev, w2f_dev, b2f_dev, support_dev, hidden, n_actions, n_atoms, q_dev,
+                          stamps_dev, sel, dtype, a, &go))
+    return rc;
+  if (!go) return HB_OK;
   const dim3 grid(static_cast<unsigned>((n_rows + FM - 1) / FM));
   if (dtype == 2) hipLaunchKernelGGL(actor_fused_kernel<true>, grid, dim3(FNT), 0, static_cast<hipStream_t>(stream), a);
   else hipLaunchKernelGGL(actor_fused_kernel<false>, grid, dim3(FNT), 0, static_cast<hipStream_t>(stream), a);
@@ -755,3 +815,63 @@ static int fused_launch(const uint32_t* obs_bits_dev, int64_t n_rows, int32_t ob
 }
 
 }  // extern "C"
+
+namespace {
+
+// ---- hb_actor_fused_act_step (env_api.hip): the policy kernel with the env step as its tail ----------------------------------
+// Env configurations served (the one-kernel actor's benched games): Hanabi-Full, 2 and 5 players. Every other one keeps the two
+// launches (hb_actor_fused_act + hb_env_step_packed).
+using ActEnvFull2 = hb::Cfg<2, 5, 5, 5, 8, 3>;
+using ActEnvFull5 = hb::Cfg<5, 5, 5, 4, 8, 3>;
+constexpr int ENV_EG = 16;   // games per wavefront of the env tail: 8 wavefronts x 16 = the workgroup's 128 rows
+
+template <class K>
+static bool is_cfg(const hb::EnvVariant& v) {
+  return v.P == K::P && v.C == K::C && v.R == K::R && v.H == K::H && v.INFO == K::INFO && v.LIFE == K::LIFE;
+}
+
+template <bool F16, class K>
+static void launch_act_env(const FusedArgs& a, const hb::EnvArgs& env, dim3 grid, hipStream_t stream) {
+  if (env.ev_start && env.ev_stop)
+    hipExtLaunchKernelGGL((actor_env_fused_kernel<F16, K, ENV_EG>), grid, dim3(FNT), 0, stream, env.ev_start, env.ev_stop, 0, a, env);
+  else
+    hipLaunchKernelGGL((actor_env_fused_kernel<F16, K, ENV_EG>), grid, dim3(FNT), 0, stream, a, env);
+}
+
+}  // namespace
+
+namespace hb {
+
+bool actor_env_fused_supported(const EnvVariant& v) { return is_cfg<ActEnvFull2>(v) || is_cfg<ActEnvFull5>(v); }
+
+int actor_env_fused_launch(const uint32_t* obs_bits_dev, const int8_t* legal_dev, int64_t n_rows, int32_t obs_len, const void* w1f_dev,
+                           const float* b1f_dev, const void* w2f_dev, const float* b2f_dev, const float* support_dev, int32_t hidden,
+                           int32_t n_actions, int32_t n_atoms, float* q_dev, float epsilon, uint64_t seed, uint64_t draw,
+                           int64_t first_game_id, int32_t* actions_dev, int32_t dtype, const EnvArgs& env, const EnvVariant& var,
+                           void* stream) {
+  if (!legal_dev || !actions_dev) return fail(HB_ERR_INVALID, "null argument");
+  if (!actor_env_fused_supported(var)) return fail(HB_ERR_INVALID, "no fused policy + env kernel for this game configuration");
+  if (n_rows != env.n) return fail(HB_ERR_INVALID, "n_rows (%lld) must equal the env's game count (%lld)", static_cast<long long>(n_rows), env.n);
+  if (n_actions != var.n_actions || obs_len != var.obs_len) return fail(HB_ERR_INVALID, "actor shape does not match the env");
+  const FusedSelect sel{legal_dev, actions_dev, epsilon, seed, draw, first_game_id};
+  FusedArgs a;
+  bool go = false;
+  if (int rc = fused_args(obs_bits_dev, n_rows, obs_len, w1f_dev, b1f_dev, w2f_dev, b2f_dev, support_dev, hidden, n_actions, n_atoms, q_dev,
+                          nullptr, &sel, dtype, a, &go))
+    return rc;
+  if (!go) return HB_OK;
+  const dim3 grid(static_cast<unsigned>((n_rows + FM - 1) / FM));
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool f16 = dtype == 2;
+  if (is_cfg<ActEnvFull2>(var)) {
+    if (f16) launch_act_env<true, ActEnvFull2>(a, env, grid, st);
+    else launch_act_env<false, ActEnvFull2>(a, env, grid, st);
+  } else {
+    if (f16) launch_act_env<true, ActEnvFull5>(a, env, grid, st);
+    else launch_act_env<false, ActEnvFull5>(a, env, grid, st);
+  }
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+}  // namespace hb

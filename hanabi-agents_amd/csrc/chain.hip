@@ -48,6 +48,17 @@ int hb_chain_run(const hb_cmd* cmds, int32_t count, const int64_t* vars_i, const
       case HB_CMD_ACTOR_FUSED_ACT:   // vars_i[var] = draw counter, vars_f[fvar] = epsilon
         if (!vi || !vf) return fail(HB_ERR_INVALID, "command %d: hb_actor_fused_act needs its draw and epsilon variables", k);
         // i[7]: operand dtype of the weight copies (0 or 1 = bf16, 2 = f16): hb_actor_fused_act_dt
+        if (c.p[9]) {   // p[9..14]: the env and its step outputs: the env step runs as the policy kernel's tail, in place
+          rc = hb_actor_fused_act_step(static_cast<hb_env*>(c.p[9]), static_cast<const uint32_t*>(c.p[0]), static_cast<const int8_t*>(c.p[1]),
+                                       c.i[0], static_cast<int32_t>(c.i[1]), c.p[2], static_cast<const float*>(c.p[3]), c.p[4],
+                                       static_cast<const float*>(c.p[5]), static_cast<const float*>(c.p[6]), static_cast<int32_t>(c.i[2]),
+                                       static_cast<int32_t>(c.i[3]), static_cast<int32_t>(c.i[4]), static_cast<float*>(c.p[7]),
+                                       static_cast<float>(vf[0]), static_cast<uint64_t>(c.i[5]), static_cast<uint64_t>(vi[0]), c.i[6],
+                                       static_cast<int32_t*>(c.p[8]), c.i[7] == 2 ? 2 : 1, static_cast<uint32_t*>(c.p[0]),
+                                       static_cast<int8_t*>(c.p[1]), static_cast<float*>(c.p[10]), static_cast<int8_t*>(c.p[11]),
+                                       static_cast<float*>(c.p[12]), static_cast<int8_t*>(c.p[13]), static_cast<int8_t*>(c.p[14]), c.stream);
+          break;
+        }
         rc = hb_actor_fused_act_dt(static_cast<const uint32_t*>(c.p[0]), static_cast<const int8_t*>(c.p[1]), c.i[0],
                                    static_cast<int32_t>(c.i[1]), c.p[2], static_cast<const float*>(c.p[3]), c.p[4],
                                    static_cast<const float*>(c.p[5]), static_cast<const float*>(c.p[6]), static_cast<int32_t>(c.i[2]),

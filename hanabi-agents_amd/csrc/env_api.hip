@@ -242,7 +242,8 @@ static int refill_async(hb_env* e, void* stream) {
   return HB_OK;
 }
 
-static int launch(hb_env* e, hb::EnvArgs& a, void* stream) {
+// the env's own fields of a launch's arguments
+static void prepare(hb_env* e, hb::EnvArgs& a) {
   a.state = e->state;
   a.decks = e->decks;
   a.next_deck = e->next_deck;
@@ -259,6 +260,10 @@ static int launch(hb_env* e, hb::EnvArgs& a, void* stream) {
   }
   a.ev_start = e->ev_start;
   a.ev_stop = e->ev_stop;
+}
+
+static int launch(hb_env* e, hb::EnvArgs& a, void* stream) {
+  prepare(e, a);
   // automatic: 32 games per wavefront when only the bit-packed rows leave the kernel and the batch is >= 32 768 games (one
   // wavefront per SIMD there, every phase wider), 16 otherwise (int8 rows: their stores want two wavefronts per SIMD; small
   // batches: more wavefronts). Measured r02, packed: 262 144 games 26.9 us (32) vs 36.2 us (16); 32 768 games 9.2 vs 9.7 us alone
@@ -401,6 +406,36 @@ int hb_env_step_select_packed(hb_env* e, const float* q_dev, const int8_t* sel_l
   if (int rc = launch(e, a, stream)) return rc;
   return refill_async(e, stream);
 }
+
+// hb_actor_fused_act followed by hb_env_step_packed as ONE launch: every workgroup of the policy kernel steps its own 128 games with
+// the moves it has just selected. Around the launch everything hb_env_step_packed does: pool join, refill cadence, counters, events.
+int hb_actor_fused_act_step(hb_env* e, const uint32_t* obs_bits_dev, const int8_t* legal_dev, int64_t n_rows, int32_t obs_len,
+                            const void* w1f_dev, const float* b1f_dev, const void* w2f_dev, const float* b2f_dev, const float* support_dev,
+                            int32_t hidden, int32_t n_actions, int32_t n_atoms, float* q_dev, float epsilon, uint64_t seed, uint64_t draw,
+                            int64_t first_game_id, int32_t* actions_dev, int32_t dtype, uint32_t* obs_bits_out_dev, int8_t* legal_out_dev,
+                            float* reward_dev, int8_t* terminal_dev, float* agent_reward_dev, int8_t* agent_step_type_dev,
+                            int8_t* score_dev, void* stream) {
+  if (!e) return fail(HB_ERR_INVALID, "null env");
+  if (int rc = check_out_packed(obs_bits_out_dev, nullptr, legal_out_dev)) return rc;
+  hb::EnvArgs a{};
+  a.mode = hb::MODE_STEP;
+  a.obs_bits = obs_bits_out_dev;
+  a.legal = legal_out_dev;
+  a.reward = reward_dev;
+  a.terminal = terminal_dev;
+  a.agent_reward = agent_reward_dev;
+  a.agent_step_type = agent_step_type_dev;
+  a.score = score_dev;
+  prepare(e, a);
+  if (int rc = join_refill(e, stream)) return rc;
+  if (int rc = hb::actor_env_fused_launch(obs_bits_dev, legal_dev, n_rows, obs_len, w1f_dev, b1f_dev, w2f_dev, b2f_dev, support_dev, hidden,
+                                          n_actions, n_atoms, q_dev, epsilon, seed, draw, first_game_id, actions_dev, dtype, a, *e->var,
+                                          stream))
+    return rc;
+  return refill_async(e, stream);
+}
+
+int hb_actor_fused_step_supported(const hb_env* e) { return e && hb::actor_env_fused_supported(*e->var) ? 1 : 0; }
 
 #ifdef HB_STAMPS
 // diagnostic library only: step once with per-wavefront phase stamps written to stamps_dev

@@ -79,12 +79,12 @@ struct EnvArgs {
     unsigned long long hb_t_;                                                                        \
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(hb_t_)::"memory");                    \
     __builtin_amdgcn_sched_barrier(0);                                                               \
-    if (a.stamps && lane == 0) a.stamps[(static_cast<long long>(blockIdx.x) * 4 + wave) * 12 + (slot)] = hb_t_; \
+    if (a.stamps && lane == 0) a.stamps[wslot * 12 + (slot)] = hb_t_; \
   } while (0)
 #define HB_STAMP_REAL(slot)                                                                          \
   do {                                                                                               \
     if (a.stamps && lane == 0)                                                                       \
-      a.stamps[(static_cast<long long>(blockIdx.x) * 4 + wave) * 12 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
+      a.stamps[wslot * 12 + (slot)] = __builtin_amdgcn_s_memrealtime(); \
   } while (0)
 #else
 #define HB_STAMP(slot) do { } while (0)
@@ -324,23 +324,25 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// LDS words one wavefront's env step needs for G games: state rows, observation bit rows, legal bit rows
 template <class K, int G>
-__global__ __launch_bounds__(256) void env_kernel(const EnvArgs a) {
+constexpr int env_lds_words() { return G * (K::SWP + K::NWP + K::LW); }
+
+// The env step of ONE wavefront: games [g0, g0 + G) of the batch, lane g < G owning game g0 + g. `srow` is the wavefront's own LDS
+// slice of env_lds_words<K, G>() words, `uid_in` the lane's move (MODE_STEP; ignored by the other modes, and by lanes past the
+// batch), `wslot` the wavefront's slot in the per-wavefront stats (g0 / G). Shared by env_kernel and by the one-kernel actor's
+// fused env tail (actor_fused.hip), so there is one copy of the rules.
+template <class K, int G>
+__device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, int lane, uint32_t* const srow, int uid_in,
+                                              long long wslot) {
   constexpr int P = K::P, C = K::C, R = K::R, H = K::H;
   // (Round 3 measured an encoder on all 64 lanes — 64 / G lanes per game, the knowledge slots and the other hands dealt out
   //  over them and OR-ed into the bit row with ds_or_b32 — against this lane-per-game one: bit-identical and SLOWER, 10.5 vs
   //  9.7 us at G = 16 and 10.8 vs 9.2 us at G = 32 (32 768 games): the LDS atomics and the two extra phases cost more than the
   //  ~25 % of the encoder's instructions they save. DESIGN section 4.)
   constexpr int LPG = 1;
-  constexpr int PER_WAVE = G * (K::SWP + K::NWP + K::LW);
-  __shared__ uint32_t lds[4 * PER_WAVE];
-
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  uint32_t* const srow = lds + wave * PER_WAVE;
   uint32_t* const obits = srow + G * K::SWP;
   uint32_t* const lbits = obits + G * K::NWP;
-  const long long g0 = (static_cast<long long>(blockIdx.x) * 4 + wave) * G;
   const long long left = a.n - g0;
   const int nvalid = left <= 0 ? 0 : (left < G ? static_cast<int>(left) : G);
   const int mode = a.mode;
@@ -350,7 +352,6 @@ __global__ __launch_bounds__(256) void env_kernel(const EnvArgs a) {
   // the per-game inputs are requested first so their HBM latency hides under the state copy
   const bool active = lane < nvalid && lane < G;
   const long long gi = g0 + lane;
-  int uid_in = 0;
   bool mask_in = true;
   // This game's pre-shuffled next deck (64 B), used only on a re-deal. Round 3: fetched only by games that CAN end with this
   // move (one life left, deck empty, or one card short of a perfect score: ~1.5 % of the games re-deal in a step, rounds 1-2
@@ -359,7 +360,6 @@ __global__ __launch_bounds__(256) void env_kernel(const EnvArgs a) {
   uint4 nd[4] = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
   const uint4* const ndp = reinterpret_cast<const uint4*>(a.next_deck + gi * NEXT_DECK_BYTES);
   if (active) {
-    if (mode == MODE_STEP) uid_in = a.sel_q ? select_action<K::A>(a, gi) : a.actions[gi];
     if (mode == MODE_RESET && a.mask) mask_in = a.mask[gi] != 0;
     if ((mode == MODE_RESET && mask_in) || (mode == MODE_STEP && (a.flags & 0x100))) {   // (0x100: measurement aid, fetch always)
       nd[0] = ndp[0]; nd[1] = ndp[1]; nd[2] = ndp[2]; nd[3] = ndp[3];
@@ -726,7 +726,7 @@ __global__ __launch_bounds__(256) void env_kernel(const EnvArgs a) {
       int sc = out_term ? out_score : 0;
       for (int o = 32; o > 0; o >>= 1) sc += __shfl_xor(sc, o);
       if (lane == 0) {
-        unsigned long long* slot = a.stats + 2 * (static_cast<long long>(blockIdx.x) * 4 + wave);
+        unsigned long long* slot = a.stats + 2 * wslot;
         atomicAdd(slot, static_cast<unsigned long long>(__popcll(ended)));
         atomicAdd(slot + 1, static_cast<unsigned long long>(sc));
       }
@@ -763,6 +763,19 @@ __global__ __launch_bounds__(256) void env_kernel(const EnvArgs a) {
   }
   HB_STAMP(9);
   HB_STAMP_REAL(11);
+}
+
+template <class K, int G>
+__global__ __launch_bounds__(256) void env_kernel(const EnvArgs a) {
+  __shared__ uint32_t lds[4 * env_lds_words<K, G>()];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const long long wslot = static_cast<long long>(blockIdx.x) * 4 + wave;
+  const long long g0 = wslot * G;
+  // the move is requested first so that its HBM latency hides under the state copy
+  int uid_in = 0;
+  if (a.mode == MODE_STEP && lane < G && g0 + lane < a.n) uid_in = a.sel_q ? select_action<K::A>(a, g0 + lane) : a.actions[g0 + lane];
+  env_wave_step<K, G>(a, g0, lane, lds + wave * env_lds_words<K, G>(), uid_in, wslot);
 }
 
 // Deck pool refill: regenerates next_deck[g] for every game whose flag is set. One wavefront scans 64 games
@@ -839,5 +852,14 @@ constexpr EnvVariant make_variant() {
   return EnvVariant{K::P, K::C, K::R, K::H, K::INFO, K::LIFE, K::OBS_LEN, K::A, K::D, K::SW,
                     &launch_env<K, 8>, &launch_env<K, 16>, &launch_env<K, 32>, &launch_env<K, 64>, &launch_refill<K>};
 }
+
+// The one-kernel actor with the env step as its tail (actor_fused.hip; hb_actor_fused_act_step): the configurations it is compiled
+// for, and its launch with the env arguments `env` prepared as for hb_env_step_packed (actions are the kernel's own selections)
+bool actor_env_fused_supported(const EnvVariant& v);
+int actor_env_fused_launch(const uint32_t* obs_bits_dev, const int8_t* legal_dev, int64_t n_rows, int32_t obs_len, const void* w1f_dev,
+                           const float* b1f_dev, const void* w2f_dev, const float* b2f_dev, const float* support_dev, int32_t hidden,
+                           int32_t n_actions, int32_t n_atoms, float* q_dev, float epsilon, uint64_t seed, uint64_t draw,
+                           int64_t first_game_id, int32_t* actions_dev, int32_t dtype, const EnvArgs& env, const EnvVariant& var,
+                           void* stream);
 
 }  // namespace hb

@@ -380,17 +380,23 @@ class FusedLearner:
             self._pack_tab = tab
         return self._pack_tab
 
-    def part2(self):
+    def part2(self, opt=True, pack=True):
+        """The optimizer step (opt) and the actor's weight copies behind it (pack); a caller may issue the two separately, in that
+        order (the early update's two graphs: the policy kernel reads only the copies, so only they wait for it)."""
         p = self.agent.params
         if self.adam_pack:
+            assert opt and pack, "hb_noisy_adam_multi_pack: the optimizer step and the copies are one launch"
             # one launch: optimizer step + the thin GEMMs' transposed online weights + the one-kernel actor's copies (set 0)
             K.check(K.lib().hb_noisy_adam_multi_pack(self._adam_table(), self._pack_table(), 4, K.dptr(self.step), 0.0, _DT[self.cd],
                                                      float(p.learning_rate), 0.9, 0.999, 3.125e-5, K.current_stream()))
             self._packed_in_part2 = True     # (the two-kernel actor form's copies: lazily, weights_updated() marks them)
             return
         # self.step was advanced by this update's loss kernel (part1): it already is this step's number
-        K.check(K.lib().hb_noisy_adam_multi(self._adam_table(), 4, K.dptr(self.step), 0.0, _DT[self.cd],
-                                            float(p.learning_rate), 0.9, 0.999, 3.125e-5, K.current_stream()))
+        if opt:
+            K.check(K.lib().hb_noisy_adam_multi(self._adam_table(), 4, K.dptr(self.step), 0.0, _DT[self.cd],
+                                                float(p.learning_rate), 0.9, 0.999, 3.125e-5, K.current_stream()))
+        if not pack:
+            return
         # Synchronous agent: the actor's weight copies follow Adam right here — on the learner's stream, inside the captured
         # update — instead of on the acting stream before the next policy call (round 2: two launches and ~12 us per step there).
         # Sound because an update starts only after its agent's last policy call has finished (`acted` event / same stream) and

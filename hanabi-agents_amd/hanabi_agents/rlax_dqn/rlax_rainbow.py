@@ -217,6 +217,7 @@ class DQNAgent:
         # rings have been read and act as soon as Adam has written the weights, instead of waiting for the whole update
         self.split_update = bool(self.actor_lag)
         self.two_graphs = False   # set_two_graphs()
+        self.adam_first = False   # set_two_graphs(adam_first=True): the optimizer step in the first graph
         self._pending_fills = []    # (start, rows) of inserts whose sum-tree leaves the NEXT update_begin() sets
         self.gathered_ev = None     # recorded when an update has finished reading the replay rings
         self.weights_ev = None      # recorded when an update's optimizer step is done (before its priority write-back)
@@ -687,15 +688,17 @@ class DQNAgent:
     # replay insert, policy and env step between the two calls, so the ~3.4 MB gradient exchange over xGMI hides
     # behind ~0.2 ms of independent work. With one rank the pair is exactly update() — and, under HIP graphs, the whole
     # update (Adam included) is one graph launched by update_begin(): do not let anything read the weights between the two.
-    def set_two_graphs(self, on=True):
+    def set_two_graphs(self, on=True, adam_first=False):
         """Capture the update as TWO graphs — everything that only READS the weights (forward, loss, backward), then the optimizer
         step with the weight packs — although no collective sits between them: a driver can then start the first half BEFORE this
         agent's policy call has finished (both only read the weights) and hold just the second half back (SelfPlaySession's
-        early update, hb_chain_run). Synchronous split-update agents only; results do not depend on it."""
-        on = bool(on)
-        if on != self.two_graphs:
+        early update, hb_chain_run). adam_first: the optimizer step goes into the FIRST graph too and only the weight copies the
+        one-kernel actor reads wait (the fused learner's Adam writes nothing that actor reads). Synchronous split-update agents
+        only; results do not depend on it."""
+        on, adam_first = bool(on), bool(adam_first)
+        if on != self.two_graphs or adam_first != self.adam_first:
             assert self._pending is None
-            self.two_graphs = on
+            self.two_graphs, self.adam_first = on, adam_first
             self._graph1 = self._graph2 = None
         return on
 
@@ -1064,10 +1067,19 @@ class DQNAgent:
                 self._update_part2(self._g_idx, self._g_prios)
             self._graph2 = None
             return
+        # Early update without a collective, adam_first (set_two_graphs): the optimizer step writes nothing the one-kernel actor
+        # reads (it reads only the packed copies), so Adam joins the first graph and only the copies wait for this agent's policy call
+        adam_early = (self._fl is not None and not self._fl.adam_pack and not self._collective() and self.two_graphs and self.adam_first
+                      and self._fl.actor is not None and self._fl.actor.fused and self.use_mfma_actor)
         with torch.cuda.graph(self._graph1, capture_error_mode="thread_local"):
             self.last_loss, self._g_idx, self._g_prios = self._update_part1()
+            if adam_early:
+                self._fl.part2(pack=False)
         with torch.cuda.graph(self._graph2, pool=self._graph1.pool(), capture_error_mode="thread_local"):
-            self._update_part2(self._g_idx, self._g_prios)
+            if adam_early:
+                self._fl.part2(opt=False)
+            else:
+                self._update_part2(self._g_idx, self._g_prios)
 
     def _collective_in_graph(self):
         import torch.distributed as dist

@@ -175,6 +175,9 @@ SIGNATURES = {
     "hb_actor_fused_pack_thin": (C.c_int, [_P, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _P]),
     "hb_actor_fused_q_dt": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P]),
     "hb_actor_fused_act_dt": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, C.c_float, _U64, _U64, _I64, _P, _I32, _P]),
+    "hb_actor_fused_act_step": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, C.c_float, _U64, _U64, _I64, _P,
+                                          _I32] + [_P] * 7 + [_P]),
+    "hb_actor_fused_step_supported": (C.c_int, [_P]),
     "hb_chain_run": (C.c_int, [C.POINTER(HbCmd), _I32, C.POINTER(_I64), C.POINTER(_F64)]),
     "hb_eval_counters": (C.c_int, [_CFG]),
     "hb_eval_tally": (C.c_int, [_CFG, _I64, _I32, _I32] + [_P] * 8 + [_P]),

@@ -93,16 +93,26 @@ class SelfPlaySession:
         # longer sits between one policy kernel and the next (0.115 -> see DESIGN section 8).
         self.early_update = (bool(early_update) and self.native_chain and self.learner_stream is not None
                              and os.environ.get("HB_EARLY_UPDATE", "1") != "0")   # (the variable: A/B measurements)
+        # One-call steps: the policy kernel with the env step as its tail (hb_actor_fused_act_step) for the games the library
+        # compiled it for (Hanabi-Full, 2 and 5 players); HB_FUSED_ENV_STEP=0 keeps two launches (A/B measurements). With it, the
+        # early update's optimizer step joins its first graph: `acted` now comes after the env step, and Adam writes nothing the
+        # policy kernel reads (only the weight copies behind it do). Without the fused step that order measured slower
+        # (0.116 vs 0.113 ms per step), so the two go together.
+        self.fuse_env_step = (os.environ.get("HB_FUSED_ENV_STEP", "1") != "0" and getattr(env, "packed", False)
+                              and env.device.type == "cuda" and self._fused_step_ok())
         if self.early_update:
             for a in agents:
                 if hasattr(a, "set_two_graphs") and getattr(a, "split_update", False) and not getattr(a, "actor_lag", 0):
-                    a.set_two_graphs(True)
+                    a.set_two_graphs(True, adam_first=self.fuse_env_step)
         self._inserted_ev = {}
         self._acted_early = os.environ.get("HB_ACTED_BEFORE_ENV", "1") != "0"
         self.select_in_env_steps = 0   # steps whose moves were picked inside the env kernel (hb_env_step_select_packed)
         self._chains = {}        # seat -> _Chain
         self.native_steps = 0
         self._evaluators = {}    # (n_games, seed) -> hanabi_hip.evaluate.Evaluator
+
+    def _fused_step_ok(self):
+        return bool(K.lib().hb_actor_fused_step_supported(self.env.h))
 
     # ---- one host call per step ----------------------------------------------------------------------------------------------
     def _chain_for(self, seat, agent, train, raw):
@@ -482,23 +492,35 @@ class _Chain:
         # synchronous agent: the policy waits for the weights of this agent's last update; actor_lag = 1: for the launch that packed
         # the weight set it reads (update before last: long past)
         put(K.CMD_WAIT_EVENT, A, [(fl.packed_ev[wset] if self.lag else agent.weights_ev).h], cond=5)
-        put(K.CMD_ACTOR_FUSED_ACT, A,
-            [env.net_obs.data_ptr(), env.legal.data_ptr(), f[0], f[1], f[2], f[3], agent._support0.data_ptr(), act.q.data_ptr(),
-             session._act_buf[seat].data_ptr()],
-            [env.n, act.obs_len, act.hidden, act.n_actions, act.n_atoms, agent.params.seed + 0x9E3779B9, agent.first_game_id, act._dt],
-            var=1, fvar=0)
-        # `acted` (the policy has read its weights) is recorded BEFORE the env step unless HB_ACTED_BEFORE_ENV=0
-        env_args = [env.h, session._act_buf[seat].data_ptr(), env.obs_bits.data_ptr(), None, env.legal.data_ptr(), env.reward.data_ptr(),
-                    env.terminal.data_ptr(), env.agent_reward.data_ptr(), env.agent_step_type.data_ptr(), env.score.data_ptr()]
-        if session._acted_early:
+        act_ints = [env.n, act.obs_len, act.hidden, act.n_actions, act.n_atoms, agent.params.seed + 0x9E3779B9, agent.first_game_id, act._dt]
+        # One launch for the policy and the env step (hb_actor_fused_act_step) where the library has the fused kernel for the game:
+        # each policy workgroup steps its own 128 games right after selecting their moves. `acted` then follows the env step too,
+        # which the early update absorbs (its optimizer step no longer waits for `acted`); actor_lag = 1 has no early update and
+        # its whole update would start an env step later (0.119 vs 0.109 ms per step): it keeps the two launches.
+        self.fused_step = session.fuse_env_step and early and env.net_obs.data_ptr() == env.obs_bits.data_ptr()
+        act_ptrs = [env.net_obs.data_ptr(), env.legal.data_ptr(), f[0], f[1], f[2], f[3], agent._support0.data_ptr(), act.q.data_ptr(),
+                    session._act_buf[seat].data_ptr()]
+        if self.fused_step:   # (p[9..14]: the env and its outputs; observation and legal rows are rewritten in place)
+            put(K.CMD_ACTOR_FUSED_ACT, A,
+                act_ptrs + [env.h, env.reward.data_ptr(), env.terminal.data_ptr(), env.agent_reward.data_ptr(), env.agent_step_type.data_ptr(),
+                            env.score.data_ptr()],
+                act_ints, var=1, fvar=0)
             put(K.CMD_RECORD_EVENT, A, [acted.h])
-            put(K.CMD_ENV_STEP_PACKED, A, env_args)
         else:
-            put(K.CMD_ENV_STEP_PACKED, A, env_args)
-            put(K.CMD_RECORD_EVENT, A, [acted.h])
+            put(K.CMD_ACTOR_FUSED_ACT, A, act_ptrs, act_ints, var=1, fvar=0)
+            # `acted` (the policy has read its weights) is recorded BEFORE the env step unless HB_ACTED_BEFORE_ENV=0
+            env_args = [env.h, session._act_buf[seat].data_ptr(), env.obs_bits.data_ptr(), None, env.legal.data_ptr(), env.reward.data_ptr(),
+                        env.terminal.data_ptr(), env.agent_reward.data_ptr(), env.agent_step_type.data_ptr(), env.score.data_ptr()]
+            if session._acted_early:
+                put(K.CMD_RECORD_EVENT, A, [acted.h])
+                put(K.CMD_ENV_STEP_PACKED, A, env_args)
+            else:
+                put(K.CMD_ENV_STEP_PACKED, A, env_args)
+                put(K.CMD_RECORD_EVENT, A, [acted.h])
         # ---- learner stream. Early update: everything that only READS the weights starts as soon as the rows are in the ring —
         # beside this agent's own policy kernel — and only what WRITES them (the optimizer step and the actor's weight copies;
-        # actor_lag: only the copies) waits for `acted`. Otherwise the whole update waits for `acted`.
+        # actor_lag: only the copies; with the fused env step also only the copies: Adam is in graph 1) waits for `acted`. Otherwise
+        # the whole update waits for `acted`.
         put(K.CMD_WAIT_EVENT, Ls, [(inserted if early else acted).h])
         put(K.CMD_TREE_FILL_RANGE, Ls, [buf.sum_tree.h, buf._max_priority.data_ptr()], var=2)
         g = fl._sg_call[3]              # hb_per_sample_gather's arguments in declaration order

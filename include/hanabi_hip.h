@@ -619,6 +619,19 @@ int hb_actor_fused_act_dt(const uint32_t* obs_bits_dev, const int8_t* legal_dev,
                           const void* w1f_dev, const float* b1f_dev, const void* w2f_dev, const float* b2f_dev,
                           const float* support_dev, int32_t hidden, int32_t n_actions, int32_t n_atoms, float* q_dev, float epsilon,
                           uint64_t seed, uint64_t draw, int64_t first_game_id, int32_t* actions_dev, int32_t dtype, void* stream);
+/* hb_actor_fused_act_dt followed by hb_env_step_packed(env, actions_dev, obs_bits_out_dev, NULL, legal_out_dev, ...) as ONE launch:
+ * each workgroup of the policy kernel steps its own 128 games with the moves it has just selected, bit for bit what the two calls
+ * compute. Around the launch it does what hb_env_step_packed does (deck-pool join and refill cadence, illegal-move and episode
+ * counters, hb_env_set_profile_events timing). The observation / legal inputs may be the output buffers themselves (in place).
+ * n_rows must be the env's game count. Compiled for Hanabi-Full with 2 and 5 players (hb_actor_fused_step_supported); other
+ * configurations: HB_ERR_INVALID.                                                                                           */
+int hb_actor_fused_act_step(hb_env* env, const uint32_t* obs_bits_dev, const int8_t* legal_dev, int64_t n_rows, int32_t obs_len,
+                            const void* w1f_dev, const float* b1f_dev, const void* w2f_dev, const float* b2f_dev,
+                            const float* support_dev, int32_t hidden, int32_t n_actions, int32_t n_atoms, float* q_dev, float epsilon,
+                            uint64_t seed, uint64_t draw, int64_t first_game_id, int32_t* actions_dev, int32_t dtype,
+                            uint32_t* obs_bits_out_dev, int8_t* legal_out_dev, float* reward_dev, int8_t* terminal_dev,
+                            float* agent_reward_dev, int8_t* agent_step_type_dev, int8_t* score_dev, void* stream);
+int hb_actor_fused_step_supported(const hb_env* env); /* 1: hb_actor_fused_act_step serves this env's configuration */
 
 /* ---- greedy evaluation (csrc/eval.hip) ------------------------------------------------------------------------------------
  * A fixed set of n_games evaluation games (auto-reset off, lock-step: turn t is seat t mod P in every game) is played to the
@@ -658,7 +671,9 @@ enum {
   HB_CMD_WAIT_EVENT = 1,       /* hb_stream_wait_event(stream, p[0]) */
   HB_CMD_RECORD_EVENT = 2,     /* hb_event_record(p[0], stream) */
   HB_CMD_REPLAY_INSERT = 3,    /* p[0..11], i[0..3] = n, obs_len (bytes per row), n_actions, capacity */
-  HB_CMD_ACTOR_FUSED_ACT = 4,  /* p = obs_bits, legal, w1f, b1f, w2f, b2f, support, q, actions; i = n_rows, obs_len, hidden, A, atoms, seed, first_gid */
+  HB_CMD_ACTOR_FUSED_ACT = 4,  /* p = obs_bits, legal, w1f, b1f, w2f, b2f, support, q, actions; i = n_rows, obs_len, hidden, A, atoms, seed, first_gid;
+                                  p[9] != NULL: hb_actor_fused_act_step instead, p[9..14] = env, reward, terminal, agent_reward,
+                                  agent_step_type, score, the step's observation / legal rows rewritten in place (p[0], p[1]) */
   HB_CMD_ENV_STEP_PACKED = 5,  /* p = env, actions, obs_bits, obs, legal, reward, terminal, agent_reward, agent_step_type, score */
   HB_CMD_TREE_FILL_RANGE = 6,  /* p = tree, value */
   HB_CMD_PER_SAMPLE_GATHER = 7,/* p = tree, counter, idx, prob, obs_tm1, obs_t, act, rew, term, x, act_out, rew_out, term_out, disc_out, size_wp;

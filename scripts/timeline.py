@@ -12,9 +12,12 @@ f = sorted(glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
 rows = list(csv.DictReader(open(f)))
 t = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Queue_Id"], r["Kernel_Name"]) for r in rows]
 t.sort()
-envs = [x for x in t if "env_kernel" in x[3]]
+# One launch per env step marks the steps: the env kernel, or, where the policy kernel steps the env itself
+# (hb_actor_fused_act_step), that fused kernel (the stand-alone env kernel then only runs in bench.py's measurements after the loop)
+STEP = "actor_env_fused_kernel" if any("actor_env_fused_kernel" in x[3] for x in t) else "env_kernel"
+envs = [x for x in t if STEP in x[3]]
 # the self-play loop's env launches come first (set-up, warm-up, timed region), stand-alone measurements after them:
-# take launches a..b of the env kernel (default 150..300) as the steady-state window
+# take launches a..b of the step kernel (default 150..300) as the steady-state window
 a, b = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (150, 300)
 lo, hi = envs[a][0], envs[b][0]
 win = [x for x in t if lo <= x[0] < hi]
@@ -23,7 +26,8 @@ print(f"{f}: {len(t)} dispatches, window {span:.0f} us with {len(win)} dispatche
 byq = defaultdict(list)
 for x in win:
     byq[x[2]].append(x)
-nenv = sum(1 for x in win if "env_kernel" in x[3])
+nenv = sum(1 for x in win if STEP in x[3])
+print(f"steps counted by {STEP} launches")
 print(f"env steps in window: {nenv} -> {span / max(nenv, 1):.1f} us per step")
 for q, xs in sorted(byq.items(), key=lambda kv: -len(kv[1])):
     busy = sum(e - s for s, e, _, _ in xs) / 1e3
