@@ -583,6 +583,21 @@ __global__ __launch_bounds__(FNT) void actor_env_fused_kernel(const FusedArgs a,
   actor_fused_body<F16, K, EG>(a);
 }
 
+// hb_actor_fused_act_grouped: workgroup t runs the body above on its 128 rows with the network of its own tile descriptor. The
+// descriptor is uniform over the workgroup (scalar loads); `a` keeps the layout every other launch uses, and the descriptor comes
+// as a separate argument after it. first_gid is rebased so that row 128 t of the launch takes the tile's first game id, exactly as
+// row 0 of an hb_actor_fused_act_dt launch over the tile's rows alone would.
+template <bool F16>
+__global__ __launch_bounds__(FNT) void actor_fused_grouped_kernel(const FusedArgs a, const hb_fused_tile* __restrict__ tiles) {
+  const hb_fused_tile& t = tiles[blockIdx.x];
+  if (!t.active) return;
+  FusedArgs b = a;
+  b.w1f = static_cast<const uint4*>(t.w1f); b.b1 = t.b1f; b.w2f = static_cast<const uint4*>(t.w2f); b.b2 = t.b2f;
+  b.support = t.support;
+  b.first_gid = t.first_game_id - static_cast<long long>(blockIdx.x) * FM;
+  actor_fused_body<F16, void, 16>(b);
+}
+
 // ---- packer: effective weights (bf16, row-major, possibly padded GEMM operands) -> the fragment-major copies
 struct PackArgs {
   const __hip_bfloat16* w1; int w1_ld;
@@ -761,6 +776,28 @@ int hb_actor_fused_act(const uint32_t* obs_bits_dev, const int8_t* legal_dev, in
                        int64_t first_game_id, int32_t* actions_dev, void* stream) {
   return hb_actor_fused_act_dt(obs_bits_dev, legal_dev, n_rows, obs_len, w1f_dev, b1f_dev, w2f_dev, b2f_dev, support_dev, hidden,
                                n_actions, n_atoms, q_dev, epsilon, seed, draw, first_game_id, actions_dev, 1, stream);
+}
+
+int hb_actor_fused_act_grouped(const hb_fused_tile* tiles_dev, int64_t n_rows, const uint32_t* obs_bits_dev, const int8_t* legal_dev,
+                               int32_t obs_len, int32_t hidden, int32_t n_actions, int32_t n_atoms, float* q_dev, float epsilon,
+                               uint64_t seed, uint64_t draw, int32_t* actions_dev, int32_t dtype, void* stream) {
+  if (dtype != 1 && dtype != 2) return fail(HB_ERR_INVALID, "dtype must be 1 (bf16) or 2 (f16)");
+  if (!tiles_dev || !obs_bits_dev || !legal_dev || !q_dev || !actions_dev) return fail(HB_ERR_INVALID, "null argument");
+  if (!hb_actor_fused_supported(obs_len, hidden, n_actions, n_atoms)) return fail(HB_ERR_INVALID, "shape not covered by the fused actor kernel");
+  if (n_actions > 64) return fail(HB_ERR_INVALID, "n_actions must be 1..64 for the fused selection");
+  if (n_rows < 0 || n_rows % FM) return fail(HB_ERR_INVALID, "n_rows (%lld) must be a multiple of %d: one tile descriptor per %d rows",
+                                             static_cast<long long>(n_rows), FM, FM);
+  if (n_rows / FM > 0x7fffffff) return fail(HB_ERR_INVALID, "too many tiles");
+  if (n_rows == 0) return HB_OK;
+  FusedArgs a{};
+  a.obs = obs_bits_dev; a.m = n_rows; a.words = (obs_len + 31) / 32; a.s1 = 2 * ((obs_len + 63) / 64);
+  a.q = q_dev; a.n_actions = n_actions; a.n_pass = passes_for(n_actions);
+  a.legal = legal_dev; a.actions = actions_dev; a.epsilon = epsilon; a.seed = seed; a.draw = draw;
+  const dim3 grid(static_cast<unsigned>(n_rows / FM));
+  if (dtype == 2) hipLaunchKernelGGL(actor_fused_grouped_kernel<true>, grid, dim3(FNT), 0, static_cast<hipStream_t>(stream), a, tiles_dev);
+  else hipLaunchKernelGGL(actor_fused_grouped_kernel<false>, grid, dim3(FNT), 0, static_cast<hipStream_t>(stream), a, tiles_dev);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
 }
 
 #ifdef HB_STAMPS

@@ -39,56 +39,70 @@ __device__ __forceinline__ void wave_add(unsigned int* c, unsigned long long mas
 // Grid-stride over the games (the loop bound is uniform across the workgroup, so every lane takes part in every ballot).
 // Each wave adds its ballot counts into the workgroup's LDS copy of the counters; the workgroup then issues one global atomic
 // per nonzero counter.
+// A macro over the arguments `a` of the enclosing kernel, so that eval_tally_kernel expands to exactly the code it was written as
+// (its code object is unchanged) and the grouped kernel shares it.
+#define HB_TALLY_BODY                                                                                                                             \
+  __shared__ unsigned int lc[kMaxCounters];                                                                                                       \
+  const int lane = threadIdx.x & 63;                                                                                                              \
+  const int B = a.bins, nc = 2 + B + 5 * a.P;                                                                                                     \
+  for (int i = threadIdx.x; i < nc; i += 256) lc[i] = 0;                                                                                          \
+  __syncthreads();                                                                                                                                \
+  for (long long base = static_cast<long long>(blockIdx.x) * 256; base < a.n; base += static_cast<long long>(gridDim.x) * 256) {                  \
+    const long long g = base + threadIdx.x;                                                                                                       \
+    int kind = -1, bin = 0;                                                                                                                       \
+    bool ended = false, misplay = false, bomb = false;                                                                                            \
+    if (g < a.n) {                                                                                                                                \
+      const uint8_t st = a.done[g];                                                                                                               \
+      if (!(st & 0x80u)) {   /* a game counts only while it is live: finished games' env outputs are never read */                                \
+        const int u = a.actions[g];                                                                                                               \
+        if (u >= 0 && u < a.A) kind = u < a.H ? 0 : u < 2 * a.H ? 1 : u < 2 * a.H + (a.P - 1) * a.C ? 2 : 3;   /* App. A.2 order */               \
+        misplay = kind == 1 && a.reward[g] <= 0.f;   /* a successful play always scores +1; a misplay 0, or -score at a bomb-out */               \
+        const int lost = (st & 0x7f) + (misplay ? 1 : 0);                                                                                         \
+        ended = a.terminal[g] != 0;                                                                                                               \
+        if (ended) {                                                                                                                              \
+          const int sc = a.score[g];   /* 0 after a bomb-out (hb_env_step) */                                                                     \
+          bin = sc < 0 ? 0 : sc > B - 1 ? B - 1 : sc;                                                                                             \
+          bomb = lost >= a.max_life;                                                                                                              \
+          a.final_score[g] = static_cast<int8_t>(sc);                                                                                             \
+          a.length[g] = static_cast<int16_t>(a.turn + 1);                                                                                         \
+          a.done[g] = static_cast<uint8_t>(0x80 | lost);                                                                                          \
+        } else if (misplay) {                                                                                                                     \
+          a.done[g] = static_cast<uint8_t>(lost);                                                                                                 \
+        }                                                                                                                                         \
+      }                                                                                                                                           \
+    }                                                                                                                                             \
+    unsigned long long m = __ballot(ended);                                                                                                       \
+    if (m) {                                                                                                                                      \
+      wave_add(lc, m, lane);   /* (slot 0 counts the games that ended: subtracted from the live count below) */                                   \
+      wave_add(lc + 1 + B, __ballot(bomb), lane);                                                                                                 \
+      while (m) {   /* histogram: one ballot per score that occurs in this wave (wave-uniform loop) */                                            \
+        const int b = __shfl(bin, __ffsll(static_cast<unsigned long long>(m)) - 1);                                                               \
+        const unsigned long long mb = __ballot(ended && bin == b);                                                                                \
+        wave_add(lc + 1 + b, mb, lane);                                                                                                           \
+        m &= ~mb;                                                                                                                                 \
+      }                                                                                                                                           \
+    }                                                                                                                                             \
+    _Pragma("unroll") for (int k = 0; k < 4; ++k) wave_add(lc + 2 + B + 4 * a.seat + k, __ballot(kind == k), lane);                                                 \
+    wave_add(lc + 2 + B + 4 * a.P + a.seat, __ballot(misplay), lane);                                                                             \
+  }                                                                                                                                               \
+  __syncthreads();                                                                                                                                \
+  for (int i = threadIdx.x; i < nc; i += 256) {                                                                                                   \
+    const unsigned int v = lc[i];                                                                                                                 \
+    if (v) atomicAdd(a.counters + i, i == 0 ? static_cast<unsigned long long>(-static_cast<long long>(v)) : static_cast<unsigned long long>(v));  \
+  }
+
 __global__ void __launch_bounds__(256) eval_tally_kernel(TallyArgs a) {
-  __shared__ unsigned int lc[kMaxCounters];
-  const int lane = threadIdx.x & 63;
-  const int B = a.bins, nc = 2 + B + 5 * a.P;
-  for (int i = threadIdx.x; i < nc; i += 256) lc[i] = 0;
-  __syncthreads();
-  for (long long base = static_cast<long long>(blockIdx.x) * 256; base < a.n; base += static_cast<long long>(gridDim.x) * 256) {
-    const long long g = base + threadIdx.x;
-    int kind = -1, bin = 0;
-    bool ended = false, misplay = false, bomb = false;
-    if (g < a.n) {
-      const uint8_t st = a.done[g];
-      if (!(st & 0x80u)) {   // a game counts only while it is live: finished games' env outputs are never read
-        const int u = a.actions[g];
-        if (u >= 0 && u < a.A) kind = u < a.H ? 0 : u < 2 * a.H ? 1 : u < 2 * a.H + (a.P - 1) * a.C ? 2 : 3;   // App. A.2 order
-        misplay = kind == 1 && a.reward[g] <= 0.f;   // a successful play always scores +1; a misplay 0, or -score at a bomb-out
-        const int lost = (st & 0x7f) + (misplay ? 1 : 0);
-        ended = a.terminal[g] != 0;
-        if (ended) {
-          const int sc = a.score[g];   // 0 after a bomb-out (hb_env_step)
-          bin = sc < 0 ? 0 : sc > B - 1 ? B - 1 : sc;
-          bomb = lost >= a.max_life;
-          a.final_score[g] = static_cast<int8_t>(sc);
-          a.length[g] = static_cast<int16_t>(a.turn + 1);
-          a.done[g] = static_cast<uint8_t>(0x80 | lost);
-        } else if (misplay) {
-          a.done[g] = static_cast<uint8_t>(lost);
-        }
-      }
-    }
-    unsigned long long m = __ballot(ended);
-    if (m) {
-      wave_add(lc, m, lane);   // (slot 0 counts the games that ended: subtracted from the live count below)
-      wave_add(lc + 1 + B, __ballot(bomb), lane);
-      while (m) {   // histogram: one ballot per score that occurs in this wave (wave-uniform loop)
-        const int b = __shfl(bin, __ffsll(static_cast<unsigned long long>(m)) - 1);
-        const unsigned long long mb = __ballot(ended && bin == b);
-        wave_add(lc + 1 + b, mb, lane);
-        m &= ~mb;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) wave_add(lc + 2 + B + 4 * a.seat + k, __ballot(kind == k), lane);
-    wave_add(lc + 2 + B + 4 * a.P + a.seat, __ballot(misplay), lane);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < nc; i += 256) {
-    const unsigned int v = lc[i];
-    if (v) atomicAdd(a.counters + i, i == 0 ? static_cast<unsigned long long>(-static_cast<long long>(v)) : static_cast<unsigned long long>(v));
-  }
+  HB_TALLY_BODY
+}
+
+// hb_eval_tally_grouped: blockIdx.y selects a block of a0.n games and its own row of counters
+__global__ void __launch_bounds__(256) eval_tally_grouped_kernel(TallyArgs a0) {
+  const long long off = static_cast<long long>(blockIdx.y) * a0.n;
+  TallyArgs a = a0;
+  a.actions += off; a.reward += off; a.terminal += off; a.score += off;
+  a.done += off; a.final_score += off; a.length += off;
+  a.counters += static_cast<long long>(blockIdx.y) * (2 + a0.bins + 5 * a0.P);
+  HB_TALLY_BODY
 }
 
 }  // namespace
@@ -99,9 +113,11 @@ extern "C" int hb_eval_counters(const hb_config* cfg) {
   return 2 + cfg->colors * cfg->ranks + 1 + 5 * cfg->players;
 }
 
-extern "C" int hb_eval_tally(const hb_config* cfg, int64_t n_games, int32_t seat, int32_t turn, const int32_t* actions_dev,
-                             const float* reward_dev, const int8_t* terminal_dev, const int8_t* score_dev, uint8_t* done_dev,
-                             int8_t* final_score_dev, int16_t* length_dev, int64_t* counters_dev, void* stream) {
+namespace {
+
+int check_tally(const hb_config* cfg, int64_t n_games, int32_t seat, int32_t turn, const int32_t* actions_dev, const float* reward_dev,
+                const int8_t* terminal_dev, const int8_t* score_dev, uint8_t* done_dev, int8_t* final_score_dev, int16_t* length_dev,
+                int64_t* counters_dev) {
   if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
   if (int rc = hb_config_validate(cfg)) return rc;
   if (n_games < 0) return hb::fail(HB_ERR_INVALID, "n_games must be >= 0");
@@ -109,12 +125,20 @@ extern "C" int hb_eval_tally(const hb_config* cfg, int64_t n_games, int32_t seat
   if (turn < 0 || turn >= 32767) return hb::fail(HB_ERR_INVALID, "turn %d out of range 0..32766 (lengths are int16)", turn);
   if (!actions_dev || !reward_dev || !terminal_dev || !score_dev || !done_dev || !final_score_dev || !length_dev || !counters_dev)
     return hb::fail(HB_ERR_INVALID, "null argument");
-  if (n_games == 0) return HB_OK;
+  return HB_OK;
+}
+
+int have_device() {
   static const int ndev = [] {
     int n = 0;
     return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
   }();
-  if (ndev <= 0) return hb::fail(HB_ERR_NO_DEVICE, "no HIP device available");
+  return ndev > 0 ? HB_OK : hb::fail(HB_ERR_NO_DEVICE, "no HIP device available");
+}
+
+TallyArgs tally_args(const hb_config* cfg, int64_t n_games, int32_t seat, int32_t turn, const int32_t* actions_dev, const float* reward_dev,
+                     const int8_t* terminal_dev, const int8_t* score_dev, uint8_t* done_dev, int8_t* final_score_dev, int16_t* length_dev,
+                     int64_t* counters_dev) {
   TallyArgs a{};
   a.n = n_games;
   a.P = cfg->players; a.C = cfg->colors; a.R = cfg->ranks; a.H = cfg->hand_size;
@@ -126,8 +150,41 @@ extern "C" int hb_eval_tally(const hb_config* cfg, int64_t n_games, int32_t seat
   a.actions = actions_dev; a.reward = reward_dev; a.terminal = terminal_dev; a.score = score_dev;
   a.done = done_dev; a.final_score = final_score_dev; a.length = length_dev;
   a.counters = reinterpret_cast<unsigned long long*>(counters_dev);
+  return a;
+}
+
+}  // namespace
+
+extern "C" int hb_eval_tally(const hb_config* cfg, int64_t n_games, int32_t seat, int32_t turn, const int32_t* actions_dev,
+                             const float* reward_dev, const int8_t* terminal_dev, const int8_t* score_dev, uint8_t* done_dev,
+                             int8_t* final_score_dev, int16_t* length_dev, int64_t* counters_dev, void* stream) {
+  if (int rc = check_tally(cfg, n_games, seat, turn, actions_dev, reward_dev, terminal_dev, score_dev, done_dev, final_score_dev,
+                           length_dev, counters_dev))
+    return rc;
+  if (n_games == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  const TallyArgs a = tally_args(cfg, n_games, seat, turn, actions_dev, reward_dev, terminal_dev, score_dev, done_dev, final_score_dev,
+                                 length_dev, counters_dev);
   const unsigned blocks = static_cast<unsigned>(std::min<int64_t>((n_games + 255) / 256, kMaxBlocks));
   hipLaunchKernelGGL(eval_tally_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+extern "C" int hb_eval_tally_grouped(const hb_config* cfg, int64_t n_blocks, int64_t block_games, int32_t seat, int32_t turn,
+                                     const int32_t* actions_dev, const float* reward_dev, const int8_t* terminal_dev,
+                                     const int8_t* score_dev, uint8_t* done_dev, int8_t* final_score_dev, int16_t* length_dev,
+                                     int64_t* counters_dev, void* stream) {
+  if (int rc = check_tally(cfg, block_games, seat, turn, actions_dev, reward_dev, terminal_dev, score_dev, done_dev, final_score_dev,
+                           length_dev, counters_dev))
+    return rc;
+  if (n_blocks < 0 || n_blocks > 65535) return hb::fail(HB_ERR_INVALID, "n_blocks must be 0..65535 (one grid row per block)");
+  if (n_blocks == 0 || block_games == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  const TallyArgs a = tally_args(cfg, block_games, seat, turn, actions_dev, reward_dev, terminal_dev, score_dev, done_dev, final_score_dev,
+                                 length_dev, counters_dev);
+  const dim3 grid(static_cast<unsigned>(std::min<int64_t>((block_games + 255) / 256, kMaxBlocks)), static_cast<unsigned>(n_blocks));
+  hipLaunchKernelGGL(eval_tally_grouped_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
   HB_HIP(hipGetLastError());
   return HB_OK;
 }

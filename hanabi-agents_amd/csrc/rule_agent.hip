@@ -266,87 +266,130 @@ __device__ int rule_legal_random(const Seat& v) {  // ruleset.py:598-604 over th
   return __ffsll(static_cast<long long>(m)) - 1;
 }
 
+// The walk over one game: state row and outputs g (the enclosing kernel's), Philox game id a.first_gid + LID, rules
+// RULES[0 .. N_RULES). A macro, so that rule_kernel expands to exactly the code it was written as (its code object is unchanged)
+// and the grouped kernel shares it.
+#define HB_RULE_GAME(LID, N_RULES, RULES)                                                                                                 \
+  Seat v;                                                                                                                                 \
+  v.row = a.rows + g * a.SW;                                                                                                              \
+  v.P = a.P; v.C = a.C; v.R = a.R; v.H = a.H; v.INFO = a.INFO;                                                                            \
+  const uint32_t w0 = v.row[0];                                                                                                           \
+  v.w1 = v.row[1];                                                                                                                        \
+  v.deck = w0 & 63;                                                                                                                       \
+  v.info = (w0 >> 6) & 15;                                                                                                                \
+  v.life = (w0 >> 10) & 7;                                                                                                                \
+  v.s = (w0 >> 13) & 7;                                                                                                                   \
+  v.n_own = v.hand_n(v.s);                                                                                                                \
+  v.kn = v.know(v.s);                                                                                                                     \
+  /* discard pile: one thermometer per card identity (state words 8-9) */                                                                 \
+  const uint64_t disc = (static_cast<uint64_t>(v.row[9]) << 32) | v.row[8];                                                               \
+  v.seen = 0;                                                                                                                             \
+  v.maxfw = 0;                                                                                                                            \
+  v.minfw = 7;                                                                                                                            \
+  for (int c = 0; c < a.C; ++c) {                                                                                                         \
+    int reach = a.R;                                                                                                                      \
+    for (int r = 0; r < a.R; ++r) {                                                                                                       \
+      const int pos = c * a.CPC + (r ? 2 * r + 1 : 0), w = v.copies(r);                                                                   \
+      const int gone = __popc(static_cast<uint32_t>(disc >> pos) & ((1u << w) - 1u));                                                     \
+      if (gone >= w && r < reach) reach = r;                                                                                              \
+      const int vis = gone + (v.fw(c) > r ? 1 : 0);                                                                                       \
+      v.seen |= static_cast<uint64_t>(vis) << (2 * (c * a.R + r));                                                                        \
+    }                                                                                                                                     \
+    v.maxfw |= static_cast<uint32_t>(reach) << (3 * c);                                                                                   \
+    v.minfw = min(v.minfw, v.fw(c));                                                                                                      \
+  }                                                                                                                                       \
+  for (int off = 1; off < a.P; ++off) {                                                                                                   \
+    const int p = v.seat(off);                                                                                                            \
+    const uint32_t hc = v.cards(p);                                                                                                       \
+    for (int i = 0; i < v.hand_n(p); ++i) v.seen += 1ull << (2 * ((hc >> (5 * i)) & 31u));                                                \
+  }                                                                                                                                       \
+  const unsigned long long gid = static_cast<unsigned long long>(a.first_gid + (LID));                                                    \
+  hb::philox4x32_10(static_cast<uint32_t>(a.draw), static_cast<uint32_t>(a.draw >> 32), static_cast<uint32_t>(gid),                       \
+                    static_cast<uint32_t>(gid >> 32), static_cast<uint32_t>(a.seed), static_cast<uint32_t>(a.seed >> 32), v.rnd);         \
+                                                                                                                                          \
+  int act = -1, fired = (N_RULES);                                                                                                        \
+  for (int q = 0; q < (N_RULES) && act < 0; ++q) {                                                                                        \
+    const hb_rule rl = (RULES)[q];                                                                                                        \
+    int m = -1;                                                                                                                           \
+    switch (rl.kind) {                                                                                                                    \
+      case HB_RULE_LEGAL_RANDOM: m = rule_legal_random(v); break;                                                                         \
+      case HB_RULE_DISCARD_OLDEST_FIRST: m = (v.info < v.INFO && v.n_own > 0) ? v.uid_discard(0) : -1; break;                             \
+      case HB_RULE_OSAWA_DISCARD: m = rule_osawa_discard(v); break;                                                                       \
+      case HB_RULE_TELL_UNKNOWN: m = rule_tell_unknown(v); break;                                                                         \
+      case HB_RULE_TELL_RANDOMLY: m = rule_tell_randomly(v); break;                                                                       \
+      case HB_RULE_PLAY_SAFE_CARD: m = rule_play_safe_card(v); break;                                                                     \
+      case HB_RULE_PLAY_IF_CERTAIN: m = rule_play_if_certain(v); break;                                                                   \
+      case HB_RULE_TELL_PLAYABLE_CARD_OUTER: m = rule_tell_playable_card_outer(v); break;                                                 \
+      case HB_RULE_TELL_DISPENSABLE: m = rule_tell_dispensable(v, rl.arg); break;                                                         \
+      case HB_RULE_DISCARD_RANDOMLY:                                                                                                      \
+        m = (v.info < v.INFO && v.n_own > 0) ? v.uid_discard(static_cast<int>(__umulhi(v.rnd[2], static_cast<uint32_t>(v.n_own)))) : -1;  \
+        break;                                                                                                                            \
+      case HB_RULE_PLAY_PROBABLY_SAFE: m = rule_play_probably_safe(v, static_cast<double>(rl.threshold), rl.arg != 0); break;             \
+      case HB_RULE_DISCARD_PROBABLY_USELESS:                                                                                              \
+        if (v.info < v.INFO && v.n_own > 0) {                                                                                             \
+          double p;                                                                                                                       \
+          const int idx = argmax_probability<true>(v, &p);                                                                                \
+          if (p >= static_cast<double>(rl.threshold)) m = v.uid_discard(idx);                                                             \
+        }                                                                                                                                 \
+        break;                                                                                                                            \
+      case HB_RULE_HAIL_MARY: m = (v.deck == 0 && v.life > 1) ? rule_play_probably_safe(v, 0.0, false) : -1; break;                       \
+      case HB_RULE_TELL_ANYONE_USELESS_CARD: m = rule_tell_anyone_useless_card(v); break;                                                 \
+      case HB_RULE_TELL_PLAYABLE_CARD: m = rule_tell_playable_card(v); break;                                                             \
+      default: break;  /* HB_RULE_TELL_MOST_INFORMATION: the reference function ends without a return (ruleset.py:539-562) */             \
+    }                                                                                                                                     \
+    if (m >= 0) {                                                                                                                         \
+      act = m;                                                                                                                            \
+      fired = q;                                                                                                                          \
+    }                                                                                                                                     \
+  }                                                                                                                                       \
+  if (act < 0) act = rule_legal_random(v);  /* rule_based.py:24 */                                                                        \
+  a.actions[g] = act;                                                                                                                     \
+  if (a.fired) a.fired[g] = fired;
+
 __global__ void __launch_bounds__(128) rule_kernel(RuleArgs a) {
   const long long g = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (g >= a.n) return;
-  Seat v;
-  v.row = a.rows + g * a.SW;
-  v.P = a.P; v.C = a.C; v.R = a.R; v.H = a.H; v.INFO = a.INFO;
-  const uint32_t w0 = v.row[0];
-  v.w1 = v.row[1];
-  v.deck = w0 & 63;
-  v.info = (w0 >> 6) & 15;
-  v.life = (w0 >> 10) & 7;
-  v.s = (w0 >> 13) & 7;
-  v.n_own = v.hand_n(v.s);
-  v.kn = v.know(v.s);
-  // discard pile: one thermometer per card identity (state words 8-9)
-  const uint64_t disc = (static_cast<uint64_t>(v.row[9]) << 32) | v.row[8];
-  v.seen = 0;
-  v.maxfw = 0;
-  v.minfw = 7;
-  for (int c = 0; c < a.C; ++c) {
-    int reach = a.R;
-    for (int r = 0; r < a.R; ++r) {
-      const int pos = c * a.CPC + (r ? 2 * r + 1 : 0), w = v.copies(r);
-      const int gone = __popc(static_cast<uint32_t>(disc >> pos) & ((1u << w) - 1u));
-      if (gone >= w && r < reach) reach = r;
-      const int vis = gone + (v.fw(c) > r ? 1 : 0);
-      v.seen |= static_cast<uint64_t>(vis) << (2 * (c * a.R + r));
-    }
-    v.maxfw |= static_cast<uint32_t>(reach) << (3 * c);
-    v.minfw = min(v.minfw, v.fw(c));
-  }
-  for (int off = 1; off < a.P; ++off) {
-    const int p = v.seat(off);
-    const uint32_t hc = v.cards(p);
-    for (int i = 0; i < v.hand_n(p); ++i) v.seen += 1ull << (2 * ((hc >> (5 * i)) & 31u));
-  }
-  const unsigned long long gid = static_cast<unsigned long long>(a.first_gid + g);
-  hb::philox4x32_10(static_cast<uint32_t>(a.draw), static_cast<uint32_t>(a.draw >> 32), static_cast<uint32_t>(gid),
-                    static_cast<uint32_t>(gid >> 32), static_cast<uint32_t>(a.seed), static_cast<uint32_t>(a.seed >> 32), v.rnd);
-
-  int act = -1, fired = a.n_rules;
-  for (int q = 0; q < a.n_rules && act < 0; ++q) {
-    const hb_rule rl = a.rules[q];
-    int m = -1;
-    switch (rl.kind) {
-      case HB_RULE_LEGAL_RANDOM: m = rule_legal_random(v); break;
-      case HB_RULE_DISCARD_OLDEST_FIRST: m = (v.info < v.INFO && v.n_own > 0) ? v.uid_discard(0) : -1; break;
-      case HB_RULE_OSAWA_DISCARD: m = rule_osawa_discard(v); break;
-      case HB_RULE_TELL_UNKNOWN: m = rule_tell_unknown(v); break;
-      case HB_RULE_TELL_RANDOMLY: m = rule_tell_randomly(v); break;
-      case HB_RULE_PLAY_SAFE_CARD: m = rule_play_safe_card(v); break;
-      case HB_RULE_PLAY_IF_CERTAIN: m = rule_play_if_certain(v); break;
-      case HB_RULE_TELL_PLAYABLE_CARD_OUTER: m = rule_tell_playable_card_outer(v); break;
-      case HB_RULE_TELL_DISPENSABLE: m = rule_tell_dispensable(v, rl.arg); break;
-      case HB_RULE_DISCARD_RANDOMLY:
-        m = (v.info < v.INFO && v.n_own > 0) ? v.uid_discard(static_cast<int>(__umulhi(v.rnd[2], static_cast<uint32_t>(v.n_own)))) : -1;
-        break;
-      case HB_RULE_PLAY_PROBABLY_SAFE: m = rule_play_probably_safe(v, static_cast<double>(rl.threshold), rl.arg != 0); break;
-      case HB_RULE_DISCARD_PROBABLY_USELESS:
-        if (v.info < v.INFO && v.n_own > 0) {
-          double p;
-          const int idx = argmax_probability<true>(v, &p);
-          if (p >= static_cast<double>(rl.threshold)) m = v.uid_discard(idx);
-        }
-        break;
-      case HB_RULE_HAIL_MARY: m = (v.deck == 0 && v.life > 1) ? rule_play_probably_safe(v, 0.0, false) : -1; break;
-      case HB_RULE_TELL_ANYONE_USELESS_CARD: m = rule_tell_anyone_useless_card(v); break;
-      case HB_RULE_TELL_PLAYABLE_CARD: m = rule_tell_playable_card(v); break;
-      default: break;  // HB_RULE_TELL_MOST_INFORMATION: the reference function ends without a return (ruleset.py:539-562)
-    }
-    if (m >= 0) {
-      act = m;
-      fired = q;
-    }
-  }
-  if (act < 0) act = rule_legal_random(v);  // rule_based.py:24
-  a.actions[g] = act;
-  if (a.fired) a.fired[g] = fired;
+  HB_RULE_GAME(g, a.n_rules, a.rules)
 }
 
+// hb_rule_act_grouped: blockIdx.y = block b of a.n games, blockIdx.x * 128 + lane = its row. The block's rule set (and with it the
+// rule walked at each step) is uniform over the workgroup.
+struct RuleGroups {
+  const int32_t* set_of_block;   // [n_blocks]
+  const hb_rule* rules;          // [n_sets][HB_MAX_RULES]
+  const int32_t* n_rules;        // [n_sets]
+  int n_sets;
+};
+__global__ void __launch_bounds__(128) rule_grouped_kernel(RuleArgs a, RuleGroups grp) {
+  const int b = static_cast<int>(blockIdx.y);
+  const int set = grp.set_of_block[b];
+  if (set < 0 || set >= grp.n_sets) return;   // (-1: a block of other agents)
+  const long long r = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (r >= a.n) return;
+  const hb_rule* rules = grp.rules + static_cast<long long>(set) * HB_MAX_RULES;
+  const int n_rules = min(max(grp.n_rules[set], 0), HB_MAX_RULES);
+  const long long g = static_cast<long long>(b) * a.n + r;
+  HB_RULE_GAME(r, n_rules, rules)
+}
+
+
 }  // namespace
+
+static RuleArgs rule_args(const hb_config* cfg, const uint32_t* state_rows_dev, int64_t n_games, int64_t first_game_id, uint64_t seed,
+                          uint64_t draw, int32_t* actions_dev, int32_t* fired_dev) {
+  RuleArgs a{};
+  a.rows = state_rows_dev;
+  a.n = n_games;
+  a.first_gid = first_game_id;
+  a.P = cfg->players; a.C = cfg->colors; a.R = cfg->ranks; a.H = cfg->hand_size; a.INFO = cfg->max_info;
+  a.SW = hb_state_words(cfg);
+  a.CPC = hb_deck_size(cfg) / cfg->colors;
+  a.seed = seed;
+  a.draw = draw;
+  a.actions = actions_dev;
+  a.fired = fired_dev;
+  return a;
+}
 
 extern "C" int hb_rule_act(const hb_config* cfg, const uint32_t* state_rows_dev, int64_t n_games, int64_t first_game_id,
                            const hb_rule* rules, int32_t n_rules, uint64_t seed, uint64_t draw, int32_t* actions_dev,
@@ -358,21 +401,29 @@ extern "C" int hb_rule_act(const hb_config* cfg, const uint32_t* state_rows_dev,
   for (int i = 0; i < n_rules; ++i)
     if (rules[i].kind < 0 || rules[i].kind >= HB_RULE_KINDS) return hb::fail(HB_ERR_INVALID, "rule %d: unknown kind %d", i, rules[i].kind);
   if (n_games <= 0) return HB_OK;
-  RuleArgs a{};
-  a.rows = state_rows_dev;
-  a.n = n_games;
-  a.first_gid = first_game_id;
-  a.P = cfg->players; a.C = cfg->colors; a.R = cfg->ranks; a.H = cfg->hand_size; a.INFO = cfg->max_info;
-  a.SW = hb_state_words(cfg);
-  a.CPC = hb_deck_size(cfg) / cfg->colors;
+  RuleArgs a = rule_args(cfg, state_rows_dev, n_games, first_game_id, seed, draw, actions_dev, fired_dev);
   a.n_rules = n_rules;
   for (int i = 0; i < n_rules; ++i) a.rules[i] = rules[i];
-  a.seed = seed;
-  a.draw = draw;
-  a.actions = actions_dev;
-  a.fired = fired_dev;
   const unsigned blocks = static_cast<unsigned>((n_games + 127) / 128);
   hipLaunchKernelGGL(rule_kernel, dim3(blocks), dim3(128), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+extern "C" int hb_rule_act_grouped(const hb_config* cfg, const uint32_t* state_rows_dev, int64_t n_blocks, int64_t block_rows,
+                                   int64_t first_game_id, const int32_t* set_of_block_dev, const hb_rule* rules_dev,
+                                   const int32_t* n_rules_dev, int32_t n_sets, uint64_t seed, uint64_t draw, int32_t* actions_dev,
+                                   int32_t* fired_dev, void* stream) {
+  if (!cfg || !state_rows_dev || !actions_dev || !set_of_block_dev || !rules_dev || !n_rules_dev) return hb::fail(HB_ERR_INVALID, "null argument");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  if (n_sets < 1) return hb::fail(HB_ERR_INVALID, "n_sets must be >= 1");
+  if (n_blocks < 0 || n_blocks > 65535) return hb::fail(HB_ERR_INVALID, "n_blocks must be 0..65535 (one grid row per block)");
+  if (block_rows < 0 || block_rows > (int64_t{1} << 31) * 128 - 1) return hb::fail(HB_ERR_INVALID, "block_rows out of range");
+  if (n_blocks == 0 || block_rows == 0) return HB_OK;
+  const RuleArgs a = rule_args(cfg, state_rows_dev, block_rows, first_game_id, seed, draw, actions_dev, fired_dev);
+  const RuleGroups grp{set_of_block_dev, rules_dev, n_rules_dev, n_sets};
+  const dim3 grid(static_cast<unsigned>((block_rows + 127) / 128), static_cast<unsigned>(n_blocks));
+  hipLaunchKernelGGL(rule_grouped_kernel, grid, dim3(128), 0, static_cast<hipStream_t>(stream), a, grp);
   HB_HIP(hipGetLastError());
   return HB_OK;
 }

@@ -559,7 +559,31 @@ class DQNAgent:
         actions_out.copy_(actions.to(torch.int32))
         return actions_out
 
-    # ---- acting (rlax_rainbow.py:277-290) ---------------------------------------------------------------
+    @torch.no_grad()
+    def eval_operands(self):
+        """What eval_moves' one-kernel branch launches with on bit-packed rows, for a tile descriptor of
+        hb_actor_fused_act_grouped (hanabi_hip.crossplay): a dict of the acting set's fragment-major copies (w1f, b1f, w2f, b2f:
+        device addresses), the support (`support` address, `support_t` the tensor), the operand dtype (1 bf16, 2 f16), obs_len,
+        hidden, n_actions, n_atoms and first_game_id; None when eval_moves would not run this agent on the one-kernel actor.
+
+        It does what eval_moves does before that launch — waits (on the calling stream) for an update in flight, builds the
+        FusedLearner of an agent that has not acted yet, picks the acting set — and nothing else: no draw counter moves and no
+        noise is resampled. The addresses stay valid until the agent's next update."""
+        if not self._fused:
+            return None
+        self._wait_for_weights()
+        self._effective_weights()
+        fl = self._fused_learner() if self.actor_lag else self._fl
+        act = fl.actor if (fl is not None and self.use_mfma_actor) else None
+        if act is None or not act.fused or act.n_actions > 64:
+            return None
+        f = act._fset_ptrs[fl.acting_set()]
+        support = self.atoms[0]
+        return dict(w1f=f[0], b1f=f[1], w2f=f[2], b2f=f[3], support=support.data_ptr(), support_t=support, dtype=act._dt,
+                    obs_len=act.obs_len, hidden=act.hidden, n_actions=act.n_actions, n_atoms=act.n_atoms,
+                    first_game_id=int(self.first_game_id))
+
+    # ---- acting (rlax_rainbow.py:277-290)---------------------------------------------------------------
     @torch.no_grad()
     def exploit(self, observations):
         obs, legal, on_device = self._unpack(observations)

@@ -69,6 +69,13 @@ class HbCmd(C.Structure):
  CMD_PER_SAMPLE_GATHER, CMD_GRAPH_LAUNCH, CMD_PER_UPDATE, CMD_ACTOR_FUSED_PACK, CMD_ACTOR_PACK_WEIGHTS) = range(1, 12)
 
 
+class HbFusedTile(C.Structure):
+    """`hb_fused_tile` of include/hanabi_hip.h (hb_actor_fused_act_grouped: one per 128-row tile)."""
+
+    _fields_ = [(n, C.c_void_p) for n in ("w1f", "b1f", "w2f", "b2f", "support")] + [("first_game_id", C.c_int64),
+                                                                                      ("active", C.c_int32), ("pad", C.c_int32)]
+
+
 class HbRule(C.Structure):
     """`hb_rule` of include/hanabi_hip.h."""
 
@@ -117,6 +124,7 @@ SIGNATURES = {
     "hb_env_import_state": (C.c_int, [_P, _P, _P]),
     "hb_env_state": (_P, [_P]),
     "hb_rule_act": (C.c_int, [_CFG, _P, _I64, _I64, C.POINTER(HbRule), _I32, _U64, _U64, _P, _P, _P]),
+    "hb_rule_act_grouped": (C.c_int, [_CFG, _P, _I64, _I64, _I64, _P, _P, _P, _I32, _U64, _U64, _P, _P, _P]),
     "hb_random_legal_actions": (C.c_int, [_P, _I64, _I32, _U64, _U64, _I64, _P, _P]),
     "hb_env_set_games_per_wave": (C.c_int, [_P, _I32]),
     "hb_env_set_async_refill": (C.c_int, [_P, _I32]),
@@ -178,9 +186,11 @@ SIGNATURES = {
     "hb_actor_fused_act_step": (C.c_int, [_P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, C.c_float, _U64, _U64, _I64, _P,
                                           _I32] + [_P] * 7 + [_P]),
     "hb_actor_fused_step_supported": (C.c_int, [_P]),
+    "hb_actor_fused_act_grouped": (C.c_int, [_P, _I64, _P, _P, _I32, _I32, _I32, _I32, _P, C.c_float, _U64, _U64, _P, _I32, _P]),
     "hb_chain_run": (C.c_int, [C.POINTER(HbCmd), _I32, C.POINTER(_I64), C.POINTER(_F64)]),
     "hb_eval_counters": (C.c_int, [_CFG]),
     "hb_eval_tally": (C.c_int, [_CFG, _I64, _I32, _I32] + [_P] * 8 + [_P]),
+    "hb_eval_tally_grouped": (C.c_int, [_CFG, _I64, _I64, _I32, _I32] + [_P] * 8 + [_P]),
     "hb_relu_bwd_colsum": (C.c_int, [_P, _P, _I64, _I32, _I64, _I64, _P, _P]),
     "hb_replay_insert": (C.c_int, [_P] * 12 + [_I64, _I32, _I32, _I64, _I64, _P]),
 }

@@ -1,0 +1,347 @@
+"""Cross-play on the GPU: every team of a pool of agents on the same fixed deals, all teams in one lock-step evaluation.
+
+Ad-hoc teamplay scores an agent against partners other than itself (the reference ships its rule-based partners for that,
+rule_based/predefined_rules.py). `CrossPlay` plays a pool of K agents — DQN checkpoints or seeds and rule-based agents — as K^2
+teams on the same deals and returns one `EvalResult` per team, each equal to what `Evaluator(...).run(team)` returns:
+
+    cp = CrossPlay("Hanabi-Full", players=2, n_games=4096, seed=7)
+    res = cp.run(pool)                      # default teams: (i, j, j, ..., j) for every ordered pair of pool indices
+    res.mean_matrix()                       # K x K: candidate i (seat 0) with partner j (every other seat)
+
+* Layout. Team k owns a block of n_pad = ceil(n / 128) * 128 games. Every block starts from the same deals: the state rows of
+  one n_pad-game env built with the evaluator's seed and first_game_id (deal g is keyed by the game id alone, so rows 0..n-1
+  are the standalone Evaluator's deals). Padding rows are real games, acted on and stepped, but their `done` byte starts at
+  "finished", so they are never counted. Teams go into chunks of at most `max_rows` games; a chunk's env and buffers are built
+  once and kept.
+* One turn (seat t mod P) issues, on the current stream: one hb_actor_fused_act_grouped per operand dtype for the blocks whose
+  seat agent takes the one-kernel actor (each 128-row tile reads its own network's descriptor), one hb_rule_act_grouped for the
+  rule-agent blocks, one HanabiEnv.step over the whole chunk and one hb_eval_tally_grouped (a row of counters per block). The
+  descriptor and rule-set tables are uploaded once per chunk and run, not per turn. Agents off the one-kernel actor take their
+  own eval_moves on row slices of their block (the generic path): rows [r0, r0 + n) in one call — exactly the standalone
+  shape, which the library GEMMs' kernel choice and the torch path's generator depend on — then the padding rows.
+* Seeds, draws and game ids are those of Evaluator.run: Philox seed = the evaluator's seed, draw = turn + 1; a DQN agent keys
+  its row r by its own first_game_id + r, a rule agent by the evaluator's first_game_id + r. No agent's draw counter,
+  histogram, noise or buffers move.
+"""
+import ctypes as C
+import math
+import weakref
+
+import torch
+
+from . import _capi as K
+from .env import HanabiEnv
+from .evaluate import EvalResult, max_turns
+
+TILE = 128   # rows per workgroup of the one-kernel actor, and per hb_fused_tile
+
+
+def default_teams(k, players):
+    """The K^2 default teams of a pool of k agents: (i, j, j, ..., j) for i, j in range(k) — candidate i in seat 0, partner j
+    in every other seat (2 players: every ordered pair)."""
+    k, players = int(k), int(players)
+    if k < 1 or players < 2:
+        raise ValueError(f"need a pool of >= 1 agents and >= 2 players, got {k} agents, {players} players")
+    return [(i,) + (j,) * (players - 1) for i in range(k) for j in range(k)]
+
+
+def check_teams(teams, k, players):
+    """Explicit teams as a list of P-tuples of pool indices; raises ValueError on a bad one."""
+    out = []
+    for team in teams:
+        t = tuple(int(x) for x in team)
+        if len(t) != players:
+            raise ValueError(f"team {team!r}: one pool index per seat ({players} players)")
+        if any(x < 0 or x >= k for x in t):
+            raise ValueError(f"team {team!r}: pool indices must be in 0..{k - 1}")
+        out.append(t)
+    if not out:
+        raise ValueError("no teams")
+    return out
+
+
+def padded_games(n):
+    """Games per team block: n rounded up to whole 128-row tiles."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"n_games must be >= 1, got {n}")
+    return -(-n // TILE) * TILE
+
+
+def plan_chunks(n_teams, n_pad, max_rows):
+    """[(first team, team count)] covering n_teams teams of n_pad rows each, at most max_rows rows per chunk (at least one team
+    per chunk: a team larger than max_rows gets a chunk of its own). Team k sits at row (k - first) * n_pad of its chunk."""
+    if n_teams < 1 or n_pad < 1:
+        raise ValueError("n_teams and n_pad must be >= 1")
+    per = max(1, int(max_rows) // int(n_pad))
+    return [(s, min(per, n_teams - s)) for s in range(0, n_teams, per)]
+
+
+class CrossPlayResult:
+    """teams: the P-tuples of pool indices, results: one EvalResult per team (the class Evaluator returns), k: pool size."""
+
+    def __init__(self, teams, results, k, players, default):
+        self.teams, self.results, self.k, self.players, self.default = list(teams), list(results), int(k), int(players), bool(default)
+
+    def _matrix(self, value):
+        if not self.default:
+            raise ValueError("a K x K matrix needs the default teams (run without `teams`)")
+        m = torch.empty(self.k, self.k, dtype=torch.float64)
+        for (i, j), r in zip(((t[0], t[-1]) for t in self.teams), self.results):
+            m[i, j] = value(r)
+        return m
+
+    def mean_matrix(self):
+        """[i, j] = mean score of candidate i in seat 0 with partner j in every other seat."""
+        return self._matrix(lambda r: r.mean)
+
+    def stderr_matrix(self):
+        return self._matrix(lambda r: r.stderr)
+
+    def as_dict(self):
+        d = dict(players=self.players, pool_size=self.k, teams=[list(t) for t in self.teams], results=[r.as_dict() for r in self.results])
+        if self.default:
+            d["mean_matrix"] = self.mean_matrix().tolist()
+            d["stderr_matrix"] = self.stderr_matrix().tolist()
+        return d
+
+    def __repr__(self):
+        return f"CrossPlayResult({len(self.teams)} teams, pool of {self.k}, {self.players} players)"
+
+
+class _Chunk:
+    """The env and buffers of `nb` team blocks of n_pad games (built once, reused by every run with that many blocks)."""
+
+    def __init__(self, cp, nb):
+        n, n_pad, dev = cp.n, cp.n_pad, cp.device
+        rows = nb * n_pad
+        self.nb, self.rows = nb, rows
+        self.env = HanabiEnv(config=cp.cfg, n_games=rows, seed=cp.seed, first_game_id=cp.first_game_id, device=dev, packed=True)
+        dev = self.env.device
+        self.rows0 = cp._deals.repeat(nb, 1)
+        pad = torch.zeros(n_pad, dtype=torch.uint8, device=dev)
+        pad[n:] = 0x80   # padding rows start finished: stepped, never counted
+        self.done0 = pad.repeat(nb)
+        self.done = torch.empty_like(self.done0)
+        self.final_score = torch.zeros(rows, dtype=torch.int8, device=dev)
+        self.length = torch.zeros(rows, dtype=torch.int16, device=dev)
+        self.counters0 = torch.zeros(nb, cp.n_counters, dtype=torch.int64, device=dev)
+        self.counters0[:, 0] = n
+        self.counters = torch.empty_like(self.counters0)
+        self.actions = torch.zeros(cp.max_turns if cp.record_actions else 1, rows, dtype=torch.int32, device=dev)
+        self.q = torch.empty(rows, self.env.num_actions, dtype=torch.float32, device=dev)
+
+
+class CrossPlay:
+    """Plays every team of a pool on the same `n_games` deals; see the module docstring.
+
+    game / players / config / seed / first_game_id / record_actions / check_every: as Evaluator. max_rows: games per chunk
+    (teams of one chunk run in lock-step; more teams than fit take several chunks one after another)."""
+
+    def __init__(self, game="Hanabi-Full", players=2, n_games=4096, seed=1, first_game_id=0, max_rows=262144, record_actions=False,
+                 device=None, config=None, check_every=8):
+        n_games = int(n_games)
+        if n_games < 1:
+            raise ValueError(f"n_games must be >= 1, got {n_games}")
+        if int(max_rows) < 1:
+            raise ValueError(f"max_rows must be >= 1, got {max_rows}")
+        if config is not None:
+            cfg = K.HbConfig(config.players, config.colors, config.ranks, config.hand_size, config.max_info, config.max_life, 0)
+        else:
+            cfg = K.make_config(game, players, 0)
+        if K.lib().hb_config_validate(C.byref(cfg)) != 0:
+            raise ValueError(f"invalid configuration {cfg!r}: {K.lib().hb_last_error().decode()}")
+        self.cfg = cfg
+        self.players = cfg.players
+        self.n = n_games
+        self.n_pad = padded_games(n_games)
+        self.seed = int(seed)
+        self.first_game_id = int(first_game_id)
+        self.max_rows = int(max_rows)
+        self.record_actions = bool(record_actions)
+        self.device = device
+        self.check_every = max(1, int(check_every))
+        self.max_turns = max_turns(cfg)
+        self.max_score = cfg.colors * cfg.ranks
+        self.n_counters = K.lib().hb_eval_counters(C.byref(cfg))
+        self._deals = None    # [n_pad, state words]: built by the first run (construction needs no GPU)
+        self._chunks = {}     # block count -> _Chunk
+        # agent -> eval_moves scratch of the generic path: the block's n rows, and its padding rows
+        self._scratch = weakref.WeakKeyDictionary()
+        self._scratch_pad = weakref.WeakKeyDictionary()
+        self.last_turns = []  # turns played by each chunk of the last run
+
+    def chunks(self, n_teams):
+        return plan_chunks(n_teams, self.n_pad, self.max_rows)
+
+    def _chunk(self, nb):
+        if self._deals is None:
+            env = HanabiEnv(config=self.cfg, n_games=self.n_pad, seed=self.seed, first_game_id=self.first_game_id, device=self.device,
+                            packed=True)
+            self._deals = env.export_state()
+            self.device = env.device
+        ch = self._chunks.get(nb)
+        if ch is None:
+            ch = self._chunks[nb] = _Chunk(self, nb)
+        return ch
+
+    @torch.no_grad()
+    def run(self, pool, teams=None, grouped=True):
+        """pool: list of agents (DQNAgent / RulebasedAgent); teams: P-tuples of pool indices (default: default_teams).
+        grouped=False: every agent takes its own eval_moves per block (the generic path). Returns a CrossPlayResult."""
+        from hanabi_agents.rule_based import RulebasedAgent
+
+        pool = list(pool)
+        k = len(pool)
+        default = teams is None
+        teams = default_teams(k, self.players) if default else check_teams(teams, k, self.players)
+        for a in pool:
+            if not hasattr(a, "eval_moves"):
+                raise TypeError(f"{type(a).__name__} has no eval_moves()")
+        # the agents' per-run operands: a tile descriptor for one-kernel DQN agents, a rule set for rule agents
+        kinds = {}
+        rule_sets = []
+        for a in pool:
+            if id(a) in kinds:
+                continue
+            if isinstance(a, RulebasedAgent):
+                kinds[id(a)] = ("rule", len(rule_sets)) if grouped else ("rule_generic", None)
+                if grouped:
+                    rule_sets.append(a)
+            elif grouped and a.requires_vectorized_observation() and hasattr(a, "eval_operands"):
+                ops = a.eval_operands()
+                kinds[id(a)] = ("tile", ops) if ops is not None else ("generic", None)
+            elif a.requires_vectorized_observation():
+                kinds[id(a)] = ("generic", None)
+            else:
+                raise TypeError(f"{type(a).__name__}: cross-play runs DQN-style agents (vectorised observations) and RulebasedAgent")
+        results = [None] * len(teams)
+        self.last_turns = []
+        rules_dev = n_rules_dev = None
+        for first, nb in self.chunks(len(teams)):
+            ch = self._chunk(nb)
+            if rule_sets and rules_dev is None:
+                tab = (K.HbRule * (K.MAX_RULES * len(rule_sets)))()
+                for s, a in enumerate(rule_sets):
+                    for q in range(len(a.rules)):
+                        tab[s * K.MAX_RULES + q] = a._tab[q]
+                dev = ch.env.device
+                rules_dev = torch.frombuffer(bytearray(tab), dtype=torch.uint8).to(dev)
+                n_rules_dev = torch.tensor([len(a.rules) for a in rule_sets], dtype=torch.int32, device=dev)
+            chunk_teams = teams[first:first + nb]
+            plans = [self._seat_plan(ch, [pool[t[s]] for t in chunk_teams], kinds) for s in range(self.players)]
+            out = self._play(ch, plans, rules_dev, n_rules_dev, len(rule_sets))
+            for b, res in enumerate(out):
+                results[first + b] = res
+        return CrossPlayResult(teams, results, k, self.players, default)
+
+    def _seat_plan(self, ch, agents, kinds):
+        """One seat of one chunk: the tile tables per operand dtype (device), the rule set of every block (device, or None when
+        no block of this seat is a rule agent) and the (block, agent, kind) list of the generic path."""
+        n_tiles, per_block = ch.rows // TILE, self.n_pad // TILE
+        env = ch.env
+        tiles = {}
+        sets = [-1] * ch.nb
+        generic = []
+        for b, a in enumerate(agents):
+            kind, arg = kinds[id(a)]
+            if kind == "tile":
+                if arg["obs_len"] != env.obs_len or arg["n_actions"] != env.num_actions:
+                    raise ValueError(f"agent of obs_len {arg['obs_len']} / {arg['n_actions']} actions in a game of "
+                                     f"{env.obs_len} / {env.num_actions}")
+                tab = tiles.get(arg["dtype"])
+                if tab is None:
+                    tab = tiles[arg["dtype"]] = (K.HbFusedTile * n_tiles)()
+                for i in range(per_block):
+                    d = tab[b * per_block + i]
+                    d.w1f, d.b1f, d.w2f, d.b2f, d.support = arg["w1f"], arg["b1f"], arg["w2f"], arg["b2f"], arg["support"]
+                    d.first_game_id = arg["first_game_id"] + TILE * i
+                    d.active = 1
+            elif kind == "rule":
+                sets[b] = arg
+            else:
+                generic.append((b, a, kind))
+        dev = env.device
+        tile_dev = [(dt, torch.frombuffer(bytearray(tab), dtype=torch.uint8).to(dev)) for dt, tab in sorted(tiles.items())]
+        hidden = {kinds[id(a)][1]["hidden"] for a in agents if kinds[id(a)][0] == "tile"}
+        atoms = {kinds[id(a)][1]["n_atoms"] for a in agents if kinds[id(a)][0] == "tile"}
+        set_dev = torch.tensor(sets, dtype=torch.int32, device=dev) if any(s >= 0 for s in sets) else None
+        keep = [kinds[id(a)][1]["support_t"] for a in agents if kinds[id(a)][0] == "tile"]   # (alive until the run ends)
+        return dict(tiles=tile_dev, hidden=hidden.pop() if hidden else 0, n_atoms=atoms.pop() if atoms else 0, sets=set_dev,
+                    generic=generic, keep=keep)
+
+    def _play(self, ch, plans, rules_dev, n_rules_dev, n_sets):
+        env, L, cfg = ch.env, K.lib(), self.cfg
+        env.import_state(ch.rows0)
+        env.observe()
+        illegal0 = env.illegal_count()
+        ch.done.copy_(ch.done0)
+        ch.final_score.zero_()
+        ch.length.zero_()
+        ch.counters.copy_(ch.counters0)
+        P, n, n_pad, nb, rows = self.players, self.n, self.n_pad, ch.nb, ch.rows
+        cfg_ref = C.byref(cfg)
+        state = L.hb_env_state(env.h)
+        obs, legal, q = env.obs_bits, env.legal, ch.q
+        tally_bufs = tuple(K.dptr(x) for x in (env.reward, env.terminal, env.score, ch.done, ch.final_score, ch.length, ch.counters))
+        rules_p = K.dptr(rules_dev)
+        n_rules_p = K.dptr(n_rules_dev)
+        live, t = nb * n, 0
+        while t < self.max_turns:
+            seat = t % P
+            plan = plans[seat]
+            act = ch.actions[t if self.record_actions else 0]
+            stream = K.current_stream()
+            for dt, tab in plan["tiles"]:
+                K.check(L.hb_actor_fused_act_grouped(K.dptr(tab), rows, K.dptr(obs), K.dptr(legal), env.obs_len, plan["hidden"],
+                                                     env.num_actions, plan["n_atoms"], K.dptr(q), 0.0, self.seed, t + 1, K.dptr(act),
+                                                     dt, stream))
+            if plan["sets"] is not None:
+                K.check(L.hb_rule_act_grouped(cfg_ref, state, nb, n_pad, self.first_game_id, K.dptr(plan["sets"]), rules_p, n_rules_p,
+                                              n_sets, self.seed, t + 1, K.dptr(act), None, stream))
+            for b, a, kind in plan["generic"]:
+                self._generic_moves(ch, b, a, kind, t, act)
+            env.step(act)
+            K.check(L.hb_eval_tally_grouped(cfg_ref, nb, n_pad, seat, t, K.dptr(act), *tally_bufs, K.current_stream()))
+            t += 1
+            if t % self.check_every == 0 or t == self.max_turns:
+                live = int(ch.counters[:, 0].sum().item())
+                if live == 0:
+                    break
+        if live != 0:
+            raise RuntimeError(f"{live} cross-play games still live after max_turns = {self.max_turns} turns")
+        illegal = env.illegal_count() - illegal0
+        if illegal:
+            raise RuntimeError(f"cross-play agents chose {illegal} illegal moves")
+        self.last_turns.append(t)
+        c = ch.counters.cpu()
+        fs, ln = ch.final_score.cpu(), ch.length.cpu()
+        B = self.max_score + 1
+        out = []
+        for b in range(nb):
+            r0 = b * n_pad
+            lengths = ln[r0:r0 + n]
+            # the turns the standalone Evaluator plays: it reads the live count every check_every turns
+            tb = min(self.max_turns, math.ceil(int(lengths.max()) / self.check_every) * self.check_every)
+            cb = c[b]
+            out.append(EvalResult(fs[r0:r0 + n], lengths, self.max_score, histogram=cb[1:1 + B], bombouts=int(cb[1 + B]),
+                                  moves=cb[2 + B:2 + B + 4 * P].view(P, 4), misplays=cb[2 + B + 4 * P:2 + B + 5 * P],
+                                  actions=ch.actions[:tb, r0:r0 + n].clone() if self.record_actions else None, turns=tb))
+        return out
+
+    def _generic_moves(self, ch, b, agent, kind, t, act):
+        """The generic path for block b: the agent's own eval_moves (or hb_rule_act) on the block's rows, the n real rows first
+        (the standalone shape), then the padding rows."""
+        env, n, n_pad = ch.env, self.n, self.n_pad
+        r0 = b * n_pad
+        if kind == "rule_generic":
+            L = K.lib()
+            sw = env.state_words
+            state = L.hb_env_state(env.h)
+            K.check(L.hb_rule_act(C.byref(self.cfg), C.c_void_p(state + 4 * sw * r0), n_pad, self.first_game_id, agent._tab,
+                                  len(agent.rules), self.seed, t + 1, C.c_void_p(act.data_ptr() + 4 * r0), None, K.current_stream()))
+            return
+        for lo, hi, store in ((r0, r0 + n, self._scratch), (r0 + n, r0 + n_pad, self._scratch_pad)):
+            if hi > lo:
+                agent.eval_moves((env, (env.obs_bits[lo:hi], env.legal[lo:hi])), self.seed, t + 1, act[lo:hi],
+                                 scratch=store.setdefault(agent, {}))

@@ -110,6 +110,7 @@ class SelfPlaySession:
         self._chains = {}        # seat -> _Chain
         self.native_steps = 0
         self._evaluators = {}    # (n_games, seed) -> hanabi_hip.evaluate.Evaluator
+        self._crossplays = {}    # (n_games, seed) -> hanabi_hip.crossplay.CrossPlay
 
     def _fused_step_ok(self):
         return bool(K.lib().hb_actor_fused_step_supported(self.env.h))
@@ -384,6 +385,21 @@ class SelfPlaySession:
             ev = self._evaluators[key] = Evaluator(config=self.env.cfg, n_games=n_games, seed=seed, first_game_id=rank * int(n_games),
                                                    device=self.env.device)
         return ev.run(self.agents if partners is None else partners)
+
+    def crossplay(self, pool, n_games=4096, seed=1, teams=None):
+        """Cross-play of a pool of agents (the session's own and others, DQN and rule-based mixed) on `n_games` fresh deals keyed
+        by `seed`: a hanabi_hip.crossplay.CrossPlayResult with one EvalResult per team. As evaluate(): updates in flight are
+        completed first, the session and its agents are left exactly as they were, and the CrossPlay is kept for the next call."""
+        self.flush()
+        from .crossplay import CrossPlay
+
+        key = (int(n_games), int(seed))
+        cp = self._crossplays.get(key)
+        if cp is None:
+            rank = self.env.first_game_id // self.env.n if self.env.n else 0   # (data-parallel: each rank its own deals)
+            cp = self._crossplays[key] = CrossPlay(config=self.env.cfg, n_games=n_games, seed=seed, first_game_id=rank * int(n_games),
+                                                   device=self.env.device)
+        return cp.run(pool, teams=teams)
 
     # ---- checkpoint / resume (SURVEY §8(f)-4) -----------------------------------------------------------------
     def checkpoint_state(self, include_replay=True):

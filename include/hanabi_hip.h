@@ -216,6 +216,16 @@ const uint32_t* hb_env_state(hb_env* env);
 int hb_rule_act(const hb_config* cfg, const uint32_t* state_rows_dev, int64_t n_games, int64_t first_game_id,
                 const hb_rule* rules, int32_t n_rules, uint64_t seed, uint64_t draw, int32_t* actions_dev,
                 int32_t* fired_dev, void* stream);
+/* hb_rule_act over n_blocks equal blocks of block_rows games (rows [b * block_rows, (b + 1) * block_rows) of state_rows_dev,
+ * actions_dev and fired_dev). Block b walks rule set set_of_block_dev[b] (-1: the block is skipped and nothing of it is
+ * written; so is a block whose index is not below n_sets) of the DEVICE tables rules_dev [n_sets][HB_MAX_RULES] and
+ * n_rules_dev [n_sets] (clamped to 0..HB_MAX_RULES); the game id of row r is first_game_id + r % block_rows. Each block's actions
+ * and fired indices are bit for bit those of hb_rule_act on that block's rows with that rule set. The rule kinds are read on
+ * the device and not checked (an unknown kind never fires).                                                                  */
+int hb_rule_act_grouped(const hb_config* cfg, const uint32_t* state_rows_dev, int64_t n_blocks, int64_t block_rows,
+                        int64_t first_game_id, const int32_t* set_of_block_dev, const hb_rule* rules_dev,
+                        const int32_t* n_rules_dev, int32_t n_sets, uint64_t seed, uint64_t draw, int32_t* actions_dev,
+                        int32_t* fired_dev, void* stream);
 
 /* Tuning knob for measurements: games handled per 64-lane wavefront (8, 16, 32 or 64); 0 (the default) picks 16,
  * or 32 for a packed-only step over >= 32768 games. The results do not depend on it.  */
@@ -633,6 +643,27 @@ int hb_actor_fused_act_step(hb_env* env, const uint32_t* obs_bits_dev, const int
                             float* agent_reward_dev, int8_t* agent_step_type_dev, int8_t* score_dev, void* stream);
 int hb_actor_fused_step_supported(const hb_env* env); /* 1: hb_actor_fused_act_step serves this env's configuration */
 
+/* Grouped one-kernel actor (cross-play: many networks over one batch of rows). hb_actor_fused_act_dt in which every 128-row tile
+ * (row block [128 t, 128 t + 128)) reads its own descriptor tiles_dev[t] (a DEVICE array of n_rows / 128 entries; n_rows must be a
+ * multiple of 128): the fragment-major copies and support of that tile's network and the Philox game id of the tile's first row.
+ * For the rows of an active tile, q_dev and actions_dev are bit for bit what hb_actor_fused_act_dt writes for the same rows with
+ * that tile's weights and first_game_id = tiles_dev[t].first_game_id; the workgroup of an inactive tile exits at once and writes
+ * nothing. One operand dtype per launch (1 bf16, 2 f16): a pool that mixes them takes one launch per dtype with complementary
+ * active tiles. All networks share obs_len / hidden / n_actions / n_atoms (checked against hb_actor_fused_supported).     */
+typedef struct hb_fused_tile {
+  const void* w1f;
+  const float* b1f;
+  const void* w2f;
+  const float* b2f;        /* that network's fragment-major copies (hb_actor_fused_pack_dt), 16-byte aligned */
+  const float* support;    /* [n_atoms] */
+  int64_t first_game_id;   /* Philox game id of the tile's first row */
+  int32_t active;          /* 0: the workgroup exits at once and writes nothing */
+  int32_t pad;
+} hb_fused_tile;
+int hb_actor_fused_act_grouped(const hb_fused_tile* tiles_dev, int64_t n_rows, const uint32_t* obs_bits_dev, const int8_t* legal_dev,
+                               int32_t obs_len, int32_t hidden, int32_t n_actions, int32_t n_atoms, float* q_dev, float epsilon,
+                               uint64_t seed, uint64_t draw, int32_t* actions_dev, int32_t dtype, void* stream);
+
 /* ---- greedy evaluation (csrc/eval.hip) ------------------------------------------------------------------------------------
  * A fixed set of n_games evaluation games (auto-reset off, lock-step: turn t is seat t mod P in every game) is played to the
  * end; hb_eval_tally is issued once per turn after hb_env_step on the same stream and tallies what that turn did.
@@ -654,6 +685,13 @@ int hb_eval_counters(const hb_config* cfg); /* number of int64 counters: 2 + col
 int hb_eval_tally(const hb_config* cfg, int64_t n_games, int32_t seat, int32_t turn, const int32_t* actions_dev,
                   const float* reward_dev, const int8_t* terminal_dev, const int8_t* score_dev, uint8_t* done_dev,
                   int8_t* final_score_dev, int16_t* length_dev, int64_t* counters_dev, void* stream);
+/* hb_eval_tally over n_blocks independent evaluations of block_games games each, stepped together (one seat and turn for all):
+ * the per-game arrays hold the blocks one after another and counters_dev is [n_blocks][hb_eval_counters(cfg)]. Block b's
+ * counters, done, final_score and length are exactly what hb_eval_tally computes on that block alone; a 2-D grid (one row of
+ * workgroups per block) keeps its per-workgroup reduction and <= 128 atomics per counter and block.                         */
+int hb_eval_tally_grouped(const hb_config* cfg, int64_t n_blocks, int64_t block_games, int32_t seat, int32_t turn,
+                          const int32_t* actions_dev, const float* reward_dev, const int8_t* terminal_dev, const int8_t* score_dev,
+                          uint8_t* done_dev, int8_t* final_score_dev, int16_t* length_dev, int64_t* counters_dev, void* stream);
 
 /* ---- One host call per step: hb_chain_run (csrc/chain.hip, round 3) ------------------------------------------------------
  * The session that drives DQNAgent (rlax_rainbow.py:277-339: explore / add_experience / update once per env step) issues ~25
