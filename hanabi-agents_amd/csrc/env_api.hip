@@ -78,9 +78,70 @@ struct hb_env {
   // consumed by a re-deal at step t is not needed again before step t + max_life: the refill launch runs every
   // `refill_period` = min(max_life, 3) steps instead of after every step (Hanabi-Full: 1 launch in 3; -Small: every step)
   int refill_period, since_refill;
+  // colour-permuted frames (hb_env_set_color_shuffle): allocated at the first call, used while `shuffled`
+  uint16_t* perms;      // [n, PERM_SLOTS] seat permutations of the deal in progress
+  uint8_t* shuf_mask;   // [n] shuffled seats of each game
+  bool shuffled;        // some seat of some game is shuffled: every step runs env_kernel_shuf
 };
 
 using hb::fail;
+
+// ---- colour-permuted frames ----------------------------------------------------------------------
+// Every game's seat permutations from its state row: sigma(seed, game id, deal counter = word 6, seat) for the seats in
+// shuf_mask[g], the identity for the others. What env_kernel_shuf draws when it deals a game, for all games at once
+// (after an import or a reset, and when the mask changes).
+template <int C>
+__global__ void color_perms_draw_kernel(const uint32_t* __restrict__ state, int sw, const uint8_t* __restrict__ mask, long long n, int P,
+                                        unsigned long long seed, long long first_gid, uint16_t* __restrict__ perms) {
+  const long long g = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const uint32_t episode = state[g * sw + 6], m = mask[g];
+  uint32_t e[hb::PERM_SLOTS / 2] = {0u, 0u, 0u, 0u};
+  for (int p = 0; p < P; ++p) {
+    const uint32_t sg = ((m >> p) & 1u) ? hb::draw_perm<C>(seed, static_cast<unsigned long long>(first_gid + g), episode, p)
+                                        : hb::identity_perm(C);
+    e[p >> 1] |= sg << (16 * (p & 1));
+  }
+  reinterpret_cast<uint4*>(perms)[g] = make_uint4(e[0], e[1], e[2], e[3]);
+}
+
+// out[g, p, c] = sigma_{g,p}(c); the identity everywhere when perms is NULL (an unshuffled env)
+__global__ void color_perms_export_kernel(const uint16_t* __restrict__ perms, long long n, int P, int C, uint8_t* __restrict__ out) {
+  const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n * P * C) return;
+  const long long g = i / (P * C);
+  const int r = static_cast<int>(i - g * P * C), p = r / C, c = r - p * C;
+  out[i] = static_cast<uint8_t>(perms ? (perms[g * hb::PERM_SLOTS + p] >> (3 * c)) & 7u : static_cast<uint32_t>(c));
+}
+
+// the [n, P, C] sigma(c) table as the kernels keep it: [n, PERM_SLOTS] u16 of 3-bit fields
+__global__ void color_perms_import_kernel(const uint8_t* __restrict__ in, long long n, int P, int C, uint16_t* __restrict__ perms) {
+  const long long g = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  uint32_t e[hb::PERM_SLOTS / 2] = {0u, 0u, 0u, 0u};
+  for (int p = 0; p < P; ++p) {
+    uint32_t sg = 0;
+    for (int c = 0; c < C; ++c) sg |= static_cast<uint32_t>(in[(g * P + p) * C + c] & 7u) << (3 * c);
+    e[p >> 1] |= sg << (16 * (p & 1));
+  }
+  reinterpret_cast<uint4*>(perms)[g] = make_uint4(e[0], e[1], e[2], e[3]);
+}
+
+static int draw_color_perms(hb_env* e, void* stream) {
+  if (!e->shuffled) return HB_OK;
+  const unsigned blocks = static_cast<unsigned>((e->n + 255) / 256);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int P = e->cfg.players, sw = e->var->state_words;
+  switch (e->cfg.colors) {
+    case 1: hipLaunchKernelGGL(color_perms_draw_kernel<1>, dim3(blocks), dim3(256), 0, st, e->state, sw, e->shuf_mask, e->n, P, e->seed, e->first_gid, e->perms); break;
+    case 2: hipLaunchKernelGGL(color_perms_draw_kernel<2>, dim3(blocks), dim3(256), 0, st, e->state, sw, e->shuf_mask, e->n, P, e->seed, e->first_gid, e->perms); break;
+    case 3: hipLaunchKernelGGL(color_perms_draw_kernel<3>, dim3(blocks), dim3(256), 0, st, e->state, sw, e->shuf_mask, e->n, P, e->seed, e->first_gid, e->perms); break;
+    case 4: hipLaunchKernelGGL(color_perms_draw_kernel<4>, dim3(blocks), dim3(256), 0, st, e->state, sw, e->shuf_mask, e->n, P, e->seed, e->first_gid, e->perms); break;
+    default: hipLaunchKernelGGL(color_perms_draw_kernel<5>, dim3(blocks), dim3(256), 0, st, e->state, sw, e->shuf_mask, e->n, P, e->seed, e->first_gid, e->perms); break;
+  }
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
 
 extern "C" {
 
@@ -139,6 +200,9 @@ int hb_env_create(const hb_config* cfg, int64_t n_games, uint64_t seed, int64_t 
   e->async_refill = false;
   e->refill_period = cfg->max_life < 3 ? cfg->max_life : 3;
   e->since_refill = 0;
+  e->perms = nullptr;
+  e->shuf_mask = nullptr;
+  e->shuffled = false;
   HB_HIP_OR(hipGetDevice(&e->device), delete e);
   const size_t bytes = static_cast<size_t>(n_games) * var->state_words * 4;
   HB_HIP_OR(hipMalloc(reinterpret_cast<void**>(&e->state), bytes), delete e);
@@ -163,6 +227,8 @@ int hb_env_destroy(hb_env* e) {
   if (e->illegal) (void)hipFree(e->illegal);
   if (e->next_deck) (void)hipFree(e->next_deck);
   if (e->refill) (void)hipFree(e->refill);
+  if (e->perms) (void)hipFree(e->perms);
+  if (e->shuf_mask) (void)hipFree(e->shuf_mask);
   if (e->side) { (void)hipStreamSynchronize(e->side); (void)hipStreamDestroy(e->side); }
   if (e->ev_step_done) (void)hipEventDestroy(e->ev_step_done);
   if (e->ev_refill_done) (void)hipEventDestroy(e->ev_refill_done);
@@ -260,6 +326,8 @@ static void prepare(hb_env* e, hb::EnvArgs& a) {
   }
   a.ev_start = e->ev_start;
   a.ev_stop = e->ev_stop;
+  a.perms = e->shuffled ? e->perms : nullptr;
+  a.shuf_mask = e->shuffled ? e->shuf_mask : nullptr;
 }
 
 static int launch(hb_env* e, hb::EnvArgs& a, void* stream) {
@@ -270,7 +338,9 @@ static int launch(hb_env* e, hb::EnvArgs& a, void* stream) {
   // and, with the selection fused in, 14.8 vs 17.5 us inside the training loop (0.142 vs 0.144 ms per step). int8 rows:
   // 13.3 (16) vs 14.2 us (32). Results do not depend on it.
   const int gpw = e->gpw ? e->gpw : ((a.obs_bits && !a.obs && e->n >= 32768) ? 32 : 16);
-  hb::LaunchFn fn = gpw == 8 ? e->var->g8 : (gpw == 16 ? e->var->g16 : (gpw == 32 ? e->var->g32 : e->var->g64));
+  const hb::EnvVariant& v = *e->var;
+  hb::LaunchFn fn = e->shuffled ? (gpw == 8 ? v.s8 : (gpw == 16 ? v.s16 : (gpw == 32 ? v.s32 : v.s64)))
+                                : (gpw == 8 ? v.g8 : (gpw == 16 ? v.g16 : (gpw == 32 ? v.g32 : v.g64)));
   fn(a, static_cast<hipStream_t>(stream));
   HB_HIP(hipGetLastError());
   return HB_OK;
@@ -289,6 +359,72 @@ static int check_out_packed(const void* bits, const void* obs, const void* legal
   return HB_OK;
 }
 
+int hb_env_set_color_shuffle(hb_env* e, const uint8_t* seat_mask_dev, uint8_t all_seats_mask, void* stream) {
+  if (all_seats_mask >> 5) return fail(HB_ERR_INVALID, "all_seats_mask 0x%x names a seat past the fifth", all_seats_mask);
+  if (seat_mask_dev && all_seats_mask) return fail(HB_ERR_INVALID, "pass either a per-game seat mask or all_seats_mask, not both");
+  if (!e) return fail(HB_ERR_INVALID, "null env");
+  const int P = e->cfg.players;
+  if (all_seats_mask >> P) return fail(HB_ERR_INVALID, "all_seats_mask 0x%x names a seat past the %d players", all_seats_mask, P);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  bool any = all_seats_mask != 0;
+  if (seat_mask_dev) {   // (a configuration call, not a step: one synchronised look at the mask to validate it)
+    std::vector<uint8_t> m(static_cast<size_t>(e->n));
+    HB_HIP(hipStreamSynchronize(st));
+    HB_HIP(hipMemcpy(m.data(), seat_mask_dev, m.size(), hipMemcpyDeviceToHost));
+    for (long long g = 0; g < e->n; ++g) {
+      if (m[g] >> P) return fail(HB_ERR_INVALID, "seat mask of game %lld is 0x%x: past the %d players", g, m[g], P);
+      any = any || m[g] != 0;
+    }
+  }
+  if (!any) {   // off: the plain kernels again
+    e->shuffled = false;
+    return HB_OK;
+  }
+  if (!e->perms) HB_HIP(hipMalloc(reinterpret_cast<void**>(&e->perms), static_cast<size_t>(e->n) * hb::PERM_SLOTS * 2));
+  if (!e->shuf_mask) HB_HIP(hipMalloc(reinterpret_cast<void**>(&e->shuf_mask), static_cast<size_t>(e->n)));
+  if (seat_mask_dev)
+    HB_HIP(hipMemcpyAsync(e->shuf_mask, seat_mask_dev, static_cast<size_t>(e->n), hipMemcpyDeviceToDevice, st));
+  else
+    HB_HIP(hipMemsetAsync(e->shuf_mask, all_seats_mask, static_cast<size_t>(e->n), st));
+  e->shuffled = true;
+  return draw_color_perms(e, stream);
+}
+
+int hb_env_color_perms(hb_env* e, uint8_t* out_dev, void* stream) {
+  if (!e) return fail(HB_ERR_INVALID, "null env");
+  if (!out_dev) return fail(HB_ERR_INVALID, "out_dev is required");
+  const long long total = e->n * e->cfg.players * e->cfg.colors;
+  hipLaunchKernelGGL(color_perms_export_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), e->shuffled ? e->perms : nullptr, e->n, e->cfg.players, e->cfg.colors, out_dev);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+int hb_env_color_shuffled(const hb_env* e) { return e && e->shuffled ? 1 : 0; }
+
+int hb_env_set_color_perms(hb_env* e, const uint8_t* perms_dev, void* stream) {
+  if (!e) return fail(HB_ERR_INVALID, "null env");
+  if (!perms_dev) return fail(HB_ERR_INVALID, "perms_dev is required");
+  if (!e->shuffled) return fail(HB_ERR_INVALID, "the env is not colour-shuffled (hb_env_set_color_shuffle first)");
+  const int P = e->cfg.players, C = e->cfg.colors;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  {   // (a configuration call: one synchronised look at the table to validate it)
+    std::vector<uint8_t> m(static_cast<size_t>(e->n) * P * C);
+    HB_HIP(hipStreamSynchronize(st));
+    HB_HIP(hipMemcpy(m.data(), perms_dev, m.size(), hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < m.size(); r += C) {
+      unsigned seen = 0;
+      for (int c = 0; c < C; ++c) seen |= m[r + c] < C ? 1u << m[r + c] : 0u;
+      if (seen != (1u << C) - 1u) return fail(HB_ERR_INVALID, "row %zu of perms_dev (game %zu, seat %zu) is not a permutation of 0..%d", r / C,
+                                               r / C / P, r / C % P, C - 1);
+    }
+  }
+  hipLaunchKernelGGL(color_perms_import_kernel, dim3(static_cast<unsigned>((e->n + 255) / 256)), dim3(256), 0, st, perms_dev, e->n, P, C,
+                     e->perms);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
 int hb_env_reset(hb_env* e, const uint8_t* mask_dev, int32_t start_player, void* stream) {
   if (!e) return fail(HB_ERR_INVALID, "null env");
   if (start_player < 0 || start_player >= e->cfg.players) return fail(HB_ERR_INVALID, "start_player out of range");
@@ -299,6 +435,7 @@ int hb_env_reset(hb_env* e, const uint8_t* mask_dev, int32_t start_player, void*
   if (int rc = join_refill(e, stream)) return rc;
   if (int rc = refill(e, stream)) return rc;  // the pool must hold deck(game, current deal counter)
   if (int rc = launch(e, a, stream)) return rc;
+  if (int rc = draw_color_perms(e, stream)) return rc;
   return refill(e, stream);
 }
 
@@ -416,6 +553,8 @@ int hb_actor_fused_act_step(hb_env* e, const uint32_t* obs_bits_dev, const int8_
                             float* reward_dev, int8_t* terminal_dev, float* agent_reward_dev, int8_t* agent_step_type_dev,
                             int8_t* score_dev, void* stream) {
   if (!e) return fail(HB_ERR_INVALID, "null env");
+  if (e->shuffled) return fail(HB_ERR_INVALID, "the fused policy + env kernel has no colour-permuted form: step a shuffled env with "
+                                               "hb_env_step_packed or hb_env_step_select_packed");
   if (int rc = check_out_packed(obs_bits_out_dev, nullptr, legal_out_dev)) return rc;
   hb::EnvArgs a{};
   a.mode = hb::MODE_STEP;
@@ -435,7 +574,7 @@ int hb_actor_fused_act_step(hb_env* e, const uint32_t* obs_bits_dev, const int8_
   return refill_async(e, stream);
 }
 
-int hb_actor_fused_step_supported(const hb_env* e) { return e && hb::actor_env_fused_supported(*e->var) ? 1 : 0; }
+int hb_actor_fused_step_supported(const hb_env* e) { return e && !e->shuffled && hb::actor_env_fused_supported(*e->var) ? 1 : 0; }
 
 #ifdef HB_STAMPS
 // diagnostic library only: step once with per-wavefront phase stamps written to stamps_dev
@@ -502,6 +641,7 @@ int hb_env_import_state(hb_env* e, const uint32_t* rows_dev, void* stream) {
   // deal counters may have changed: every pooled deck is stale
   if (int rc = join_refill(e, stream)) return rc;
   HB_HIP(hipMemsetAsync(e->refill, 1, static_cast<size_t>(e->n), static_cast<hipStream_t>(stream)));
+  if (int rc = draw_color_perms(e, stream)) return rc;   // the imported deals' permutations
   return refill(e, stream);
 }
 

@@ -68,6 +68,11 @@ struct EnvArgs {
   long long sel_first_gid;
   unsigned long long* stamps;  // diagnostic builds only (-DHB_STAMPS): 12 u64 per wavefront
   hipEvent_t ev_start, ev_stop;  // host-side only: optional per-dispatch timing events
+  // Colour-permuted frames, read only by the shuffled instantiations (SHUF): perms [n, PERM_SLOTS] u16,
+  // entry p = sigma of seat p as 3-bit fields (field c = the colour seat p sees for true colour c); shuf_mask [n]: the seats
+  // whose sigma is drawn when the game is dealt (a clear bit: identity)
+  uint16_t* perms;
+  const uint8_t* shuf_mask;
 };
 
 // In-kernel phase stamps (cdna_hip_programming.md §7): compiled in only with -DHB_STAMPS, into a
@@ -207,6 +212,53 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// ---- colour-permuted frames ------------------------------------------------------------------------
+constexpr int PERM_SLOTS = 8;  // u16 entries per game in EnvArgs::perms: seats 0..4, padded to one 16-byte load
+__host__ __device__ constexpr uint32_t factorial(int n) { return n <= 1 ? 1u : static_cast<uint32_t>(n) * factorial(n - 1); }
+// the identity of 0..C-1 as 3-bit fields
+__host__ __device__ constexpr uint32_t identity_perm(int C) { return C <= 0 ? 0u : identity_perm(C - 1) | (static_cast<uint32_t>(C - 1) << (3 * (C - 1))); }
+
+// sigma of seat p for the deal `episode` of game `gid`: Philox4x32-10 on counter (64 + p, episode, gid) and key seed (the deck
+// shuffle's counters have c0 < 64, so no draw is shared), index = (out[0] * C!) >> 32, and sigma = the index-th permutation of
+// 0..C-1 in lexicographic order (Lehmer decode; index 0 is the identity). Returned as 3-bit fields, field c = sigma(c).
+template <int C>
+__device__ __forceinline__ uint32_t draw_perm(unsigned long long seed, unsigned long long gid, uint32_t episode, int p) {
+  uint32_t r[4];
+  philox4x32_10(64u + static_cast<uint32_t>(p), episode, static_cast<uint32_t>(gid), static_cast<uint32_t>(gid >> 32),
+                static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), r);
+  uint32_t idx = static_cast<uint32_t>((static_cast<uint64_t>(r[0]) * factorial(C)) >> 32);
+  uint32_t pool = identity_perm(C), sig = 0;
+#pragma unroll
+  for (int i = 0; i < C; ++i) {
+    const uint32_t f = factorial(C - 1 - i);
+    const uint32_t d = idx / f;
+    idx -= d * f;
+    const uint32_t sh = 3u * d;
+    sig |= ((pool >> sh) & 7u) << (3 * i);
+    pool = (pool & ((1u << sh) - 1u)) | ((pool >> (sh + 3u)) << sh);  // drop the taken entry from the list
+  }
+  return sig;
+}
+
+// a C-bit colour mask as a seat with permutation sg sees it: bit c moves to bit sg(c) (SHUF false: unchanged)
+template <bool SHUF, int C>
+__device__ __forceinline__ uint32_t seen_colours(uint32_t m, uint32_t sg) {
+  if constexpr (!SHUF) {
+    return m;
+  } else {
+    uint32_t q = 0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) q |= ((m >> c) & 1u) << ((sg >> (3 * c)) & 7u);
+    return q;
+  }
+}
+
+// seat s's entry of a game's 16-byte perms row
+__device__ __forceinline__ uint32_t perm_of(const uint4& pm, int s) {
+  const uint32_t w = s < 2 ? pm.x : (s < 4 ? pm.y : pm.z);
+  return (w >> (16 * (s & 1))) & 0xFFFFu;
+}
+
 // 4 bits -> 4 bytes of 0/1 (bit i lands in byte i)
 __device__ __forceinline__ uint32_t spread4(uint32_t b) { return ((b & 15u) * 0x00204081u) & 0x01010101u; }
 
@@ -332,7 +384,11 @@ constexpr int env_lds_words() { return G * (K::SWP + K::NWP + K::LW); }
 // slice of env_lds_words<K, G>() words, `uid_in` the lane's move (MODE_STEP; ignored by the other modes, and by lanes past the
 // batch), `wslot` the wavefront's slot in the per-wavefront stats (g0 / G). Shared by env_kernel and by the one-kernel actor's
 // fused env tail (actor_fused.hip), so there is one copy of the rules.
-template <class K, int G>
+//
+// SHUF: every seat plays in its own colour frame. The move arrives in the mover's frame and is taken back
+// to the true colours before the rules run; the observation and legal mask are written in the frame of the seat to act; a game
+// dealt here draws its seats' permutations into a.perms. With SHUF false none of this is compiled in.
+template <class K, int G, bool SHUF = false>
 __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, int lane, uint32_t* const srow, int uid_in,
                                               long long wslot) {
   constexpr int P = K::P, C = K::C, R = K::R, H = K::H;
@@ -364,6 +420,10 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
     if ((mode == MODE_RESET && mask_in) || (mode == MODE_STEP && (a.flags & 0x100))) {   // (0x100: measurement aid, fetch always)
       nd[0] = ndp[0]; nd[1] = ndp[1]; nd[2] = ndp[2]; nd[3] = ndp[3];
     }
+  }
+  uint4 pm = make_uint4(0u, 0u, 0u, 0u);  // (SHUF) this game's seat permutations
+  if constexpr (SHUF) {
+    if (active) pm = reinterpret_cast<const uint4*>(a.perms)[gi];
   }
 
   // ---- phase 1: state rows HBM -> LDS (coalesced 16-byte loads) ---------------------------
@@ -427,6 +487,17 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
         for (int c = 0; c < C; ++c) fsum += fw(c);
         if (!(a.flags & 0x100) && (((w0 >> 10) & 7) <= 1 || (w0 & 63) == 0 || fsum >= C * R - 1)) {
           nd[0] = ndp[0]; nd[1] = ndp[1]; nd[2] = ndp[2]; nd[3] = ndp[3];
+        }
+      }
+      if constexpr (SHUF) {  // a reveal-colour move names the colour the mover sees: back to the true colour (sigma^-1)
+        const int xc0 = uid_in - 2 * H;
+        if (xc0 >= 0 && xc0 < (P - 1) * C) {
+          const uint32_t sgm = perm_of(pm, (w0 >> 13) & 7);
+          const int tgt = xc0 / C, seen = xc0 - tgt * C;
+          int c = 0;
+#pragma unroll
+          for (int k = 0; k < C; ++k) c = static_cast<int>((sgm >> (3 * k)) & 7u) == seen ? k : c;
+          uid_in = 2 * H + tgt * C + c;
         }
       }
       // The four move types are evaluated WITHOUT divergent branches: every effect is computed under a 0/1
@@ -596,6 +667,18 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
         row[K::W_KNOW + 2 * p + 1] = static_cast<uint32_t>(kn >> 32);
         w1 |= static_cast<uint32_t>(H) << (15 + 3 * p);
       }
+      if constexpr (SHUF) {  // the new deal's seat permutations (a pure function of seed, game id, deal counter and seat)
+        const uint32_t sm = a.shuf_mask[gi];
+        uint32_t e[PERM_SLOTS / 2] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+          const uint32_t sg = ((sm >> p) & 1u) ? draw_perm<C>(a.seed, static_cast<unsigned long long>(a.first_gid + gi), w6, p)
+                                               : identity_perm(C);
+          e[p >> 1] |= sg << (16 * (p & 1));
+        }
+        pm = make_uint4(e[0], e[1], e[2], e[3]);
+        reinterpret_cast<uint4*>(a.perms)[gi] = pm;
+      }
     }
     if (mode != MODE_OBSERVE) {
       row[0] = w0; row[1] = w1; row[2] = w2; row[3] = w3;
@@ -606,6 +689,9 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
 
     if (mode != MODE_RESET) {
       const int o = (w0 >> 13) & 7;
+      uint32_t sg = 0;  // (SHUF) the observer's permutation: true colour c is seen as colour sig(c)
+      if constexpr (SHUF) sg = perm_of(pm, o);
+      auto sig = [&](int c) -> int { return static_cast<int>((sg >> (3 * c)) & 7u); };
       if constexpr (LPG == 1) {
         const int deck_size = w0 & 63, info = (w0 >> 6) & 15, life = (w0 >> 10) & 7;
         BitAcc<K::NW> acc;
@@ -626,8 +712,14 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
               constexpr int i = decltype(I)::value;
               const int card = (hc >> (5 * i)) & 31;
               const bool have = i < n_p;
-              acc.template put<((rel - 1) * H + i) * K::BITS, K::BITS>(have ? (1u << card) : 0u);
-              if (have) { cmask |= 1u << (card / R); rmask |= 1u << (card % R); }
+              if constexpr (SHUF) {  // the card as the observer sees it; a colour hint is legal on the colour it sees
+                const int col = have ? card / R : 0, rk = card - col * R, sc = sig(col);
+                acc.template put<((rel - 1) * H + i) * K::BITS, K::BITS>(have ? (1u << (sc * R + rk)) : 0u);
+                if (have) { cmask |= 1u << sc; rmask |= 1u << rk; }
+              } else {
+                acc.template put<((rel - 1) * H + i) * K::BITS, K::BITS>(have ? (1u << card) : 0u);
+                if (have) { cmask |= 1u << (card / R); rmask |= 1u << (card % R); }
+              }
             });
             if (info > 0) {
               legal |= static_cast<uint64_t>(cmask) << (2 * H + (rel - 1) * C);
@@ -640,19 +732,38 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
         legal |= static_cast<uint64_t>(own) << H;
         // 2. board
         acc.template put64<K::BOARD_OFF, K::DECK_T>((1ull << deck_size) - 1ull);
-        static_for<C>([&](auto CI) {
-          constexpr int c = decltype(CI)::value;
-          acc.template put<K::FW_OFF + c * R, R>((1u << fw(c)) >> 1);
-        });
+        if constexpr (SHUF) {  // firework c moves to block sig(c)
+          uint32_t fwv = 0;
+          static_for<C>([&](auto CI) {
+            constexpr int c = decltype(CI)::value;
+            fwv |= ((1u << fw(c)) >> 1) << (R * sig(c));
+          });
+          acc.template put<K::FW_OFF, K::BITS>(fwv);
+        } else {
+          static_for<C>([&](auto CI) {
+            constexpr int c = decltype(CI)::value;
+            acc.template put<K::FW_OFF + c * R, R>((1u << fw(c)) >> 1);
+          });
+        }
         acc.template put<K::INFO_OFF, K::INFO>((1u << info) - 1u);
         acc.template put<K::LIFE_OFF, K::LIFE>((1u << life) - 1u);
         // 3. discards: one thermometer per card identity,
-        acc.template put64<K::DISC_OFF, K::D>(disc);  // kept in this very form in the state row
+        if constexpr (SHUF) {  // colour-major blocks of CPC bits: block c moves to block sig(c)
+          uint64_t dv = 0;
+          static_for<C>([&](auto CI) {
+            constexpr int c = decltype(CI)::value;
+            dv |= ((disc >> (c * K::CPC)) & ((1ull << K::CPC) - 1ull)) << (K::CPC * sig(c));
+          });
+          acc.template put64<K::DISC_OFF, K::D>(dv);
+        } else {
+          acc.template put64<K::DISC_OFF, K::D>(disc);  // kept in this very form in the state row
+        }
         // 4. most recent move, observer-relative
         {
           const uint32_t valid = w2 & 1u;
           const int la_player = (w2 >> 1) & 7, la_type = (w2 >> 4) & 3, la_ci = (w2 >> 6) & 7, la_toff = (w2 >> 9) & 7;
-          const int la_color = (w2 >> 12) & 7, la_rank = (w2 >> 15) & 7;
+          const int la_color_t = (w2 >> 12) & 7, la_rank = (w2 >> 15) & 7;
+          const int la_color = SHUF ? sig(la_color_t) : la_color_t;
           const uint32_t la_scored = (w2 >> 18) & 1u, la_info = (w2 >> 19) & 1u, la_mask = (w2 >> 20) & 31u;
           int actor = la_player - o;
           if (actor < 0) actor += P;
@@ -685,7 +796,8 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
           static_for<H>([&](auto I) {
             constexpr int i = decltype(I)::value;
             const uint32_t k = static_cast<uint32_t>(kn >> (12 * i)) & 0xFFFu;
-            const uint32_t cp = k & 31u, rp = (k >> 5) & 31u;
+            // (SHUF: colour-plausibility bit c moves to bit sig(c), for the plausible identities and the revealed colour alike)
+            const uint32_t cp = seen_colours<SHUF, C>(k & 31u, sg), rp = (k >> 5) & 31u;
             const uint32_t plaus = __umul24(spread_colors<C, R>(cp), rp);  // disjoint R-bit fields: no carries
             const uint32_t ch = (k >> 10) & 1u, rh = (k >> 11) & 1u;
             uint64_t v = plaus | (static_cast<uint64_t>(ch ? cp : 0u) << K::BITS) |
@@ -778,6 +890,19 @@ __global__ __launch_bounds__(256) void env_kernel(const EnvArgs a) {
   env_wave_step<K, G>(a, g0, lane, lds + wave * env_lds_words<K, G>(), uid_in, wslot);
 }
 
+// the same step in colour-permuted frames: every move, observation and legal mask in the acting seat's frame
+template <class K, int G>
+__global__ __launch_bounds__(256) void env_kernel_shuf(const EnvArgs a) {
+  __shared__ uint32_t lds[4 * env_lds_words<K, G>()];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const long long wslot = static_cast<long long>(blockIdx.x) * 4 + wave;
+  const long long g0 = wslot * G;
+  int uid_in = 0;
+  if (a.mode == MODE_STEP && lane < G && g0 + lane < a.n) uid_in = a.sel_q ? select_action<K::A>(a, g0 + lane) : a.actions[g0 + lane];
+  env_wave_step<K, G, true>(a, g0, lane, lds + wave * env_lds_words<K, G>(), uid_in, wslot);
+}
+
 // Deck pool refill: regenerates next_deck[g] for every game whose flag is set. One wavefront scans 64 games
 // and shuffles the flagged ones one at a time with all lanes: lane j draws Philox4x32-10(j, episode, game id;
 // seed), key = 26 random bits | j (all distinct); its rank among the D keys comes from D v_readlane
@@ -840,17 +965,30 @@ void launch_env(const EnvArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL((env_kernel<K, G>), dim3(blocks), dim3(256), 0, stream, a);
 }
 
+template <class K, int G>
+void launch_env_shuf(const EnvArgs& a, hipStream_t stream) {
+  const long long per_block = 4LL * G;
+  const unsigned blocks = static_cast<unsigned>((a.n + per_block - 1) / per_block);
+  if (blocks == 0) return;
+  if (a.ev_start && a.ev_stop)
+    hipExtLaunchKernelGGL((env_kernel_shuf<K, G>), dim3(blocks), dim3(256), 0, stream, a.ev_start, a.ev_stop, 0, a);
+  else
+    hipLaunchKernelGGL((env_kernel_shuf<K, G>), dim3(blocks), dim3(256), 0, stream, a);
+}
+
 using LaunchFn = void (*)(const EnvArgs&, hipStream_t);
 struct EnvVariant {
   int P, C, R, H, INFO, LIFE;
   int obs_len, n_actions, deck, state_words;
   LaunchFn g8, g16, g32, g64, refill;
+  LaunchFn s8, s16, s32, s64;  // the colour-permuted step (env_kernel_shuf)
 };
 
 template <class K>
 constexpr EnvVariant make_variant() {
   return EnvVariant{K::P, K::C, K::R, K::H, K::INFO, K::LIFE, K::OBS_LEN, K::A, K::D, K::SW,
-                    &launch_env<K, 8>, &launch_env<K, 16>, &launch_env<K, 32>, &launch_env<K, 64>, &launch_refill<K>};
+                    &launch_env<K, 8>, &launch_env<K, 16>, &launch_env<K, 32>, &launch_env<K, 64>, &launch_refill<K>,
+                    &launch_env_shuf<K, 8>, &launch_env_shuf<K, 16>, &launch_env_shuf<K, 32>, &launch_env_shuf<K, 64>};
 }
 
 // The one-kernel actor with the env step as its tail (actor_fused.hip; hb_actor_fused_act_step): the configurations it is compiled

@@ -123,6 +123,10 @@ SIGNATURES = {
     "hb_env_export_state": (C.c_int, [_P, _P, _P]),
     "hb_env_import_state": (C.c_int, [_P, _P, _P]),
     "hb_env_state": (_P, [_P]),
+    "hb_env_set_color_shuffle": (C.c_int, [_P, _P, C.c_uint8, _P]),
+    "hb_env_color_perms": (C.c_int, [_P, _P, _P]),
+    "hb_env_color_shuffled": (C.c_int, [_P]),
+    "hb_env_set_color_perms": (C.c_int, [_P, _P, _P]),
     "hb_rule_act": (C.c_int, [_CFG, _P, _I64, _I64, C.POINTER(HbRule), _I32, _U64, _U64, _P, _P, _P]),
     "hb_rule_act_grouped": (C.c_int, [_CFG, _P, _I64, _I64, _I64, _P, _P, _P, _I32, _U64, _U64, _P, _P, _P]),
     "hb_random_legal_actions": (C.c_int, [_P, _I64, _I32, _U64, _U64, _I64, _P, _P]),

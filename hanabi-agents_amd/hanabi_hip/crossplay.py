@@ -19,6 +19,8 @@ teams on the same deals and returns one `EvalResult` per team, each equal to wha
   descriptor and rule-set tables are uploaded once per chunk and run, not per turn. Agents off the one-kernel actor take their
   own eval_moves on row slices of their block (the generic path): rows [r0, r0 + n) in one call — exactly the standalone
   shape, which the library GEMMs' kernel choice and the torch path's generator depend on — then the padding rows.
+* `color_shuffle=True`: as Evaluator's, per block: the seats of a block held by DQN-style agents play in colour-permuted frames,
+  with the permutations the standalone Evaluator draws for the same deals (game id first_game_id + g, not the chunk row).
 * Seeds, draws and game ids are those of Evaluator.run: Philox seed = the evaluator's seed, draw = turn + 1; a DQN agent keys
   its row r by its own first_game_id + r, a rule agent by the evaluator's first_game_id + r. No agent's draw counter,
   histogram, noise or buffers move.
@@ -31,7 +33,7 @@ import torch
 
 from . import _capi as K
 from .env import HanabiEnv
-from .evaluate import EvalResult, max_turns
+from .evaluate import EvalResult, max_turns, shuffle_mask
 
 TILE = 128   # rows per workgroup of the one-kernel actor, and per hb_fused_tile
 
@@ -139,8 +141,9 @@ class CrossPlay:
     (teams of one chunk run in lock-step; more teams than fit take several chunks one after another)."""
 
     def __init__(self, game="Hanabi-Full", players=2, n_games=4096, seed=1, first_game_id=0, max_rows=262144, record_actions=False,
-                 device=None, config=None, check_every=8):
+                 device=None, config=None, check_every=8, color_shuffle=False):
         n_games = int(n_games)
+        self.color_shuffle = bool(color_shuffle)
         if n_games < 1:
             raise ValueError(f"n_games must be >= 1, got {n_games}")
         if int(max_rows) < 1:
@@ -165,6 +168,7 @@ class CrossPlay:
         self.max_score = cfg.colors * cfg.ranks
         self.n_counters = K.lib().hb_eval_counters(C.byref(cfg))
         self._deals = None    # [n_pad, state words]: built by the first run (construction needs no GPU)
+        self._perms = None    # color_shuffle: [n_pad, P, C] every seat's permutation of those deals
         self._chunks = {}     # block count -> _Chunk
         # agent -> eval_moves scratch of the generic path: the block's n rows, and its padding rows
         self._scratch = weakref.WeakKeyDictionary()
@@ -179,6 +183,9 @@ class CrossPlay:
             env = HanabiEnv(config=self.cfg, n_games=self.n_pad, seed=self.seed, first_game_id=self.first_game_id, device=self.device,
                             packed=True)
             self._deals = env.export_state()
+            if self.color_shuffle:   # (the rows are byte-identical to an unshuffled env's)
+                env.set_color_shuffle(True, observe=False)
+                self._perms = env.color_perms()
             self.device = env.device
         ch = self._chunks.get(nb)
         if ch is None:
@@ -230,7 +237,8 @@ class CrossPlay:
                 n_rules_dev = torch.tensor([len(a.rules) for a in rule_sets], dtype=torch.int32, device=dev)
             chunk_teams = teams[first:first + nb]
             plans = [self._seat_plan(ch, [pool[t[s]] for t in chunk_teams], kinds) for s in range(self.players)]
-            out = self._play(ch, plans, rules_dev, n_rules_dev, len(rule_sets))
+            masks = [shuffle_mask([pool[i] for i in t]) for t in chunk_teams] if self.color_shuffle else None
+            out = self._play(ch, plans, rules_dev, n_rules_dev, len(rule_sets), masks)
             for b, res in enumerate(out):
                 results[first + b] = res
         return CrossPlayResult(teams, results, k, self.players, default)
@@ -270,9 +278,19 @@ class CrossPlay:
         return dict(tiles=tile_dev, hidden=hidden.pop() if hidden else 0, n_atoms=atoms.pop() if atoms else 0, sets=set_dev,
                     generic=generic, keep=keep)
 
-    def _play(self, ch, plans, rules_dev, n_rules_dev, n_sets):
+    def _play(self, ch, plans, rules_dev, n_rules_dev, n_sets, masks=None):
         env, L, cfg = ch.env, K.lib(), self.cfg
+        perms = None
+        if masks is not None:
+            m = torch.tensor(masks, dtype=torch.uint8, device=env.device).repeat_interleave(self.n_pad)
+            env.set_color_shuffle(m, observe=False)
         env.import_state(ch.rows0)
+        if masks is not None and env.color_shuffled:
+            # the standalone Evaluator's permutations of these deals, block by block, on the block's shuffled seats only
+            seat_on = ((m[:, None] >> torch.arange(self.players, device=env.device, dtype=torch.uint8)) & 1).bool()
+            ident = torch.arange(cfg.colors, device=env.device, dtype=torch.uint8).expand(ch.rows, self.players, cfg.colors)
+            perms = torch.where(seat_on[:, :, None], self._perms.repeat(ch.nb, 1, 1), ident).contiguous()
+            env.set_color_perms(perms)
         env.observe()
         illegal0 = env.illegal_count()
         ch.done.copy_(ch.done0)
@@ -326,7 +344,8 @@ class CrossPlay:
             cb = c[b]
             out.append(EvalResult(fs[r0:r0 + n], lengths, self.max_score, histogram=cb[1:1 + B], bombouts=int(cb[1 + B]),
                                   moves=cb[2 + B:2 + B + 4 * P].view(P, 4), misplays=cb[2 + B + 4 * P:2 + B + 5 * P],
-                                  actions=ch.actions[:tb, r0:r0 + n].clone() if self.record_actions else None, turns=tb))
+                                  actions=ch.actions[:tb, r0:r0 + n].clone() if self.record_actions else None, turns=tb,
+                                  perms=perms[r0:r0 + n] if perms is not None and masks[b] else None))
         return out
 
     def _generic_moves(self, ch, b, agent, kind, t, act):

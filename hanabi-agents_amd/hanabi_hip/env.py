@@ -12,6 +12,10 @@ this object and rewritten in place by every step (zero host traffic).
 2-player full Hanabi); `obs` is then expanded from it on access (`hb_obs_unpack`), bit for bit what
 the unpacked mode writes. The DQN agent, the replay ring and the actor / learner kernels consume
 the packed rows directly (`RlaxRainbowParams(packed_obs=True)`).
+
+`color_shuffle=True` (or a tuple of seats): colour-permuted frames (Other-Play). Every seat of every
+game sees the colours through its own permutation, drawn at each deal; observations, legal masks and the moves the acting seat
+submits are all in that seat's frame. `color_perms()` returns the permutations, `hanabi_hip.symmetry` maps logged data.
 """
 import ctypes as C
 
@@ -23,7 +27,7 @@ from . import _capi as K
 class HanabiEnv:
     def __init__(self, game="Hanabi-Full", players=2, n_games=1, seed=1234, first_game_id=0, auto_reset=True,
                  lockstep=True, lenient_reward=False, device=None, config=None, decks=None, start_player=0,
-                 games_per_wave=None, packed=False):
+                 games_per_wave=None, packed=False, color_shuffle=False):
         if not torch.cuda.is_available():
             raise K.HbError("HanabiEnv needs an MI355X: torch.cuda.is_available() is False and there is no CPU path")
         self.L = K.lib()
@@ -61,6 +65,9 @@ class HanabiEnv:
             self.set_games_per_wave(games_per_wave)
         if decks is not None:
             self.set_decks(decks)
+        self._shuffle_mask = 0     # int seat mask, or the [n] uint8 tensor last passed to set_color_shuffle
+        if color_shuffle is not None and color_shuffle is not False:
+            self.set_color_shuffle(color_shuffle, observe=False)
         self.reset(start_player=start_player)
 
     @property
@@ -105,6 +112,51 @@ class HanabiEnv:
         d = torch.as_tensor(decks, dtype=torch.uint8).reshape(self.n, self.deck_size).contiguous().to(self.device)
         self._decks = d  # keep the borrowed buffer alive
         K.check(self.L.hb_env_set_decks(self.h, K.dptr(d)))
+
+    def set_color_shuffle(self, mask, observe=True):
+        """Colour-permuted frames for the seats in `mask`: True (every seat), False / 0 (off), a tuple of seats, an int bit
+        mask, or an [n] uint8 tensor of per-game masks. The seats' permutations are drawn at once for the deals in progress
+        (a pure function of seed, game id, deal counter and seat), and obs / legal are refreshed in the new frames unless
+        observe=False. Rule-based agents read the true state and must sit in unshuffled seats."""
+        from . import symmetry
+
+        if isinstance(mask, torch.Tensor):
+            m = mask.to(device=self.device, dtype=torch.uint8).contiguous()
+            if m.shape != (self.n,):
+                raise ValueError(f"a per-game seat mask has shape ({self.n},), got {tuple(m.shape)}")
+            K.check(self.L.hb_env_set_color_shuffle(self.h, K.dptr(m), 0, K.current_stream()))
+            self._shuffle_mask = m
+        else:
+            bits = symmetry.seat_mask(mask, self.players)
+            K.check(self.L.hb_env_set_color_shuffle(self.h, None, bits, K.current_stream()))
+            self._shuffle_mask = bits
+        if observe:
+            self.observe()
+
+    @property
+    def color_shuffle(self):
+        """The seat mask in force: an int (every game alike) or the [n] uint8 tensor passed to set_color_shuffle; 0 = off."""
+        return self._shuffle_mask if self.color_shuffled else 0
+
+    @property
+    def color_shuffled(self):
+        return bool(self.L.hb_env_color_shuffled(self.h))
+
+    def color_perms(self, out=None):
+        """[n, players, colors] uint8: perms[g, p, c] = the colour seat p of game g sees for true colour c, in the deal in
+        progress (the identity for unshuffled seats)."""
+        if out is None:
+            out = torch.empty((self.n, self.players, self.cfg.colors), dtype=torch.uint8, device=self.device)
+        K.check(self.L.hb_env_color_perms(self.h, K.dptr(out), K.current_stream()))
+        return out
+
+    def set_color_perms(self, perms):
+        """Overwrite the permutations of the deals in progress ([n, players, colors] uint8, each row a permutation) until each
+        game is dealt again. The env must be colour-shuffled. Refresh obs / legal with observe() afterwards."""
+        p = torch.as_tensor(perms).to(device=self.device, dtype=torch.uint8).contiguous()
+        if p.shape != (self.n, self.players, self.cfg.colors):
+            raise ValueError(f"perms has shape {(self.n, self.players, self.cfg.colors)}, got {tuple(p.shape)}")
+        K.check(self.L.hb_env_set_color_perms(self.h, K.dptr(p), K.current_stream()))
 
     # -- stepping ----------------------------------------------------------------------------
     def reset(self, mask=None, start_player=0):

@@ -14,6 +14,10 @@ the separate evaluation env of its external session). `Evaluator` does that with
   `agents[seat].eval_moves` -> `HanabiEnv.step` -> `hb_eval_tally` (include/hanabi_hip.h, csrc/eval.hip). The agents' moves use
   Philox seed = the evaluator's `seed`, draw = turn + 1; no agent's own draw counter, histogram or buffers move.
 * The host reads the live-game counter every `check_every` turns and stops at 0; `max_turns(cfg)` bounds the loop.
+* `color_shuffle=True`: the seats held by DQN-style agents (vectorised observations) play in colour-permuted frames
+  (the "OP score"); rule-based seats read the true state and stay unshuffled. The permutations are those
+  of the deals (seed, game id, deal counter 1, seat) and come back as `EvalResult.perms`; recorded actions are in each seat's
+  own frame.
 """
 import ctypes as C
 import math
@@ -46,14 +50,22 @@ def max_turns(cfg):
 MOVE_KINDS = ("discard", "play", "reveal_color", "reveal_rank")
 
 
+def shuffle_mask(team):
+    """Seat mask of a team's colour-shuffled seats: those whose agent reads vectorised observations (DQN-style agents).
+    Rule-based agents read the true state rows and keep the true colours."""
+    return sum(1 << s for s, a in enumerate(team) if a.requires_vectorized_observation())
+
+
 class EvalResult:
     """Outcome of one evaluation: plain CPU tensors and ints.
 
     scores [n] int32 final scores (0 after a bomb-out), lengths [n] int32 turns played, histogram [max_score + 1] int64,
     bombouts (games that lost every life), moves [P, 4] int64 per seat and kind (MOVE_KINDS), misplays [P] int64 per seat,
-    actions [turns, n] int32 (record_actions only; rows of finished games hold moves the env ignored), turns = turns played."""
+    actions [turns, n] int32 (record_actions only; rows of finished games hold moves the env ignored), turns = turns played,
+    perms [n, P, C] uint8 (colour-shuffled evaluations only): perms[g, p, c] = the colour seat p saw for true colour c."""
 
-    def __init__(self, scores, lengths, max_score, histogram=None, bombouts=0, moves=None, misplays=None, actions=None, turns=None):
+    def __init__(self, scores, lengths, max_score, histogram=None, bombouts=0, moves=None, misplays=None, actions=None, turns=None,
+                 perms=None):
         self.scores = torch.as_tensor(scores).to("cpu", torch.int32)
         self.lengths = torch.as_tensor(lengths).to("cpu", torch.int32)
         n = self.scores.numel()
@@ -67,6 +79,7 @@ class EvalResult:
         self.misplays = None if misplays is None else torch.as_tensor(misplays).to("cpu", torch.int64)
         self.actions = None if actions is None else actions.cpu()
         self.turns = int(turns) if turns is not None else int(self.lengths.max())
+        self.perms = None if perms is None else torch.as_tensor(perms).to("cpu", torch.uint8)
 
     @property
     def n_games(self):
@@ -115,10 +128,11 @@ class Evaluator:
     never auto-reset and score without leniency). first_game_id: global id of game 0 (keys the deals and the agents' draws)."""
 
     def __init__(self, game="Hanabi-Full", players=2, n_games=4096, seed=1, first_game_id=0, device=None, record_actions=False,
-                 config=None, check_every=8):
+                 config=None, check_every=8, color_shuffle=False):
         n_games = int(n_games)
         if n_games < 1:
             raise ValueError(f"n_games must be >= 1, got {n_games}")
+        self.color_shuffle = bool(color_shuffle)
         if config is not None:
             cfg = K.HbConfig(config.players, config.colors, config.ranks, config.hand_size, config.max_info, config.max_life, 0)
         else:
@@ -166,8 +180,13 @@ class Evaluator:
                 raise TypeError(f"{type(a).__name__} has no eval_moves()")
         self._setup()
         env, L, cfg = self.env, K.lib(), self.cfg
+        perms = None
+        if self.color_shuffle:   # DQN seats shuffled, rule seats not; the import below draws the deals' permutations
+            env.set_color_shuffle(shuffle_mask(agents), observe=False)
         env.import_state(self.rows0)
         env.observe()
+        if self.color_shuffle and env.color_shuffled:
+            perms = env.color_perms()
         illegal0 = env.illegal_count()
         self.done.zero_()
         self.final_score.zero_()
@@ -202,4 +221,4 @@ class Evaluator:
         B = self.max_score + 1
         return EvalResult(self.final_score, self.length, self.max_score, histogram=c[1:1 + B], bombouts=int(c[1 + B]),
                           moves=c[2 + B:2 + B + 4 * P].view(P, 4), misplays=c[2 + B + 4 * P:2 + B + 5 * P],
-                          actions=self.actions[:t].clone() if self.record_actions else None, turns=t)
+                          actions=self.actions[:t].clone() if self.record_actions else None, turns=t, perms=perms)

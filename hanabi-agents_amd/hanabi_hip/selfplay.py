@@ -29,6 +29,7 @@ class SelfPlaySession:
                  learner_stream=True, learner_priority=-1, stream_per_agent=None, fuse_select=True, split_update=True,
                  native_chain=True, early_update=True):
         assert len(agents) == env.players, "one agent per seat"
+        self._check_color_shuffle(env, agents)
         self.env = env
         self.agents = list(agents)
         self.updates_per_step = int(updates_per_step)
@@ -111,6 +112,20 @@ class SelfPlaySession:
         self.native_steps = 0
         self._evaluators = {}    # (n_games, seed) -> hanabi_hip.evaluate.Evaluator
         self._crossplays = {}    # (n_games, seed) -> hanabi_hip.crossplay.CrossPlay
+
+    @staticmethod
+    def _check_color_shuffle(env, agents):
+        """Training on a colour-shuffled env is Other-Play: replay then holds each seat's own frames and
+        moves. Rule-based agents read the true state rows, so they cannot sit in a shuffled seat."""
+        if not getattr(env, "color_shuffled", False):
+            return
+        m = env.color_shuffle
+        if isinstance(m, torch.Tensor):
+            m = sum(1 << s for s in range(env.players) if bool(((m >> s) & 1).any()))
+        seats = int(m)
+        for s, a in enumerate(agents):
+            if (seats >> s) & 1 and not a.requires_vectorized_observation():
+                raise ValueError(f"seat {s}: {type(a).__name__} reads the true state and cannot play in a colour-shuffled seat")
 
     def _fused_step_ok(self):
         return bool(K.lib().hb_actor_fused_step_supported(self.env.h))
@@ -370,7 +385,7 @@ class SelfPlaySession:
         self.flush()
 
     # ---- greedy evaluation (hanabi_hip.evaluate) -----------------------------------------------------------------
-    def evaluate(self, n_games=4096, seed=1, partners=None):
+    def evaluate(self, n_games=4096, seed=1, partners=None, color_shuffle=False):
         """Greedy mean score of the session's agents (or of `partners`: one agent per seat, DQN and rule-based mixed) over a
         fixed set of `n_games` fresh deals keyed by `seed`: an EvalResult. Updates in flight are completed first (flush());
         the session's env, counters, command arrays and agents are left exactly as they were, so training continues as if
@@ -378,27 +393,27 @@ class SelfPlaySession:
         self.flush()
         from .evaluate import Evaluator
 
-        key = (int(n_games), int(seed))
+        key = (int(n_games), int(seed), bool(color_shuffle))
         ev = self._evaluators.get(key)
         if ev is None:
             rank = self.env.first_game_id // self.env.n if self.env.n else 0   # (data-parallel: each rank its own deals)
             ev = self._evaluators[key] = Evaluator(config=self.env.cfg, n_games=n_games, seed=seed, first_game_id=rank * int(n_games),
-                                                   device=self.env.device)
+                                                   device=self.env.device, color_shuffle=color_shuffle)
         return ev.run(self.agents if partners is None else partners)
 
-    def crossplay(self, pool, n_games=4096, seed=1, teams=None):
+    def crossplay(self, pool, n_games=4096, seed=1, teams=None, color_shuffle=False):
         """Cross-play of a pool of agents (the session's own and others, DQN and rule-based mixed) on `n_games` fresh deals keyed
         by `seed`: a hanabi_hip.crossplay.CrossPlayResult with one EvalResult per team. As evaluate(): updates in flight are
         completed first, the session and its agents are left exactly as they were, and the CrossPlay is kept for the next call."""
         self.flush()
         from .crossplay import CrossPlay
 
-        key = (int(n_games), int(seed))
+        key = (int(n_games), int(seed), bool(color_shuffle))
         cp = self._crossplays.get(key)
         if cp is None:
             rank = self.env.first_game_id // self.env.n if self.env.n else 0   # (data-parallel: each rank its own deals)
             cp = self._crossplays[key] = CrossPlay(config=self.env.cfg, n_games=n_games, seed=seed, first_game_id=rank * int(n_games),
-                                                   device=self.env.device)
+                                                   device=self.env.device, color_shuffle=color_shuffle)
         return cp.run(pool, teams=teams)
 
     # ---- checkpoint / resume (SURVEY §8(f)-4) -----------------------------------------------------------------

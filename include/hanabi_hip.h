@@ -167,6 +167,33 @@ int hb_env_stats(hb_env* env, int64_t* episodes, int64_t* score_sum);
 int hb_env_export_state(hb_env* env, uint32_t* rows_dev, void* stream);
 int hb_env_import_state(hb_env* env, const uint32_t* rows_dev, void* stream);
 
+/* ---- colour-permuted frames (Other-Play, Hu et al. 2020) ------------------------------------
+ * Each game g and seat p has a permutation sigma_{g,p} of the colours, fixed for one deal: the seat sees true colour c as
+ * sigma(c). The observation and legal mask the env writes are in the frame of the seat to act, and the move it submits is in
+ * that frame too (reveal-colour uid 2H + o*C + c names the colour the seat sees; the env applies 2H + o*C + sigma^-1(c); every
+ * other uid is colour-free). The colour-carrying sections of the encoder move by colour block: the other hands' cards,
+ * fireworks, discards, the last move's revealed colour and card, and each knowledge slot's plausible identities and
+ * revealed-colour bits. sigma_{g,p} = the index-th permutation of 0..C-1 in lexicographic order, index =
+ * (out[0] * C!) >> 32 of Philox4x32-10(counter 64 + p, deal counter (state word 6), game id lo, hi; key seed lo, hi), drawn
+ * whenever the game is dealt. State rows, decks and hb_env_export_state stay byte-identical to an unshuffled env; importing
+ * rows or resetting recomputes every game's sigma from its row.
+ *
+ * hb_env_set_color_shuffle: seat_mask_dev [n] uint8 (bit p: seat p of that game is shuffled) or NULL, in which case
+ * all_seats_mask applies to every game; passing both non-zero is an error, as is a bit past the env's players. An all-zero
+ * mask turns the option off (the plain kernels again). The seats' sigma is drawn at once for the deals in progress, so the
+ * observation buffers are stale until the next hb_env_observe / step. Rule-based agents (hb_rule_act) read true state rows
+ * and belong in unshuffled seats. A shuffled env has no one-launch actor + env step (hb_actor_fused_step_supported is 0).
+ * Synchronises `stream` when seat_mask_dev is given (to validate it).
+ * hb_env_color_perms: out_dev [n, players, colors] uint8 = sigma_{g,p}(c) (the identity for an unshuffled env or seat).
+ * hb_env_color_shuffled: 1 when some seat of some game is shuffled.
+ * hb_env_set_color_perms: overwrite the permutations of the deals in progress with perms_dev [n, players, colors] (each row a
+ * permutation of 0..colors-1; synchronises `stream` to validate it). They hold until the game is dealt again, when the rule
+ * above draws the next ones. For evaluations that replay fixed deals under another game-id layout (hanabi_hip.crossplay).  */
+int hb_env_set_color_shuffle(hb_env* env, const uint8_t* seat_mask_dev, uint8_t all_seats_mask, void* stream);
+int hb_env_color_perms(hb_env* env, uint8_t* out_dev, void* stream);
+int hb_env_color_shuffled(const hb_env* env);
+int hb_env_set_color_perms(hb_env* env, const uint8_t* perms_dev, void* stream);
+
 /* Uniform-random legal policy used by bench/tests (Philox(seed, game, draw)):
  * actions_dev[g] = the k-th set entry of legal_dev[g], k uniform. No legal move -> 0.  */
 int hb_random_legal_actions(const int8_t* legal_dev, int64_t n_games, int32_t n_actions, uint64_t seed,

@@ -5,6 +5,10 @@ sys.path.insert(0, os.path.join(ROOT, "hanabi-agents_amd"))
 import hanabi_hip
 from hanabi_agents.rlax_dqn import ActionSpec, DQNAgent, ObservationSpec, RlaxRainbowParams
 from hanabi_hip.selfplay import SelfPlaySession
+# --color-shuffle: every seat in colour-permuted frames (Other-Play)
+color_shuffle = "--color-shuffle" in sys.argv
+if color_shuffle:
+    sys.argv.remove("--color-shuffle")
 game = sys.argv[1] if len(sys.argv) > 1 else "Hanabi-Small"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 6000
 n = int(sys.argv[3]) if len(sys.argv) > 3 else 2048
@@ -13,7 +17,8 @@ flags = hanabi_hip.FLAG_AUTO_RESET | hanabi_hip.FLAG_RESET_START_NEXT
 lag = int(os.environ.get("HB_ACTOR_LAG", "0"))   # 1: asynchronous actor (RlaxRainbowParams.actor_lag)
 packed = bool(int(os.environ.get("HB_PACKED", "1")))
 players = int(os.environ.get("HB_PLAYERS", "2"))
-env = hanabi_hip.HanabiEnv(config=hanabi_hip.make_config(game, players, flags), n_games=n, seed=int(os.environ.get("HB_SEED", "1")), packed=packed)
+env = hanabi_hip.HanabiEnv(config=hanabi_hip.make_config(game, players, flags), n_games=n, seed=int(os.environ.get("HB_SEED", "1")), packed=packed,
+                           color_shuffle=color_shuffle)
 params = RlaxRainbowParams(compute_dtype=os.environ.get("HB_DTYPE", "bfloat16"),   # (float16: the reference's own network dtype)
                            mask_terminal=True, experience_buffer_size=2**18, learning_rate=2.5e-4,
                            epsilon=lambda ts: max(0.02, 1.0 - ts / 3000.0), target_update_period=200, atom_vmax=10,
