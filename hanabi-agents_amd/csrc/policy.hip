@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void policy_kernel(const T* __restrict__ logit
   const unsigned long long legal_wave = __ballot(on && is_legal);
   const unsigned long long ties_wave = __ballot(on && is_legal && q == best);
   if (on && a == 0) {
-    const unsigned long long mask_a = (1ull << A) - 1ull;
+    const unsigned long long mask_a = ~0ull >> (64 - A);   // A = 64: (1 << A) - 1 would shift by the full width
     const unsigned long long legal_mask = (legal_wave >> (gw * A)) & mask_a;
     const unsigned long long ties = (ties_wave >> (gw * A)) & mask_a;
     const unsigned long long gid = static_cast<unsigned long long>(first_gid + g0 + gw);
