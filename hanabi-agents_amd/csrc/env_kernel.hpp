@@ -417,7 +417,7 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
   const uint4* const ndp = reinterpret_cast<const uint4*>(a.next_deck + gi * NEXT_DECK_BYTES);
   if (active) {
     if (mode == MODE_RESET && a.mask) mask_in = a.mask[gi] != 0;
-    if ((mode == MODE_RESET && mask_in) || (mode == MODE_STEP && (a.flags & 0x100))) {   // (0x100: measurement aid, fetch always)
+    if (mode == MODE_RESET && mask_in) {
       nd[0] = ndp[0]; nd[1] = ndp[1]; nd[2] = ndp[2]; nd[3] = ndp[3];
     }
   }
@@ -485,7 +485,7 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
         int fsum = 0;
 #pragma unroll
         for (int c = 0; c < C; ++c) fsum += fw(c);
-        if (!(a.flags & 0x100) && (((w0 >> 10) & 7) <= 1 || (w0 & 63) == 0 || fsum >= C * R - 1)) {
+        if (((w0 >> 10) & 7) <= 1 || (w0 & 63) == 0 || fsum >= C * R - 1) {
           nd[0] = ndp[0]; nd[1] = ndp[1]; nd[2] = ndp[2]; nd[3] = ndp[3];
         }
       }

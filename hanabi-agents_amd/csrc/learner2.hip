@@ -21,7 +21,6 @@
 #include <hip/hip_fp16.h>
 
 #include <cstdint>
-#include <cstdlib>
 #include <type_traits>
 
 #include "../../include/hanabi_hip.h"
@@ -231,7 +230,6 @@ struct BwdArgs {
   float* db2;             // out [A*K]
   int B, H, A, K, h_ld, w2_ld, dw2_ld;
   int n_dh_tiles;         // workgroups [0, n_dh_tiles): dH tiles of JT hidden units; the rest: (action, 64-unit tile) of dW2
-  int block_offset;       // added to blockIdx.x (0; measurements launch the two halves separately)
 };
 
 constexpr int BWD_T = 1024;  // threads per workgroup of the backward kernel (16 wavefronts)
@@ -242,7 +240,7 @@ __global__ __launch_bounds__(BWD_T) void c51_backward_kernel(const BwdArgs a) {
   __shared__ int wave_cnt[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const T* h = static_cast<const T*>(a.h);
-  const int blk = static_cast<int>(blockIdx.x) + a.block_offset;
+  const int blk = static_cast<int>(blockIdx.x);
   if (blk < a.n_dh_tiles) {
     // ---- dH tile: hidden units j0 .. j0 + JT - 1 for every sample. The JT rows of W2 sit in LDS, every action's K atoms
     // in a slot of its own: 64 elements (k >= K zero, where dl is zero too) + padding to SLOT elements, so that 16-byte reads
@@ -496,11 +494,7 @@ int launch_backward(const BwdArgs& a0, hipStream_t s) {
   int jt = 8;
   while (jt > 1 && jt * row + 16 * jt * 4 > 64 * 1024) jt >>= 1;
   a.n_dh_tiles = (a.H + jt - 1) / jt;
-  unsigned blocks = static_cast<unsigned>(a.n_dh_tiles + a.A * n_jt);
-  if (const char* part = getenv("HB_BWD_PART")) {  // measurement aid: "1" = only the dH tiles, "2" = only the dW2 / db2 tiles
-    if (part[0] == '1') blocks = static_cast<unsigned>(a.n_dh_tiles);
-    if (part[0] == '2') { a.block_offset = a.n_dh_tiles; blocks = static_cast<unsigned>(a.A * n_jt); }
-  }
+  const unsigned blocks = static_cast<unsigned>(a.n_dh_tiles + a.A * n_jt);
   size_t lds = jt * row + 16 * jt * 4;
   if (lds < list_bytes) lds = list_bytes;
   // the dW2 / db2 half: sample list, the staged dl rows of up to B samples, the reduction buffers
@@ -615,7 +609,7 @@ __device__ __forceinline__ tg_f32x4 tg_mfma(const uint4& wv, const uint4& xv, co
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.f, x.f, c, 0, 0, 0);
   }
 }
-template <bool F16, bool PIPE>
+template <bool F16>
 __global__ __launch_bounds__(64) void thin_gemm_kernel(const ThinArgs a, const int batch) {
   // One wavefront per (row tile, column tile); it walks the batch itself, so a launch never has more workgroups than
   // (m / 32) * (n / 16): for the learner's shapes that is 1 024 = one wavefront per SIMD of the chip, which leaves an
@@ -635,34 +629,16 @@ __global__ __launch_bounds__(64) void thin_gemm_kernel(const ThinArgs a, const i
     const unsigned xo = (z * a.x_bs + (blockIdx.x * 32u + lr) * a.ldx + kq * 8u) * 2u;
     const unsigned wo = (z * a.w_bs + (ct * 16u + lr) * a.ldw + kq * 8u) * 2u;
     tg_f32x4 acc0 = tg_f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-    // PIPE (HB_THIN_PIPE=1, measurements only): the operands of K step s + 1 requested before the MFMAs of step s — one wavefront per
-    // SIMD has nobody to hide its load latency behind. 12 more registers (48: the most that fits beside an actor workgroup).
-    // Measured round 3, same box, alternating: the kernel gains 6 % (14.2 vs 15.1 us in the loop) and the STEP loses 15 % (0.128 vs
-    // 0.112 ms): at 48 registers it takes everything an actor workgroup leaves, and the learner's other small kernels (36-47
-    // registers) no longer share a SIMD with it. The plain loop (36 registers) is what runs.
+    // The plain loop (36 registers). Requesting K step s + 1's operands before step s's MFMAs (48 registers) was measured in round 3:
+    // the kernel gained 6 % (14.2 vs 15.1 us) and the STEP lost 15 % (0.128 vs 0.112 ms): at 48 registers it takes everything an actor
+    // workgroup leaves and the learner's other small kernels no longer share a SIMD with it; that form was removed.
     const unsigned kend = static_cast<unsigned>(a.k) * 2u;
-    if constexpr (PIPE) {
-      uint4 x0 = *reinterpret_cast<const uint4*>(a.x + xo), x1 = *reinterpret_cast<const uint4*>(a.x + xo + half);
-      uint4 w0 = *reinterpret_cast<const uint4*>(a.wt + wo);
 #pragma unroll 1
-      for (unsigned kb = 64u; kb < kend; kb += 64u) {
-        const uint4 nx0 = *reinterpret_cast<const uint4*>(a.x + xo + kb), nx1 = *reinterpret_cast<const uint4*>(a.x + xo + kb + half);
-        const uint4 nw0 = *reinterpret_cast<const uint4*>(a.wt + wo + kb);
-        asm volatile("" ::: "memory");   // (the loads are issued here, not sunk below the MFMAs)
-        acc0 = tg_mfma<F16>(w0, x0, acc0);
-        acc1 = tg_mfma<F16>(w0, x1, acc1);
-        x0 = nx0; x1 = nx1; w0 = nw0;
-      }
+    for (unsigned kb = 0; kb < kend; kb += 64u) {
+      const uint4 x0 = *reinterpret_cast<const uint4*>(a.x + xo + kb), x1 = *reinterpret_cast<const uint4*>(a.x + xo + kb + half);
+      const uint4 w0 = *reinterpret_cast<const uint4*>(a.wt + wo + kb);
       acc0 = tg_mfma<F16>(w0, x0, acc0);
       acc1 = tg_mfma<F16>(w0, x1, acc1);
-    } else {
-#pragma unroll 1
-      for (unsigned kb = 0; kb < kend; kb += 64u) {
-        const uint4 x0 = *reinterpret_cast<const uint4*>(a.x + xo + kb), x1 = *reinterpret_cast<const uint4*>(a.x + xo + kb + half);
-        const uint4 w0 = *reinterpret_cast<const uint4*>(a.wt + wo + kb);
-        acc0 = tg_mfma<F16>(w0, x0, acc0);
-        acc1 = tg_mfma<F16>(w0, x1, acc1);
-      }
     }
     // acc_m[j] = out[row 32 bx + 16 m + (lane & 15)][col 16 by + 4 (lane >> 4) + j]
     float v[8] = {acc0[0] + b0, acc0[1] + b1, acc0[2] + b2, acc0[3] + b3, acc1[0] + b0, acc1[1] + b1, acc1[2] + b2, acc1[3] + b3};
@@ -736,18 +712,12 @@ int hb_thin_gemm(const void* x_dev, const void* wt_dev, const void* bias_dev, vo
              static_cast<unsigned>(w_batch_stride), static_cast<unsigned>(out_batch_stride), k, relu, 0u, static_cast<unsigned>(n)};
   // at most 1 024 workgroups (= wavefronts) per launch: one per SIMD of the chip, so that an actor-GEMM workgroup arriving
   // while this kernel runs still finds its registers; wider outputs take several launches
-  const bool pipe = [] { const char* e = getenv("HB_THIN_PIPE"); return e && e[0] == '1'; }();
   const unsigned tiles = static_cast<unsigned>(n / 16), gx = static_cast<unsigned>(m / 32), cap = gx >= 1024u ? 1u : 1024u / gx;
   for (unsigned t0 = 0; t0 < tiles; t0 += cap) {
     a.n_tiles = t0;
     const dim3 grid(gx, tiles - t0 < cap ? tiles - t0 : cap);
-    if (pipe) {
-      if (relu & 4) hipLaunchKernelGGL((thin_gemm_kernel<true, true>), grid, dim3(64), 0, static_cast<hipStream_t>(stream), a, batch);
-      else hipLaunchKernelGGL((thin_gemm_kernel<false, true>), grid, dim3(64), 0, static_cast<hipStream_t>(stream), a, batch);
-    } else {
-      if (relu & 4) hipLaunchKernelGGL((thin_gemm_kernel<true, false>), grid, dim3(64), 0, static_cast<hipStream_t>(stream), a, batch);
-      else hipLaunchKernelGGL((thin_gemm_kernel<false, false>), grid, dim3(64), 0, static_cast<hipStream_t>(stream), a, batch);
-    }
+    if (relu & 4) hipLaunchKernelGGL((thin_gemm_kernel<true>), grid, dim3(64), 0, static_cast<hipStream_t>(stream), a, batch);
+    else hipLaunchKernelGGL((thin_gemm_kernel<false>), grid, dim3(64), 0, static_cast<hipStream_t>(stream), a, batch);
   }
   HB_HIP(hipGetLastError());
   return HB_OK;
@@ -792,7 +762,7 @@ int hb_c51_backward(const float* dl_dev, const int32_t* act_dev, const void* hid
   if (hidden < 1 || hidden_ld < hidden || w2_ld < AK || dw2_ld < AK) return fail(HB_ERR_INVALID, "bad hidden size / row strides");
   if (reinterpret_cast<uintptr_t>(dl_dev) & 15u) return fail(HB_ERR_ALIGN, "dl_dev must be 16-byte aligned");
   BwdArgs a{dl_dev, act_dev, hidden_dev, w2_dev, dh_dev, db1_dev, dw2_dev, db2_dev, static_cast<int>(batch), hidden, n_actions,
-            n_atoms, hidden_ld, w2_ld, dw2_ld, 0, 0};
+            n_atoms, hidden_ld, w2_ld, dw2_ld, 0};
   hipStream_t s = static_cast<hipStream_t>(stream);
   int rc;
   if (dtype == 0) rc = launch_backward<float>(a, s);

@@ -64,8 +64,8 @@ class FusedLearner:
         # "thin" forward (bf16): the two dense layers on hb_thin_gemm, a kernel small enough to run on the CUs WHILE the other
         # seat's actor GEMMs hold them (a library GEMM would wait for those to retire). It reads the weights TRANSPOSED
         # (k-contiguous): copies kept current by one hb_actor_pack_weights launch after every optimizer step / target sync.
-        self.thin = (self.cd in (torch.bfloat16, torch.float16) and os.environ.get("HB_THIN_LEARNER", "1") != "0" and self.Kp % 32 == 0
-                     and H % 64 == 0 and self.Np % 16 == 0 and (2 * B) % 32 == 0)
+        self.thin = (self.cd in (torch.bfloat16, torch.float16) and self.Kp % 32 == 0 and H % 64 == 0 and self.Np % 16 == 0
+                     and (2 * B) % 32 == 0)
         if self.thin:
             self.w1catT = torch.zeros(2 * H, self.Kp, dtype=self.cd, device=dev)
             self.w2stT = torch.zeros(2, self.Np, H, dtype=self.cd, device=dev)
@@ -135,8 +135,8 @@ class FusedLearner:
         if ActorMFMA.supports(self.L, H, self.Kk, self.Kp, self.cd, self.A) and getattr(agent, "use_mfma_actor", True):
             self.actor = ActorMFMA(self.L, H, self.A, self.Kk, self.Kp, dev, n_sets=2 if self.lag else 1, dtype=self.cd)
         # one pack launch per update: hb_actor_fused_pack_thin writes the thin GEMMs' transposed ONLINE weights together with the
-        # one-kernel actor's copies, right behind Adam; part1() then launches no transposer (HB_PACK_THIN=0: two launches as before)
-        self.pack_thin = bool(self.thin and self.actor is not None and self.actor.fused and os.environ.get("HB_PACK_THIN", "1") != "0")
+        # one-kernel actor's copies, right behind Adam; part1() then launches no transposer
+        self.pack_thin = bool(self.thin and self.actor is not None and self.actor.fused)
         if self.lag and (self.actor is None or not agent.params.use_priority or agent.params.resample_noise):
             raise ValueError("actor_lag=1 needs the MFMA actor (bf16 GEMM dtype, one hidden layer of a multiple of 256 units), "
                              "prioritized replay and frozen noise")

@@ -93,8 +93,8 @@ class ActorMFMA:
         self.fuse_select = False
         self._set_ptrs = [tuple(t.data_ptr() for t in st) for st in self.sets]
         # Round 3: the whole forward as ONE kernel (csrc/actor_fused.hip) for bit-packed observations on the reference topology
-        # (hidden 512, 51 atoms): its own fragment-major weight copies per set. HB_ACTOR_FUSED=0 keeps the two-kernel form.
-        self.fused = bool(K.lib().hb_actor_fused_supported(obs_len, hidden, n_actions, n_atoms)) and os.environ.get("HB_ACTOR_FUSED", "1") != "0"
+        # (hidden 512, 51 atoms): its own fragment-major weight copies per set.
+        self.fused = bool(K.lib().hb_actor_fused_supported(obs_len, hidden, n_actions, n_atoms))
         self.fsets = []
         if self.fused:
             b1, b2, nb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
@@ -128,8 +128,7 @@ class ActorMFMA:
     @staticmethod
     def supports(obs_len, hidden, n_atoms, k_pad, dtype, n_actions=1):
         if dtype == torch.float16:   # the one-kernel form only, and only where it also selects the moves
-            return (k_pad % 64 == 0 and n_actions <= 64 and os.environ.get("HB_ACTOR_FUSED", "1") != "0"
-                    and bool(K.lib().hb_actor_fused_supported(obs_len, hidden, n_actions, n_atoms)))
+            return k_pad % 64 == 0 and n_actions <= 64 and bool(K.lib().hb_actor_fused_supported(obs_len, hidden, n_actions, n_atoms))
         return dtype == torch.bfloat16 and k_pad % 64 == 0 and hidden % 256 == 0 and 2 <= n_atoms <= 256
 
     def pack(self, w1, b1, w2, b2, s=0, lazy_two_kernel=False, thin=None):

@@ -23,6 +23,9 @@ import torch
 
 from . import _capi as K
 
+# learner streams a session opens at most (seats beyond that share them round-robin)
+MAX_LEARNER_STREAMS = 2
+
 
 class SelfPlaySession:
     def __init__(self, env, agents, updates_per_step=1, min_replay=None, train_seats=None, overlap_allreduce=None,
@@ -69,7 +72,6 @@ class SelfPlaySession:
         #  only has to finish before that agent acts again, and two 0.14 ms updates on ONE stream outlast two steps)
         self._stream_per_agent = True if stream_per_agent is None else bool(stream_per_agent)
         self._lstreams = {}
-        self.max_learner_streams = int(os.environ.get("HB_MAX_LEARNER_STREAMS", "2"))   # (the variable: measurements)
         if self.learner_stream is not None and split_update:
             for a in agents:
                 if hasattr(a, "set_split_update"):
@@ -92,8 +94,7 @@ class SelfPlaySession:
         # with the weight packs waits for the policy kernel (`acted`). The reference's order of effects is unchanged (insert,
         # act on W_t, update W_t -> W_t+1 from a ring that contains the inserted rows); what changes is that the update's head no
         # longer sits between one policy kernel and the next (0.115 -> see DESIGN section 8).
-        self.early_update = (bool(early_update) and self.native_chain and self.learner_stream is not None
-                             and os.environ.get("HB_EARLY_UPDATE", "1") != "0")   # (the variable: A/B measurements)
+        self.early_update = bool(early_update) and self.native_chain and self.learner_stream is not None
         # One-call steps: the policy kernel with the env step as its tail (hb_actor_fused_act_step) for the games the library
         # compiled it for (Hanabi-Full, 2 and 5 players); HB_FUSED_ENV_STEP=0 keeps two launches (A/B measurements). With it, the
         # early update's optimizer step joins its first graph: `acted` now comes after the env step, and Adam writes nothing the
@@ -106,7 +107,6 @@ class SelfPlaySession:
                 if hasattr(a, "set_two_graphs") and getattr(a, "split_update", False) and not getattr(a, "actor_lag", 0):
                     a.set_two_graphs(True, adam_first=self.fuse_env_step)
         self._inserted_ev = {}
-        self._acted_early = os.environ.get("HB_ACTED_BEFORE_ENV", "1") != "0"
         self.select_in_env_steps = 0   # steps whose moves were picked inside the env kernel (hb_env_step_select_packed)
         self._chains = {}        # seat -> _Chain
         self.native_steps = 0
@@ -252,7 +252,7 @@ class SelfPlaySession:
             agent.add_experience(observations, self.last_actions[seat], env.agent_reward, env.agent_step_type)
         else:
             agent.add_experience_dense(observations, self.last_actions[seat], env.agent_reward, env.agent_step_type)
-        early = self._acted_early and main is not None
+        early = main is not None
 
         def record_acted():
             # The policy has read the weights: the learner may overwrite them from here on. Round 3: recorded BEFORE the env step,
@@ -323,11 +323,11 @@ class SelfPlaySession:
             return self.learner_stream
         ls = self._lstreams.get(id(agent))
         if ls is None:
-            # at most max_learner_streams distinct streams, dealt round-robin in seat order: consecutive seats' updates never
+            # at most MAX_LEARNER_STREAMS distinct streams, dealt round-robin in seat order: consecutive seats' updates never
             # share a stream (what "per agent" is for), and a 5-seat session does not open 5 high-priority streams
             made = list(dict.fromkeys(self._lstreams.values()))
-            if len(made) >= self.max_learner_streams:
-                ls = made[len(self._lstreams) % self.max_learner_streams]
+            if len(made) >= MAX_LEARNER_STREAMS:
+                ls = made[len(self._lstreams) % MAX_LEARNER_STREAMS]
             else:
                 ls = (self.learner_stream if not made else self._stream_factory() if self._stream_factory else
                       torch.cuda.Stream(device=self.env.device, priority=self.learner_stream.priority))
@@ -539,15 +539,11 @@ class _Chain:
             put(K.CMD_RECORD_EVENT, A, [acted.h])
         else:
             put(K.CMD_ACTOR_FUSED_ACT, A, act_ptrs, act_ints, var=1, fvar=0)
-            # `acted` (the policy has read its weights) is recorded BEFORE the env step unless HB_ACTED_BEFORE_ENV=0
-            env_args = [env.h, session._act_buf[seat].data_ptr(), env.obs_bits.data_ptr(), None, env.legal.data_ptr(), env.reward.data_ptr(),
-                        env.terminal.data_ptr(), env.agent_reward.data_ptr(), env.agent_step_type.data_ptr(), env.score.data_ptr()]
-            if session._acted_early:
-                put(K.CMD_RECORD_EVENT, A, [acted.h])
-                put(K.CMD_ENV_STEP_PACKED, A, env_args)
-            else:
-                put(K.CMD_ENV_STEP_PACKED, A, env_args)
-                put(K.CMD_RECORD_EVENT, A, [acted.h])
+            # `acted` (the policy has read its weights) is recorded BEFORE the env step
+            put(K.CMD_RECORD_EVENT, A, [acted.h])
+            put(K.CMD_ENV_STEP_PACKED, A,
+                [env.h, session._act_buf[seat].data_ptr(), env.obs_bits.data_ptr(), None, env.legal.data_ptr(), env.reward.data_ptr(),
+                 env.terminal.data_ptr(), env.agent_reward.data_ptr(), env.agent_step_type.data_ptr(), env.score.data_ptr()])
         # ---- learner stream. Early update: everything that only READS the weights starts as soon as the rows are in the ring —
         # beside this agent's own policy kernel — and only what WRITES them (the optimizer step and the actor's weight copies;
         # actor_lag: only the copies; with the fused env step also only the copies: Adam is in graph 1) waits for `acted`. Otherwise

@@ -21,7 +21,6 @@ w2 = torch.zeros(H, Np, device=dev, dtype=torch.bfloat16); w2[:, :A * NA] = (tor
 b2 = torch.zeros(Np, device=dev, dtype=torch.bfloat16); b2[:A * NA] = (torch.randn(A * NA, device=dev) * 0.5).bfloat16()
 support = torch.linspace(-25, 25, NA, device=dev)
 
-os.environ["HB_ACTOR_FUSED"] = "1"
 act = ops.ActorMFMA(L, H, A, NA, Kp, dev)
 act.fused_min_rows = 0
 assert act.fused, "shape not covered"
