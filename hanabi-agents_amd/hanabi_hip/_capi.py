@@ -87,6 +87,7 @@ class HbRule(C.Structure):
  RULE_PLAY_PROBABLY_SAFE, RULE_DISCARD_PROBABLY_USELESS, RULE_HAIL_MARY, RULE_TELL_ANYONE_USELESS_CARD,
  RULE_TELL_PLAYABLE_CARD, RULE_TELL_MOST_INFORMATION) = range(16)
 MAX_RULES = 16
+TRAIN_MAX_MEMBERS = 64   # HB_TRAIN_MAX_MEMBERS
 
 
 def library_path():
@@ -129,6 +130,7 @@ SIGNATURES = {
     "hb_env_set_color_perms": (C.c_int, [_P, _P, _P]),
     "hb_rule_act": (C.c_int, [_CFG, _P, _I64, _I64, C.POINTER(HbRule), _I32, _U64, _U64, _P, _P, _P]),
     "hb_rule_act_grouped": (C.c_int, [_CFG, _P, _I64, _I64, _I64, _P, _P, _P, _I32, _U64, _U64, _P, _P, _P]),
+    "hb_rule_act_blocks": (C.c_int, [_CFG, _P, _I64, _I64, _I64, _P, _P, _P, _I32, _U64, _U64, _P, _P, _P]),
     "hb_random_legal_actions": (C.c_int, [_P, _I64, _I32, _U64, _U64, _I64, _P, _P]),
     "hb_env_set_games_per_wave": (C.c_int, [_P, _I32]),
     "hb_env_set_async_refill": (C.c_int, [_P, _I32]),
@@ -195,6 +197,9 @@ SIGNATURES = {
     "hb_eval_counters": (C.c_int, [_CFG]),
     "hb_eval_tally": (C.c_int, [_CFG, _I64, _I32, _I32] + [_P] * 8 + [_P]),
     "hb_eval_tally_grouped": (C.c_int, [_CFG, _I64, _I64, _I32, _I32] + [_P] * 8 + [_P]),
+    "hb_train_counters": (C.c_int, [_CFG]),
+    "hb_train_tally_init": (C.c_int, [_CFG, _P, _I64, _P, _P, _P]),
+    "hb_train_tally": (C.c_int, [_CFG, _I64, _I32] + [_P] * 5 + [_I32] + [_P] * 3 + [_P]),
     "hb_relu_bwd_colsum": (C.c_int, [_P, _P, _I64, _I32, _I64, _I64, _P, _P]),
     "hb_replay_insert": (C.c_int, [_P] * 12 + [_I64, _I32, _I32, _I64, _I64, _P]),
 }

@@ -32,6 +32,11 @@ class SelfPlaySession:
                  learner_stream=True, learner_priority=-1, stream_per_agent=None, fuse_select=True, split_update=True,
                  native_chain=True, early_update=True):
         assert len(agents) == env.players, "one agent per seat"
+        self.train_seats = set(range(env.players)) if train_seats is None else set(train_seats)
+        # a partner pool (hanabi_hip.partner_pool) is bound to this env and its seats; it may fill several seats
+        self.pool = check_pool_seats(agents, self.train_seats)
+        if self.pool is not None:
+            self.pool.bind(env, [s for s, a in enumerate(agents) if a is self.pool])
         self._check_color_shuffle(env, agents)
         self.env = env
         self.agents = list(agents)
@@ -41,19 +46,20 @@ class SelfPlaySession:
         self._act_buf = [torch.zeros(env.n, dtype=torch.int32, device=env.device) for _ in agents]
         self.fuse_select = bool(fuse_select) and getattr(env, "packed", False) and env.device.type == "cuda"
         self.min_replay = min_replay
-        self.train_seats = set(range(env.players)) if train_seats is None else set(train_seats)
         if overlap_allreduce is None:  # only worth the reordering when there is a collective to hide
             import torch.distributed as dist
 
             overlap_allreduce = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-        self.overlap_allreduce = bool(overlap_allreduce) and len(set(map(id, agents))) == len(agents)
+        # (the seats of one partner pool count as one occupant: it never trains)
+        solo = [a for a in agents if a is not self.pool] + ([self.pool] if self.pool is not None else [])
+        self.overlap_allreduce = bool(overlap_allreduce) and len(set(map(id, solo))) == len(solo)
         # Learner stream: seat A's update only has to finish before A acts again, so it is enqueued on a second HIP
         # stream right after A's policy forward and runs beside the env step and the NEXT seat's insert / policy /
         # env step (big GEMMs on the main stream, the ~30 small learner kernels on the side). Every dependency of the
         # sequential order is kept by events, so results are identical to running everything on one stream.
         self.learner_stream = None
         self._stream_factory = None
-        if learner_stream and env.device.type == "cuda" and len(set(map(id, agents))) == len(agents) and len(agents) > 1:
+        if learner_stream and env.device.type == "cuda" and len(set(map(id, solo))) == len(solo) and len(agents) > 1:
             # (a torch.cuda.Stream / ExternalStream may be passed in, e.g. one restricted to a CU subset: streams.py)
             # (also accepted: a callable returning a new stream each time it is called — one per agent with per-agent streams)
             self._stream_factory = learner_stream if callable(learner_stream) and not isinstance(learner_stream, torch.cuda.Stream) else None
@@ -124,7 +130,9 @@ class SelfPlaySession:
             m = sum(1 << s for s in range(env.players) if bool(((m >> s) & 1).any()))
         seats = int(m)
         for s, a in enumerate(agents):
-            if (seats >> s) & 1 and not a.requires_vectorized_observation():
+            if hasattr(a, "check_color_shuffle"):   # a partner pool: per row, for its rule members only
+                a.check_color_shuffle(env)
+            elif (seats >> s) & 1 and not a.requires_vectorized_observation():
                 raise ValueError(f"seat {s}: {type(a).__name__} reads the true state and cannot play in a colour-shuffled seat")
 
     def _fused_step_ok(self):
@@ -226,7 +234,10 @@ class SelfPlaySession:
                 self._main, self._main_raw = torch.cuda.current_stream(), raw
             ch = self._chain_for(seat, agent, train, raw)
             if ch is not None:
-                return self._native_step(ch, seat, agent, explore)
+                self._native_step(ch, seat, agent, explore)
+                if self.pool is not None:
+                    self.pool.tally(env, seat, self.last_actions[seat])
+                return
         main = None
         if self.learner_stream is not None:
             raw = K.current_stream().value  # (torch.cuda.current_stream() costs ~8 us of Python: look it up only when it changed)
@@ -292,6 +303,8 @@ class SelfPlaySession:
         self.last_actions[seat] = actions
         if main is not None and acted is None:
             acted = record_acted()
+        if self.pool is not None:
+            self.pool.tally(env, seat, actions)
         self.env_steps += env.n
         if self.learner_stream is None:
             self._train_inline(agent, seat, train)
@@ -390,6 +403,8 @@ class SelfPlaySession:
         fixed set of `n_games` fresh deals keyed by `seed`: an EvalResult. Updates in flight are completed first (flush());
         the session's env, counters, command arrays and agents are left exactly as they were, so training continues as if
         the evaluation had not happened. The evaluator (its env and buffers) is kept for the next call of the same size."""
+        if partners is None and self.pool is not None:
+            raise ValueError("a session with a partner pool is evaluated member by member: use evaluate_pool()")
         self.flush()
         from .evaluate import Evaluator
 
@@ -415,6 +430,30 @@ class SelfPlaySession:
             cp = self._crossplays[key] = CrossPlay(config=self.env.cfg, n_games=n_games, seed=seed, first_game_id=rank * int(n_games),
                                                    device=self.env.device, color_shuffle=color_shuffle)
         return cp.run(pool, teams=teams)
+
+    def evaluate_pool(self, n_games=4096, seed=1, color_shuffle=False):
+        """Greedy evaluation of the session's team with each member of its partner pool in the pool's seats: one EvalResult per
+        member, each equal to Evaluator(...).run(that team). One CrossPlay over explicit teams (kept for the next call); as
+        evaluate(), updates in flight are completed first and the session and its agents are left exactly as they were."""
+        if self.pool is None:
+            raise ValueError("this session has no partner pool: use evaluate()")
+        self.flush()
+        from .crossplay import CrossPlay
+
+        others = []
+        for a in self.agents:
+            if a is not self.pool and not any(a is o for o in others):
+                others.append(a)
+        agents = others + list(self.pool.members)
+        seat_idx = [None if a is self.pool else next(i for i, o in enumerate(others) if a is o) for a in self.agents]
+        teams = [tuple(len(others) + k if i is None else i for i in seat_idx) for k in range(len(self.pool.members))]
+        key = (int(n_games), int(seed), bool(color_shuffle))
+        cp = self._crossplays.get(key)
+        if cp is None:
+            rank = self.env.first_game_id // self.env.n if self.env.n else 0   # (data-parallel: each rank its own deals)
+            cp = self._crossplays[key] = CrossPlay(config=self.env.cfg, n_games=n_games, seed=seed, first_game_id=rank * int(n_games),
+                                                   device=self.env.device, color_shuffle=color_shuffle)
+        return cp.run(agents, teams=teams).results
 
     # ---- checkpoint / resume (SURVEY §8(f)-4) -----------------------------------------------------------------
     def checkpoint_state(self, include_replay=True):
@@ -472,6 +511,29 @@ class SelfPlaySession:
         ep, sc = self.env.stats()
         ep, sc = ep - self._stats0[0], sc - self._stats0[1]
         return sc / ep if ep else float("nan")
+
+
+def check_pool_seats(agents, train_seats):
+    """The session's partner pool (None without one). ValueError: two different pools, a pool in a trained seat, a pool member
+    that is also one of the session's agents."""
+    from .partner_pool import PartnerPool
+
+    pools = []
+    for a in agents:
+        if isinstance(a, PartnerPool) and not any(a is p for p in pools):
+            pools.append(a)
+    if not pools:
+        return None
+    if len(pools) > 1:
+        raise ValueError("at most one partner pool per session (one pool may fill several seats)")
+    pool = pools[0]
+    for s, a in enumerate(agents):
+        if a is pool and s in train_seats:
+            raise ValueError(f"seat {s}: a partner pool's members are frozen; leave its seats out of train_seats")
+    for k, m in enumerate(pool.members):
+        if any(m is a for a in agents):
+            raise ValueError(f"pool member {k} is also one of the session's agents: pool members are frozen partners")
+    return pool
 
 
 class _Chain:

@@ -253,6 +253,13 @@ int hb_rule_act_grouped(const hb_config* cfg, const uint32_t* state_rows_dev, in
                         int64_t first_game_id, const int32_t* set_of_block_dev, const hb_rule* rules_dev,
                         const int32_t* n_rules_dev, int32_t n_sets, uint64_t seed, uint64_t draw, int32_t* actions_dev,
                         int32_t* fired_dev, void* stream);
+/* hb_rule_act_grouped for blocks of DISTINCT games (training against a partner pool, hanabi_hip.partner_pool): the same layout
+ * and tables, but row r of block b is keyed by its global game id first_game_id + b * block_rows + r. Each block's actions and
+ * fired indices are bit for bit those of hb_rule_act on that block's rows with first_game_id + b * block_rows.            */
+int hb_rule_act_blocks(const hb_config* cfg, const uint32_t* state_rows_dev, int64_t n_blocks, int64_t block_rows,
+                       int64_t first_game_id, const int32_t* set_of_block_dev, const hb_rule* rules_dev,
+                       const int32_t* n_rules_dev, int32_t n_sets, uint64_t seed, uint64_t draw, int32_t* actions_dev,
+                       int32_t* fired_dev, void* stream);
 
 /* Tuning knob for measurements: games handled per 64-lane wavefront (8, 16, 32 or 64); 0 (the default) picks 16,
  * or 32 for a packed-only step over >= 32768 games. The results do not depend on it.  */
@@ -719,6 +726,34 @@ int hb_eval_tally(const hb_config* cfg, int64_t n_games, int32_t seat, int32_t t
 int hb_eval_tally_grouped(const hb_config* cfg, int64_t n_blocks, int64_t block_games, int32_t seat, int32_t turn,
                           const int32_t* actions_dev, const float* reward_dev, const int8_t* terminal_dev, const int8_t* score_dev,
                           uint8_t* done_dev, int8_t* final_score_dev, int16_t* length_dev, int64_t* counters_dev, void* stream);
+
+/* ---- training statistics against a partner pool (csrc/train_tally.hip) ----------------------------------------------------
+ * A training env (auto-reset, lock-step) whose rows are cut into 128-game tiles, each tile owned by one member of a partner pool
+ * (hanabi_hip.partner_pool). hb_train_tally is issued once per env step, after the step, on the same stream, and adds what that
+ * step did to the counter row of the member owning each game's tile:
+ *   actions_dev [n] int32 the moves just stepped (seat `seat` acted); reward_dev [n] f32, terminal_dev [n] int8, score_dev [n]
+ *                         int8: that step's outputs
+ *   tile_member_dev [n / 128] int32: the member of each tile (-1 or >= n_members: not counted); n must be a multiple of 128
+ *   lost_dev [n] uint8 / length_dev [n] int16: per-game tally state, set by hb_train_tally_init. Bit 7 of lost = the game's deal
+ *                         was not seen (its length and lives are unknown); bits 0-6 = lives lost. Both restart at each terminal:
+ *                         every game is tracked from its next deal on.
+ *   counters_dev [n_members][hb_train_counters(cfg)] int64, zeroed by the caller:
+ *     [0] episodes ended, [1] sum of their scores, [2] sum of their squared scores (score 0 after a bomb-out, as score_dev and
+ *     the env's own statistics report it), [3 .. 3 + B) score histogram (B = colors * ranks + 1),
+ *     [3 + B] bomb-outs, [4 + B] sum of lengths, [5 + B] episodes counted in those two (deal seen),
+ *     [6 + B + 4 * p + k] moves of seat p of kind k (App. A.2 order), [6 + B + 4 * P + p] misplays of seat p (a play whose reward
+ *     is <= 0). Bomb-out and misplay rules are those of hb_eval_tally.
+ * Reduced per wavefront (ballots) and per workgroup (LDS); each counter takes at most one global atomic per workgroup, from
+ * <= 128 workgroups. Without a device: HB_ERR_NO_DEVICE (arguments are checked first).
+ * hb_train_tally_init arms game g (lost = 0, length = 0) when its state row is at the first move of a deal (every information
+ * token, no firework, no discard, the deck less the hands: every game of a fresh or reset env), else leaves it unarmed.   */
+#define HB_TRAIN_MAX_MEMBERS 64
+int hb_train_counters(const hb_config* cfg); /* 6 + colors * ranks + 1 + 5 * players */
+int hb_train_tally_init(const hb_config* cfg, const uint32_t* state_rows_dev, int64_t n_games, uint8_t* lost_dev, int16_t* length_dev,
+                        void* stream);
+int hb_train_tally(const hb_config* cfg, int64_t n_games, int32_t seat, const int32_t* actions_dev, const float* reward_dev,
+                   const int8_t* terminal_dev, const int8_t* score_dev, const int32_t* tile_member_dev, int32_t n_members,
+                   uint8_t* lost_dev, int16_t* length_dev, int64_t* counters_dev, void* stream);
 
 /* ---- One host call per step: hb_chain_run (csrc/chain.hip, round 3) ------------------------------------------------------
  * The session that drives DQNAgent (rlax_rainbow.py:277-339: explore / add_experience / update once per env step) issues ~25
