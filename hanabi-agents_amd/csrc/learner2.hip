@@ -659,6 +659,150 @@ __global__ __launch_bounds__(64) void thin_gemm_kernel(const ThinArgs a, const i
   }
 }
 
+// ---- the learner's forward pass on the thin GEMM's arithmetic, restricted to what the C51 loss and the backward read --------
+// hb_thin_gemm computes every element of [2B, 2H] (layer 1) and [2, 2B, Np] (layer 2). Nobody reads the target network on
+// obs_tm1 (rows [0, B): a quarter of layer 1, a quarter of layer 2), and of the online logits on obs_tm1 the loss reads only
+// the K atoms of the action each sample took. Here a launch is a flat list of UNITS dealt to at most 1 024 one-wavefront
+// workgroups (a wavefront walks ceil(units / 1 024) of them): a unit is thin_gemm_kernel's 32 x 16 output tile of ONE product,
+// either of a dense region or, for the online logits on obs_tm1, GATHERED: (action a, up to 32 of the samples that took a in
+// ascending order, one of the 16-column tiles that cover a's K columns). Every output element is the same chain of
+// v_mfma_f32_16x16x32 accumulations over its own row and column in ascending k as in thin_gemm_kernel, the same bias add, ReLU
+// and rounding: bit-identical to hb_thin_gemm wherever it writes. 2 players, B = 256: layer 1 768 units (was 1 024), layer 2
+// 1 024 dense + at most 140 gathered units of 16 K steps (was 1 024 wavefronts of 32 K steps).
+struct FwdArgs {
+  const unsigned char* x;      // [batch][2B][ldx]
+  const unsigned char* wt;     // [batch][n][ldw]
+  const __hip_bfloat16* bias;  // [batch][nb] or NULL
+  void* out;                   // [batch][2B][ldo]
+  const int32_t* act;          // [B]: the action of each sample (gathered units), or NULL
+  unsigned ldx, ldw, ldo, x_bs, w_bs, o_bs, nb;
+  int k, relu;                 // relu: the flags of hb_thin_gemm
+  unsigned n_gather;           // units [0, n_gather): (row group g, column tile p) = (u / npair, u % npair) of the gathered part
+  unsigned npair;              // 16-column tiles that cover one action's atoms at any alignment
+  unsigned n_units, stride;    // all units; workgroups of the launch
+  unsigned nrt;                // 32-row tiles per dense region (B / 32)
+  unsigned reg0_units;         // dense units of region 0 (nrt * its column tiles); the rest belong to region 1
+  unsigned z[2], row0[2];      // batch entry and first row of the two dense regions
+  int B, A, K;
+};
+
+// epilogue of one 16-column tile (columns c0 + 4 (lane >> 4) ..) for the two row tiles: bias, ReLU, rounding and stores of
+// thin_gemm_kernel; o0 / o1: element offsets of the lane's two rows at the tile's column 0, st0 / st1: whether they are stored
+template <bool F16>
+__device__ __forceinline__ void tf_store(void* out, int relu, const __hip_bfloat16* bz, unsigned c0, size_t o0, size_t o1, bool st0,
+                                         bool st1, const tg_f32x4& am0, const tg_f32x4& am1) {
+  float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
+  if (bz) { b0 = tg_bias<F16>(bz, c0); b1 = tg_bias<F16>(bz, c0 + 1); b2 = tg_bias<F16>(bz, c0 + 2); b3 = tg_bias<F16>(bz, c0 + 3); }
+  float v[8] = {am0[0] + b0, am0[1] + b1, am0[2] + b2, am0[3] + b3, am1[0] + b0, am1[1] + b1, am1[2] + b2, am1[3] + b3};
+  if (relu & 1) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = fmaxf(v[i], 0.f);
+  }
+  if (relu & 2) {   // fp32 output: the accumulators + bias as they are
+    float* o = static_cast<float*>(out) + c0;
+    if (st0) *reinterpret_cast<float4*>(o + o0) = make_float4(v[0], v[1], v[2], v[3]);
+    if (st1) *reinterpret_cast<float4*>(o + o1) = make_float4(v[4], v[5], v[6], v[7]);
+  } else {
+    __hip_bfloat16* o = static_cast<__hip_bfloat16*>(out) + c0;
+    if (st0) *reinterpret_cast<uint2*>(o + o0) = make_uint2(tg_pack<F16>(v[0], v[1]), tg_pack<F16>(v[2], v[3]));
+    if (st1) *reinterpret_cast<uint2*>(o + o1) = make_uint2(tg_pack<F16>(v[4], v[5]), tg_pack<F16>(v[6], v[7]));
+  }
+}
+
+template <bool F16>
+__global__ __launch_bounds__(64) void thin_forward_kernel(const FwdArgs a) {
+  __shared__ int rows[32];     // a gathered unit's samples (128 B: inside one LDS granule)
+#pragma unroll 1
+  for (unsigned u = blockIdx.x; u < a.n_units; u += a.stride) {
+    // (the lane index is made opaque per unit: otherwise every value derived from it is kept in a register of its own across
+    // the walk, which costs a dozen registers for a loop that almost always runs once)
+    int lane = threadIdx.x;
+    asm volatile("" : "+v"(lane));
+    const unsigned lr = lane & 15, kq = lane >> 4;
+    unsigned z, r0, r1, t0;   // batch entry; this lane's row of the two row tiles; the column tile
+    bool v0 = true, v1 = true;   // the lane's rows are real: stored
+    if (u < a.n_gather) {
+      const unsigned g = u / a.npair, p = u - g * a.npair;
+      int av[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) av[i] = lane + 64 * i < a.B ? a.act[lane + 64 * i] : -1;
+      // the row groups in (action, 32 samples at a time) order: find the g-th one
+      int act_id = -1, cnt = 0;
+      unsigned first = 0;
+      for (int c = 0; c < a.A; ++c) {
+        int n = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) n += __popcll(__ballot(av[i] == c));
+        const unsigned ng = static_cast<unsigned>(n + 31) >> 5;
+        if (g < first + ng) { act_id = c; cnt = n; break; }
+        first += ng;
+      }
+      if (act_id < 0) continue;   // fewer row groups than the launch provides for
+      const unsigned tf = static_cast<unsigned>(act_id * a.K) >> 4, tl = static_cast<unsigned>(act_id * a.K + a.K - 1) >> 4;
+      t0 = tf + p;
+      if (t0 > tl) continue;
+      const unsigned j = g - first;   // samples of rank [32 j, 32 j + 32) among those that took act_id
+      wave_fence();                   // (a walking wavefront: the previous unit's reads of `rows` are done)
+      int base = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool mine = av[i] == act_id;
+        const unsigned long long mk = __ballot(mine);
+        const int rank = base + __popcll(mk & ((1ull << lane) - 1ull));
+        if (mine && static_cast<unsigned>(rank >> 5) == j) rows[rank & 31] = lane + 64 * i;
+        base += __popcll(mk);
+      }
+      wave_fence();
+      const unsigned nr = static_cast<unsigned>(cnt) - 32u * j;   // >= 1; rows of this unit: min(nr, 32)
+      v0 = lr < nr;
+      v1 = lr + 16u < nr;
+      r0 = static_cast<unsigned>(rows[v0 ? lr : 0u]);
+      r1 = static_cast<unsigned>(rows[v1 ? lr + 16u : 0u]);
+      z = 0u;
+    } else {
+      unsigned d = u - a.n_gather;
+      const unsigned reg = d < a.reg0_units ? 0u : 1u;
+      if (reg) d -= a.reg0_units;
+      const unsigned ct = d / a.nrt, rt = d - ct * a.nrt;
+      z = a.z[reg];
+      r0 = a.row0[reg] + 32u * rt + lr;
+      r1 = r0 + 16u;
+      t0 = ct;
+    }
+    const unsigned xo0 = (z * a.x_bs + r0 * a.ldx + kq * 8u) * 2u, xo1 = (z * a.x_bs + r1 * a.ldx + kq * 8u) * 2u;
+    const unsigned wo0 = (z * a.w_bs + (t0 * 16u + lr) * a.ldw + kq * 8u) * 2u;
+    tg_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};   // one per row tile
+    const unsigned kend = static_cast<unsigned>(a.k) * 2u;
+    // Two K steps per round trip to memory: the six loads of steps s and s + 1 are requested together, the MFMAs follow in
+    // ascending k (the chain of thin_gemm_kernel). 40 + 8 registers: the allocation thin_gemm_kernel has (36 + 8 -> 48); a
+    // 32 x 32 unit (four accumulators) needs 51 - 60 and is outside what a policy workgroup leaves.
+    unsigned kb = 0;
+#pragma unroll 1
+    for (; kb + 64u < kend; kb += 128u) {
+      const uint4 x0 = *reinterpret_cast<const uint4*>(a.x + (xo0 + kb)), x1 = *reinterpret_cast<const uint4*>(a.x + (xo1 + kb));
+      const uint4 w0 = *reinterpret_cast<const uint4*>(a.wt + (wo0 + kb));
+      const uint4 y0 = *reinterpret_cast<const uint4*>(a.x + (xo0 + kb + 64u)), y1 = *reinterpret_cast<const uint4*>(a.x + (xo1 + kb + 64u));
+      const uint4 u0 = *reinterpret_cast<const uint4*>(a.wt + (wo0 + kb + 64u));
+      __builtin_amdgcn_sched_barrier(0);   // (else the compiler defers two of the loads behind the first MFMAs to save registers)
+      acc0 = tg_mfma<F16>(w0, x0, acc0);
+      acc1 = tg_mfma<F16>(w0, x1, acc1);
+      acc0 = tg_mfma<F16>(u0, y0, acc0);
+      acc1 = tg_mfma<F16>(u0, y1, acc1);
+    }
+    if (kb < kend) {   // an odd number of K steps: the last one
+      const uint4 x0 = *reinterpret_cast<const uint4*>(a.x + (xo0 + kb)), x1 = *reinterpret_cast<const uint4*>(a.x + (xo1 + kb));
+      const uint4 w0 = *reinterpret_cast<const uint4*>(a.wt + (wo0 + kb));
+      acc0 = tg_mfma<F16>(w0, x0, acc0);
+      acc1 = tg_mfma<F16>(w0, x1, acc1);
+    }
+    // acc<m>[j] = out[row r<m>][col 16 t0 + 4 (lane >> 4) + j]
+    const size_t ob = z * static_cast<size_t>(a.o_bs) + 4u * kq;
+    const size_t o0 = ob + static_cast<size_t>(r0) * a.ldo, o1 = ob + static_cast<size_t>(r1) * a.ldo;
+    const __hip_bfloat16* bz = a.bias ? a.bias + static_cast<size_t>(z) * a.nb + 4u * kq : nullptr;
+    tf_store<F16>(a.out, a.relu, bz, t0 * 16u, o0, o1, v0, v1, acc0, acc1);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -719,6 +863,71 @@ int hb_thin_gemm(const void* x_dev, const void* wt_dev, const void* bias_dev, vo
     if (relu & 4) hipLaunchKernelGGL((thin_gemm_kernel<true>), grid, dim3(64), 0, static_cast<hipStream_t>(stream), a, batch);
     else hipLaunchKernelGGL((thin_gemm_kernel<false>), grid, dim3(64), 0, static_cast<hipStream_t>(stream), a, batch);
   }
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+int hb_thin_forward(int32_t layer, const void* x_dev, const void* wt_dev, const void* bias_dev, void* out_dev, const int32_t* act_dev,
+                    int64_t batch, int32_t n, int32_t k, int32_t ldx, int32_t ldw, int32_t ldo, int64_t x_batch_stride,
+                    int64_t w_batch_stride, int64_t out_batch_stride, int32_t n_actions, int32_t n_atoms, int32_t relu, void* stream) {
+  if (!x_dev || !wt_dev || !out_dev) return fail(HB_ERR_INVALID, "null argument");
+  if (layer != 1 && layer != 2) return fail(HB_ERR_INVALID, "layer must be 1 or 2");
+  if (batch <= 0 || n <= 0) return HB_OK;
+  const int64_t m = 2 * batch;
+  const int nz = layer == 2 ? 2 : 1;
+  if (batch % 32 || n % (layer == 1 ? 32 : 16) || k % 32 || k < 32)
+    return fail(HB_ERR_INVALID, "need batch % 32 == 0, n % 16 == 0 (layer 1: n % 32 == 0), k % 32 == 0");
+  if (ldx < k || ldw < k || ldo < n || ldx % 8 || ldw % 8 || ldo % 4) return fail(HB_ERR_INVALID, "bad leading dimensions");
+  if (relu < 0 || relu > 7) return fail(HB_ERR_INVALID, "relu: bit 0 = ReLU, bit 1 = fp32 output, bit 2 = fp16 (not bf16) operands");
+  if ((reinterpret_cast<uintptr_t>(x_dev) & 15u) || (reinterpret_cast<uintptr_t>(wt_dev) & 15u) ||
+      (reinterpret_cast<uintptr_t>(out_dev) & ((relu & 2) ? 15u : 7u)))
+    return fail(HB_ERR_ALIGN, "x / wt must be 16-byte aligned, out 8-byte (fp32 output: 16-byte) aligned");
+  if (layer == 2) {
+    if (!act_dev) return fail(HB_ERR_INVALID, "null argument");
+    if (batch > 256) return fail(HB_ERR_INVALID, "batch must be <= 256 (a wavefront keeps the batch's actions in four registers per lane)");
+    if (n_actions < 1 || n_actions > 64 || n_atoms < 1 || n_atoms > 64 || n_actions * n_atoms > n)
+      return fail(HB_ERR_INVALID, "need n_actions <= 64, n_atoms <= 64, n_actions * n_atoms <= n");
+    if (x_batch_stride < 0 || w_batch_stride < 0 || out_batch_stride < 0) return fail(HB_ERR_INVALID, "negative batch stride");
+    if (x_batch_stride % 8 || w_batch_stride % 8 || out_batch_stride % 4) return fail(HB_ERR_INVALID, "batch strides must keep the alignment");
+  }
+  const int64_t xe = (nz - 1) * x_batch_stride + m * static_cast<int64_t>(ldx), we = (nz - 1) * w_batch_stride + n * static_cast<int64_t>(ldw);
+  if (xe >= (1LL << 30) || we >= (1LL << 30)) return fail(HB_ERR_INVALID, "operands beyond the kernel's 32-bit offsets");
+  FwdArgs a{};
+  a.x = static_cast<const unsigned char*>(x_dev);
+  a.wt = static_cast<const unsigned char*>(wt_dev);
+  a.bias = static_cast<const __hip_bfloat16*>(bias_dev);
+  a.out = out_dev;
+  a.act = act_dev;
+  a.ldx = static_cast<unsigned>(ldx); a.ldw = static_cast<unsigned>(ldw); a.ldo = static_cast<unsigned>(ldo);
+  a.nb = static_cast<unsigned>(n);
+  a.k = k; a.relu = relu;
+  a.B = static_cast<int>(batch);
+  a.nrt = static_cast<unsigned>(batch / 32);
+  const unsigned ncp = static_cast<unsigned>(n / 16);   // 16-column tiles
+  if (layer == 1) {
+    // rows [0, B) (obs_tm1): the online half of the columns only; rows [B, 2B) (obs_t): online and target
+    a.npair = 1u;
+    a.z[0] = a.z[1] = 0u;
+    a.row0[0] = 0u; a.row0[1] = static_cast<unsigned>(batch);
+    a.reg0_units = a.nrt * (ncp / 2u);
+    a.n_units = a.reg0_units + a.nrt * ncp;
+  } else {
+    // online and target on rows [B, 2B) dense; online on rows [0, B): the atoms of the action taken, gathered by action
+    a.x_bs = static_cast<unsigned>(x_batch_stride); a.w_bs = static_cast<unsigned>(w_batch_stride); a.o_bs = static_cast<unsigned>(out_batch_stride);
+    a.A = n_actions; a.K = n_atoms;
+    a.npair = static_cast<unsigned>((n_atoms + 14) / 16 + 1);   // n_atoms columns touch at most this many 16-column tiles
+    const unsigned groups = a.nrt + static_cast<unsigned>(n_actions < batch ? n_actions : batch);   // >= sum over actions of ceil(count / 32)
+    a.n_gather = groups * a.npair;
+    a.z[0] = 0u; a.z[1] = 1u;
+    a.row0[0] = a.row0[1] = static_cast<unsigned>(batch);
+    a.reg0_units = a.nrt * ncp;
+    a.n_units = a.n_gather + 2u * a.reg0_units;
+  }
+  // at most 1 024 workgroups (= wavefronts), as hb_thin_gemm: beyond that every wavefront walks ceil(units / 1 024) units
+  const unsigned per = (a.n_units + 1023u) / 1024u;
+  a.stride = (a.n_units + per - 1u) / per;
+  if (relu & 4) hipLaunchKernelGGL((thin_forward_kernel<true>), dim3(a.stride), dim3(64), 0, static_cast<hipStream_t>(stream), a);
+  else hipLaunchKernelGGL((thin_forward_kernel<false>), dim3(a.stride), dim3(64), 0, static_cast<hipStream_t>(stream), a);
   HB_HIP(hipGetLastError());
   return HB_OK;
 }

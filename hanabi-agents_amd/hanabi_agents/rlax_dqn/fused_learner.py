@@ -73,6 +73,9 @@ class FusedLearner:
             self._logits = torch.zeros(2, 2 * B, self.Np, **f32)   # fp32: the accumulators + bias as they are (round 3; bf16 before)
             self._bias_sink = torch.zeros(max(2 * H, self.Np), **f32)   # (the transposer also converts a bias: unused here)
             self._t_jobs = [None, None]
+        # hb_thin_forward instead of the two hb_thin_gemm calls (its shape limits; the dense cross-check chain reads dense logits)
+        self.trimmed = bool(self.thin and B % 32 == 0 and B <= 256 and self.Np % 32 == 0 and self.A <= 64 and self.Kk <= 64)
+        self._dense_forward = False    # tests only: the two dense hb_thin_gemm calls, to compare the trimmed forward against
         # flat gradient buffer [dW1 | db1 | dW2 | db2] (fp32), one all-reduce bucket
         sizes = [layers[0].w.numel(), H, layers[1].w.numel(), AK]
         self.flat_grad = torch.zeros(sum(sizes), **f32)
@@ -290,10 +293,18 @@ class FusedLearner:
             if not (self.adam_pack or self.pack_thin):   # (else the pack behind Adam keeps the online half current)
                 self._transpose(0)
             f16 = 4 if self.cd == torch.float16 else 0   # (hb_thin_gemm: bit 2 of its flags = fp16 operands)
-            K.check(L.hb_thin_gemm(K.dptr(self.x), K.dptr(self.w1catT), K.dptr(self.b1cat), K.dptr(hcat), 2 * B, 2 * H, self.Kp,
-                                   self.Kp, self.Kp, 2 * H, 1, 0, 0, 0, 1 | f16, s))                 # bias + ReLU, [2B, 2H]
-            K.check(L.hb_thin_gemm(K.dptr(hcat), K.dptr(self.w2stT), K.dptr(self.b2st), K.dptr(logits), 2 * B, self.Np, H, 2 * H, H,
-                                   self.Np, 2, H, self.Np * H, 2 * B * self.Np, 2 | f16, s))         # {online, target}: [2, 2B, Np] fp32, biases added
+            if self.trimmed and self.sparse_backward and not self._dense_forward:
+                # only what the loss and the backward read (hb_thin_forward): not the target net on obs_tm1, and of the online
+                # logits on obs_tm1 the atoms of the action taken; the rest of hcat / logits keeps its zeros
+                K.check(L.hb_thin_forward(1, K.dptr(self.x), K.dptr(self.w1catT), K.dptr(self.b1cat), K.dptr(hcat), None, B, 2 * H,
+                                          self.Kp, self.Kp, self.Kp, 2 * H, 0, 0, 0, 0, 0, 1 | f16, s))
+                K.check(L.hb_thin_forward(2, K.dptr(hcat), K.dptr(self.w2stT), K.dptr(self.b2st), K.dptr(logits), K.dptr(self.act), B,
+                                          self.Np, H, 2 * H, H, self.Np, H, self.Np * H, 2 * B * self.Np, self.A, self.Kk, 2 | f16, s))
+            else:
+                K.check(L.hb_thin_gemm(K.dptr(self.x), K.dptr(self.w1catT), K.dptr(self.b1cat), K.dptr(hcat), 2 * B, 2 * H, self.Kp,
+                                       self.Kp, self.Kp, 2 * H, 1, 0, 0, 0, 1 | f16, s))                 # bias + ReLU, [2B, 2H]
+                K.check(L.hb_thin_gemm(K.dptr(hcat), K.dptr(self.w2stT), K.dptr(self.b2st), K.dptr(logits), 2 * B, self.Np, H, 2 * H, H,
+                                       self.Np, 2, H, self.Np * H, 2 * B * self.Np, 2 | f16, s))         # {online, target}: [2, 2B, Np] fp32, biases added
         else:
             hcat = torch._addmm_activation(self.b1cat, self.x, self.w1cat, use_gelu=False)   # bias + ReLU in the epilogue, [2B, 2H]
             logits = torch.bmm(hcat.view(2 * B, 2, H).transpose(0, 1), self.w2st)            # [2, 2B, Np], strided A operand: no copy

@@ -483,6 +483,23 @@ int hb_thin_gemm(const void* x_dev, const void* wt_dev, const void* bias_dev, vo
                  int32_t ldx, int32_t ldw, int32_t ldo, int32_t batch, int64_t x_batch_stride, int64_t w_batch_stride,
                  int64_t out_batch_stride, int32_t relu, void* stream);
 
+/* hb_thin_forward: the two hb_thin_gemm products of the C51 learner's forward pass, restricted to the elements the loss
+ * (hb_c51_loss_sparse) and the backward (hb_c51_backward) read, on the same per-element arithmetic: every element it writes is
+ * bit-identical to hb_thin_gemm's; the others are not touched. The 2 * batch operand rows are {obs_tm1 [0, batch), obs_t
+ * [batch, 2 batch)}. Operands, strides, alignment and the relu flags are hb_thin_gemm's (m = 2 * batch).
+ *   layer 1: hb_thin_gemm(m, n, k, batch entries 1) with wt = [online | target] rows (n = 2 * hidden): everything except rows
+ *            [0, batch) x columns [n / 2, n) (the target network on obs_tm1, which nobody reads); act_dev and the batch strides unused
+ *   layer 2: hb_thin_gemm(m, n, k, batch entries 2 = {online, target}): entry 0 and entry 1 on rows [batch, 2 batch) in full,
+ *            entry 1 on rows [0, batch) not at all, and of entry 0 on rows [0, batch) the 16-column tiles that hold the n_atoms
+ *            columns [act[b] * n_atoms, (act[b] + 1) * n_atoms) of each sample b (grouped by action inside the kernel; act_dev
+ *            int32 [batch]; values outside [0, n_actions) select nothing). batch <= 256, n_actions, n_atoms <= 64
+ * batch % 32 == 0, n % 32 == 0 (layer 1: n % 64 == 0), k % 32 == 0. One wavefront per workgroup, at most 1 024 workgroups,
+ * 128 B of LDS: it runs beside the policy kernel like hb_thin_gemm, with 384 (layer 1) / <= 596 (layer 2) wavefronts at the
+ * 2-player shape instead of 1 024, each with the K steps of one product.                                                      */
+int hb_thin_forward(int32_t layer, const void* x_dev, const void* wt_dev, const void* bias_dev, void* out_dev, const int32_t* act_dev,
+                    int64_t batch, int32_t n, int32_t k, int32_t ldx, int32_t ldw, int32_t ldo, int64_t x_batch_stride,
+                    int64_t w_batch_stride, int64_t out_batch_stride, int32_t n_actions, int32_t n_atoms, int32_t relu, void* stream);
+
 /* hb_dqn_loss_sparse: the scalar double-Q loss of the older agent (hanabi_agents/rlax_dqn/rlax_dqn.py:170-205: td = r + g * (1 -
  * terminal) * q_target(s')[argmax q_online(s')] - q_online(s)[a], loss = mean(w_IS * 0.5 * td^2)) on precomputed q values, in the
  * same compact-gradient form as hb_c51_loss_sparse: q_online_dev [2B, row_stride] (rows 0..B-1: obs_tm1, B..2B-1: obs_t),
