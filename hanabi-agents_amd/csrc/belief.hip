@@ -1,0 +1,238 @@
+// belief.hip — fictitious states drawn from a public-knowledge belief, and the reduction of the rollouts played from them
+// (hanabi_hip/search.py).
+//
+// hb_belief_determinize: output row o = source row o / replicas with the observing seat's own hand and the undealt deck re-drawn
+// from what that seat cannot see (the "pool": its hand's cards, oldest first, then the undealt deck positions ascending; at most
+// 5 + 50 - 2 * 5 = 45 elements, one per lane). ONE wavefront per output row, everything in registers: lane j < SW holds word j of
+// the row, lane l < npool holds pool element l; scalars travel by v_readlane, the hand slots are drawn with one ballot each
+// (sequential importance sampling: the weight is the product of the candidate counts), the rest of the pool is shuffled onto the
+// undealt deck positions by ranking distinct random keys (refill_kernel's shuffle, env_kernel.hpp). Waves share nothing: no LDS,
+// no barrier.
+//
+// hb_search_reduce: per root, sum of weight * score and of weight over the replicas of every action in 64-bit integers (the
+// result does not depend on the order of summation), one division per (root, action), and the arg-max over the legal actions.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "../../include/hanabi_hip.h"
+#include "common.hpp"
+#include "env_kernel.hpp"  // hb::philox4x32_10
+
+namespace {
+
+struct DetArgs {
+  const uint32_t* src;
+  uint32_t* out;
+  uint32_t* weight;
+  long long n_out, first_row;
+  unsigned long long seed, draw;
+  int replicas, seat, P, C, R, H, D, SW;
+};
+
+__device__ __forceinline__ uint32_t lane_read(uint32_t v, int l) {
+  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), l));
+}
+
+__global__ void __launch_bounds__(256) belief_determinize_kernel(DetArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long long o = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);   // output row of this wavefront
+  if (o >= a.n_out) return;
+  const long long i = o / a.replicas;
+  const uint32_t wj = lane < a.SW ? a.src[i * a.SW + lane] : 0u;
+  uint32_t* const dst = a.out + o * a.SW;
+  const uint32_t w0 = lane_read(wj, 0), w1 = lane_read(wj, 1);
+  const int seat = a.seat < 0 ? static_cast<int>((w0 >> 13) & 7u) : a.seat;
+  if (((w0 >> 19) & 3u) != 0 || seat >= a.P) {   // not running (or no such seat): an unchanged copy that weighs nothing
+    if (lane < a.SW) dst[lane] = wj;
+    if (lane == 0) a.weight[o] = 0u;
+    return;
+  }
+  const int W_DECK = 10 + 3 * a.P;
+  const uint32_t hand = lane_read(wj, 10 + seat);
+  const uint64_t know = (static_cast<uint64_t>(lane_read(wj, 10 + a.P + 2 * seat + 1)) << 32) | lane_read(wj, 10 + a.P + 2 * seat);
+  const int n_hand = min(static_cast<int>((w1 >> (15 + 3 * seat)) & 7u), a.H);
+  const int deck_size = min(static_cast<int>(w0 & 63u), a.D);
+  const int deck_pos = a.D - deck_size;
+  const int npool = n_hand + deck_size;
+
+  // pool element of this lane: a hand slot, or the deck byte at position q (fetched from the lane that holds its word)
+  const int q = deck_pos + lane - n_hand;
+  const uint32_t wq = static_cast<uint32_t>(__shfl(static_cast<int>(wj), (W_DECK + (q >> 2)) & 63));
+  const uint32_t card = lane < n_hand ? (hand >> (5 * lane)) & 31u : (wq >> (8 * (q & 3))) & 255u;
+  const bool in_pool = lane < npool;
+  const uint32_t col = card / static_cast<uint32_t>(a.R), rk = card - col * static_cast<uint32_t>(a.R);
+  const bool card_ok = in_pool && col < static_cast<uint32_t>(a.C);
+
+  const unsigned long long row_id = static_cast<unsigned long long>(a.first_row + o);
+  uint32_t rnd[4];
+  hb::philox4x32_10(128u + static_cast<uint32_t>(lane), static_cast<uint32_t>(a.draw), static_cast<uint32_t>(row_id),
+                    static_cast<uint32_t>(row_id >> 32), static_cast<uint32_t>(a.seed),
+                    static_cast<uint32_t>(a.seed >> 32) ^ static_cast<uint32_t>(a.draw >> 32), rnd);
+
+  // ---- the hand, slot by slot: ballot of the free plausible pool elements, take the k-th -------------------------------------
+  unsigned long long taken = 0;
+  uint32_t weight = 1u, new_hand = hand;
+  bool dead = false;
+  for (int s = 0; s < n_hand; ++s) {
+    const uint32_t kn = static_cast<uint32_t>(know >> (12 * s)) & 0xFFFu;
+    const bool cand = card_ok && !((taken >> lane) & 1ull) && ((kn >> col) & 1u) && ((kn >> (5u + rk)) & 1u);
+    const unsigned long long mask = __ballot(cand);
+    const uint32_t n = static_cast<uint32_t>(__popcll(mask));
+    if (n == 0) {
+      dead = true;
+      break;
+    }
+    const uint32_t k = static_cast<uint32_t>((static_cast<uint64_t>(lane_read(rnd[0], s)) * n) >> 32);
+    const uint32_t before = static_cast<uint32_t>(__popcll(mask & ((1ull << lane) - 1ull)));
+    const int idx = __ffsll(static_cast<unsigned long long>(__ballot(cand && before == k))) - 1;
+    taken |= 1ull << idx;
+    weight *= n;
+    new_hand = (new_hand & ~(31u << (5 * s))) | (lane_read(card, idx) << (5 * s));
+  }
+  if (dead) {
+    if (lane < a.SW) dst[lane] = wj;
+    if (lane == 0) a.weight[o] = 0u;
+    return;
+  }
+
+  // ---- the rest of the pool onto the undealt deck positions: rank of a distinct random key ------------------------------------
+  const unsigned long long rest = __ballot(in_pool && !((taken >> lane) & 1ull));
+  const uint32_t key = (rnd[1] & ~63u) | static_cast<uint32_t>(lane);
+  int rank = 0;
+  for (unsigned long long todo = rest; todo; todo &= todo - 1) {
+    const uint32_t ki = lane_read(key, __ffsll(todo) - 1);
+    rank += ki < key ? 1 : 0;
+  }
+  const int dest = deck_pos + rank;   // (meaningful in the lanes of `rest`)
+
+  // ---- the row: word 10 + seat = the new hand, the deck words' undealt bytes = the shuffled cards ------------------------------
+  const int j = lane - W_DECK;   // deck word of this lane (bytes 4j .. 4j + 3), if 0 <= j < ceil(D / 4)
+  uint32_t neww = wj;
+  if (j >= 0 && 4 * j < a.D) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int p = 4 * j + b;
+      if (p >= deck_pos && p < a.D) neww &= ~(255u << (8 * b));
+    }
+  }
+  for (unsigned long long todo = rest; todo; todo &= todo - 1) {
+    const int l = __ffsll(todo) - 1;
+    const int d = static_cast<int>(lane_read(static_cast<uint32_t>(dest), l));
+    const uint32_t c = lane_read(card, l);
+    if ((d >> 2) == j) neww |= c << (8 * (d & 3));
+  }
+  if (lane == 10 + seat) neww = new_hand;
+  if (lane < a.SW) dst[lane] = neww;
+  if (lane == 0) a.weight[o] = weight;
+}
+
+// 64-bit sum over the wavefront (xor butterfly on the two halves: every lane ends with the total)
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t lo = static_cast<uint32_t>(__shfl_xor(static_cast<int>(static_cast<uint32_t>(v)), off));
+    const uint32_t hi = static_cast<uint32_t>(__shfl_xor(static_cast<int>(static_cast<uint32_t>(static_cast<unsigned long long>(v) >> 32)), off));
+    v += static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo);
+  }
+  return v;
+}
+
+// One wavefront per root: the replicas' weights are summed once (every action of a root starts from the same replicas), then
+// sum of weight * score per legal action, lanes striding over the replicas.
+__global__ void __launch_bounds__(256) search_reduce_kernel(const int8_t* __restrict__ score, const uint32_t* __restrict__ weight,
+                                                            const int8_t* __restrict__ legal, long long m, int A, int R,
+                                                            float* __restrict__ value, long long* __restrict__ wsum,
+                                                            int32_t* __restrict__ n_live, int32_t* __restrict__ best) {
+  const int lane = threadIdx.x & 63;
+  const long long i = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (i >= m) return;
+  const uint32_t* w = weight + i * R;
+  long long sw = 0, nl = 0;
+  for (int r = lane; r < R; r += 64) {
+    const uint32_t v = w[r];
+    sw += v;
+    nl += v != 0u ? 1 : 0;
+  }
+  sw = wave_sum(sw);
+  nl = wave_sum(nl);
+  float best_v = -INFINITY;
+  int best_a = -1;
+  for (int act = 0; act < A; ++act) {
+    const bool ok = legal[i * A + act] != 0 && sw > 0;   // (wave-uniform)
+    long long num = 0;
+    if (ok) {
+      const int8_t* s = score + (i * A + act) * static_cast<long long>(R);
+      for (int r = lane; r < R; r += 64) num += static_cast<long long>(w[r]) * s[r];
+      num = wave_sum(num);
+    }
+    const float v = ok ? static_cast<float>(static_cast<double>(num) / static_cast<double>(sw)) : NAN;
+    if (ok && v > best_v) {   // strict: the lowest uid wins ties
+      best_v = v;
+      best_a = act;
+    }
+    if (lane == 0) {
+      value[i * A + act] = v;
+      wsum[i * A + act] = ok ? sw : 0;
+      n_live[i * A + act] = ok ? static_cast<int32_t>(nl) : 0;
+    }
+  }
+  if (best && lane == 0) best[i] = best_a;
+}
+
+int have_device() {
+  static const int ndev = [] {
+    int n = 0;
+    return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
+  }();
+  return ndev > 0 ? HB_OK : hb::fail(HB_ERR_NO_DEVICE, "no HIP device available");
+}
+
+}  // namespace
+
+extern "C" int hb_belief_determinize(const hb_config* cfg, const uint32_t* src_rows_dev, int64_t m, int32_t seat, int32_t replicas,
+                                     uint64_t seed, uint64_t draw, int64_t first_row_id, uint32_t* out_rows_dev, uint32_t* weight_dev,
+                                     void* stream) {
+  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  if (m < 0) return hb::fail(HB_ERR_INVALID, "m must be >= 0");
+  if (replicas < 1) return hb::fail(HB_ERR_INVALID, "replicas must be >= 1, got %d", replicas);
+  if (seat < -1 || seat >= cfg->players)
+    return hb::fail(HB_ERR_INVALID, "seat %d out of range: -1 (each row's current player) or 0..%d", seat, cfg->players - 1);
+  if (!src_rows_dev || !out_rows_dev || !weight_dev) return hb::fail(HB_ERR_INVALID, "null argument");
+  if (m > (static_cast<int64_t>(1) << 31) / replicas - 1)
+    return hb::fail(HB_ERR_INVALID, "m * replicas must stay below 2^31 output rows: split the call (first_row_id)");
+  if (m == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  DetArgs a{};
+  a.src = src_rows_dev; a.out = out_rows_dev; a.weight = weight_dev;
+  a.n_out = m * replicas;
+  a.first_row = first_row_id;
+  a.seed = seed; a.draw = draw;
+  a.replicas = replicas; a.seat = seat;
+  a.P = cfg->players; a.C = cfg->colors; a.R = cfg->ranks; a.H = cfg->hand_size;
+  a.D = hb_deck_size(cfg);
+  a.SW = hb_state_words(cfg);
+  const unsigned blocks = static_cast<unsigned>((a.n_out + 3) / 4);   // four wavefronts = four output rows per workgroup
+  hipLaunchKernelGGL(belief_determinize_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+extern "C" int hb_search_reduce(const int8_t* score_dev, const uint32_t* weight_dev, const int8_t* legal_dev, int64_t m,
+                                int32_t n_actions, int32_t replicas, float* value_dev, int64_t* wsum_dev, int32_t* n_live_dev,
+                                int32_t* best_dev, void* stream) {
+  if (m < 0) return hb::fail(HB_ERR_INVALID, "m must be >= 0");
+  if (n_actions < 1 || n_actions > 64) return hb::fail(HB_ERR_INVALID, "n_actions %d out of range 1..64", n_actions);
+  if (replicas < 1 || replicas > (1 << 20)) return hb::fail(HB_ERR_INVALID, "replicas %d out of range 1..2^20 (64-bit sums)", replicas);
+  if (!score_dev || !weight_dev || !legal_dev || !value_dev || !wsum_dev || !n_live_dev) return hb::fail(HB_ERR_INVALID, "null argument");
+  if (m > (static_cast<int64_t>(1) << 31) - 8) return hb::fail(HB_ERR_INVALID, "m must stay below 2^31 roots");
+  if (m == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  const unsigned blocks = static_cast<unsigned>((m + 3) / 4);
+  hipLaunchKernelGGL(search_reduce_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), score_dev, weight_dev, legal_dev,
+                     static_cast<long long>(m), n_actions, replicas, value_dev, reinterpret_cast<long long*>(wsum_dev), n_live_dev,
+                     best_dev);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}

@@ -772,6 +772,39 @@ int hb_train_tally(const hb_config* cfg, int64_t n_games, int32_t seat, const in
                    const int8_t* terminal_dev, const int8_t* score_dev, const int32_t* tile_member_dev, int32_t n_members,
                    uint8_t* lost_dev, int16_t* length_dev, int64_t* counters_dev, void* stream);
 
+/* ---- belief-sampled rollout search (csrc/belief.hip; hanabi_hip/search.py) -----------------------------
+ * hb_belief_determinize: states the observing seat cannot tell apart from the real one. Output row i * replicas + r is source
+ * row i (src_rows_dev [m, hb_state_words()], as hb_env_export_state writes them) with ONLY two things changed: the seat's hand
+ * word and the undealt tail of the deck bytes. seat = -1: each row's current player. The pool is the multiset of cards the seat
+ * cannot see, in a fixed order: its hand slots oldest first, then the undealt deck positions ascending (<= 64 elements). A card
+ * is plausible for a slot iff the slot's knowledge bits (colour_plausible[5] rank_plausible[5]) allow its colour and its rank.
+ * Sequential importance sampling, no rejection loop:
+ *   for slot s = 0 .. hand size - 1: candidates = the pool elements not yet taken that are plausible for slot s, in pool order;
+ *   n_s = their number; n_s == 0: the replica is dead (weight 0, the output row is the source row unchanged); otherwise slot s
+ *   takes the k-th candidate, k = (u_s * n_s) >> 32;
+ *   the remaining pool elements go to the undealt deck positions in the order of their keys (element l: (v_l & ~63) | l, all
+ *   distinct; the element with the smallest key is dealt next): a uniform shuffle;
+ *   weight_dev[i * replicas + r] = prod n_s (<= 55^5 < 2^32).
+ * With these weights the rows estimate the uniform distribution over all assignments of the pool's PHYSICAL cards to (hand
+ * slots, deck positions) that respect the slots' plausibility: the public-knowledge-plus-card-counting belief ("V0 belief"). It
+ * does NOT model what the partners' policy implies about the hand (no range tracking): it is not the exact posterior.
+ * Randomness: Philox4x32-10(counter (128 + j, draw lo, row id lo, row id hi); key (seed lo, seed hi ^ draw hi)) with row id =
+ * first_row_id + output row index: u_s = word 0 of j = s, v_l = word 1 of j = l. A pure function of (seed, draw, row id, slot /
+ * pool index): the result does not depend on how a call is split. (The deals use counter word 0 < 64 and the colour
+ * permutations 64 .. 68 with the key seed; this kernel uses 128 .. 191.)
+ * Rows whose status is not "running" (and rows whose current player is no seat) give weight 0 and an unchanged copy.
+ * hb_search_reduce: score_dev [m, n_actions, replicas] int8 final scores of the rollouts, weight_dev [m, replicas] u32 (every
+ * action of a root starts from the same replicas), legal_dev [m, n_actions] int8 the roots' legal masks ->
+ *   value_dev [m, A] f32 = float(double(sum w * score) / double(sum w)), both sums exact in 64-bit integers;
+ *   wsum_dev [m, A] int64 = sum w; n_live_dev [m, A] int32 = replicas with w > 0;
+ *   best_dev [m] int32 (may be NULL) = the legal action of the largest value, the lowest uid winning ties; -1 when there is none.
+ * An action that is illegal at the root, and every action of a root with sum w = 0: value NaN, wsum 0, n_live 0.
+ * Both check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                         */
+int hb_belief_determinize(const hb_config* cfg, const uint32_t* src_rows_dev, int64_t m, int32_t seat, int32_t replicas, uint64_t seed,
+                          uint64_t draw, int64_t first_row_id, uint32_t* out_rows_dev, uint32_t* weight_dev, void* stream);
+int hb_search_reduce(const int8_t* score_dev, const uint32_t* weight_dev, const int8_t* legal_dev, int64_t m, int32_t n_actions,
+                     int32_t replicas, float* value_dev, int64_t* wsum_dev, int32_t* n_live_dev, int32_t* best_dev, void* stream);
+
 /* ---- One host call per step: hb_chain_run (csrc/chain.hip, round 3) ------------------------------------------------------
  * The session that drives DQNAgent (rlax_rainbow.py:277-339: explore / add_experience / update once per env step) issues ~25
  * launches, event waits and event records per step. A host fills an array of hb_cmd ONCE with every pointer, size and stream of
