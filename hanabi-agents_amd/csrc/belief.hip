@@ -11,6 +11,12 @@
 //
 // hb_search_reduce: per root, sum of weight * score and of weight over the replicas of every action in 64-bit integers (the
 // result does not depend on the order of summation), one division per (root, action), and the arg-max over the legal actions.
+//
+// hb_search_layout: the determinized rows copied into the [m, C, replicas] rollout games of a per-root candidate list, with each
+// game's forced first move and its "not played" mark. ONE wavefront per (root, replica): lane j < SW holds word j of the row and
+// stores it C times, coalesced. hb_search_compare: per root, every candidate's paired difference to a baseline candidate over the
+// shared replicas, and that difference's standard error; one wavefront per root like hb_search_reduce. Neither uses LDS, a
+// barrier or an atomic.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -180,6 +186,118 @@ __global__ void __launch_bounds__(256) search_reduce_kernel(const int8_t* __rest
   if (best && lane == 0) best[i] = best_a;
 }
 
+struct LayoutArgs {
+  const uint32_t* det;
+  const uint32_t* weight;
+  const int32_t* cand;
+  const int32_t* filler;
+  uint32_t* rows;
+  int32_t* forced;
+  uint8_t* done;
+  int32_t* n_played;
+  long long n_src;   // m * R
+  int C, R, SW;
+};
+
+// One wavefront per (root i, replica r): source row i * R + r goes to games (i * C + c) * R + r, c = 0 .. C - 1. The wavefront of
+// replica 0 also counts the root's played games: (candidates >= 0) * (replicas of weight != 0).
+__global__ void __launch_bounds__(256) search_layout_kernel(LayoutArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long long o = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);   // source row of this wavefront
+  if (o >= a.n_src) return;
+  const long long i = o / a.R;
+  const int r = static_cast<int>(o - i * a.R);
+  const uint32_t wj = lane < a.SW ? a.det[o * a.SW + lane] : 0u;
+  const bool live = a.weight[o] != 0u;
+  const int32_t fill = a.filler[i];
+  const int32_t* cand = a.cand + i * a.C;
+  for (int c = 0; c < a.C; ++c) {
+    const int32_t uid = cand[c];   // (wave-uniform)
+    const bool played = uid >= 0 && live;
+    const long long g = (i * a.C + c) * a.R + r;
+    if (lane < a.SW) a.rows[g * a.SW + lane] = wj;
+    if (lane == 0) {
+      a.forced[g] = uid >= 0 ? uid : fill;   // (a dead replica is a copy of its root: the candidate is as legal there)
+      a.done[g] = played ? 0 : 0x80;
+    }
+  }
+  if (r == 0) {
+    const int n_cand = __popcll(__ballot(lane < a.C && cand[lane < a.C ? lane : 0] >= 0));
+    long long nl = 0;
+    for (int q = lane; q < a.R; q += 64) nl += a.weight[o + q] != 0u ? 1 : 0;
+    nl = wave_sum(nl);
+    if (lane == 0) a.n_played[i] = static_cast<int32_t>(nl * n_cand);
+  }
+}
+
+// double sum over the wavefront (the butterfly of wave_sum: every lane ends with the same total)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(v));
+    const uint32_t lo = static_cast<uint32_t>(__shfl_xor(static_cast<int>(static_cast<uint32_t>(b)), off));
+    const uint32_t hi = static_cast<uint32_t>(__shfl_xor(static_cast<int>(static_cast<uint32_t>(b >> 32)), off));
+    v += __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
+  }
+  return v;
+}
+
+// One wavefront per root. d_r = score[c][r] - score[base][r] over the replicas of weight > 0: mu = sum w d / sum w from exact
+// integer sums; then a second pass in double over the non-negative terms (w (d - mu))^2, each lane adding its replicas in
+// ascending order, stride 64. se = sqrt(sum) / sum w * sqrt(n / (n - 1)): with constant weights the s / sqrt(n) of the d_r.
+__global__ void __launch_bounds__(256) search_compare_kernel(const int8_t* __restrict__ score, const uint32_t* __restrict__ weight,
+                                                             const int32_t* __restrict__ cand, const int32_t* __restrict__ base_slot,
+                                                             long long m, int C, int R, double* __restrict__ diff,
+                                                             double* __restrict__ se, int32_t* __restrict__ n_pair) {
+  const int lane = threadIdx.x & 63;
+  const long long i = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (i >= m) return;
+  const uint32_t* w = weight + i * R;
+  long long sw = 0, nl = 0;
+  for (int r = lane; r < R; r += 64) {
+    const uint32_t v = w[r];
+    sw += v;
+    nl += v != 0u ? 1 : 0;
+  }
+  sw = wave_sum(sw);
+  nl = wave_sum(nl);
+  if (lane == 0) n_pair[i] = static_cast<int32_t>(nl);
+  int base = base_slot[i];
+  if (base >= C) base = -1;   // (no such slot: no baseline)
+  const bool root_ok = base >= 0 && sw > 0 && cand[i * C + (base >= 0 ? base : 0)] >= 0;   // (wave-uniform)
+  const int8_t* sb = score + (i * C + (base >= 0 ? base : 0)) * static_cast<long long>(R);
+  const double dsw = static_cast<double>(sw);
+  for (int c = 0; c < C; ++c) {
+    double mu = NAN, err = NAN;
+    if (root_ok && cand[i * C + c] >= 0) {
+      if (c == base) {
+        mu = 0.0;
+        err = 0.0;
+      } else {
+        const int8_t* s = score + (i * C + c) * static_cast<long long>(R);
+        long long num = 0;
+        for (int r = lane; r < R; r += 64) num += static_cast<long long>(w[r]) * (static_cast<int>(s[r]) - static_cast<int>(sb[r]));
+        num = wave_sum(num);
+        mu = static_cast<double>(num) / dsw;
+        err = INFINITY;
+        if (nl >= 2) {
+          double acc = 0.0;
+          for (int r = lane; r < R; r += 64) {
+            const double t = static_cast<double>(w[r]) * (static_cast<double>(static_cast<int>(s[r]) - static_cast<int>(sb[r])) - mu);
+            acc += t * t;
+          }
+          acc = wave_sum_f64(acc);
+          err = sqrt(acc) / dsw * sqrt(static_cast<double>(nl) / static_cast<double>(nl - 1));
+        }
+      }
+    }
+    if (lane == 0) {
+      diff[i * C + c] = mu;
+      se[i * C + c] = err;
+    }
+  }
+}
+
 int have_device() {
   static const int ndev = [] {
     int n = 0;
@@ -233,6 +351,51 @@ extern "C" int hb_search_reduce(const int8_t* score_dev, const uint32_t* weight_
   hipLaunchKernelGGL(search_reduce_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), score_dev, weight_dev, legal_dev,
                      static_cast<long long>(m), n_actions, replicas, value_dev, reinterpret_cast<long long*>(wsum_dev), n_live_dev,
                      best_dev);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+extern "C" int hb_search_layout(const hb_config* cfg, const uint32_t* det_rows_dev, const uint32_t* weight_dev, const int32_t* cand_dev,
+                                const int32_t* filler_dev, int64_t m, int32_t n_cand, int32_t replicas, uint32_t* rows_out_dev,
+                                int32_t* forced_out_dev, uint8_t* done_out_dev, int32_t* n_played_out_dev, void* stream) {
+  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  if (m < 0) return hb::fail(HB_ERR_INVALID, "m must be >= 0");
+  if (n_cand < 1 || n_cand > 64) return hb::fail(HB_ERR_INVALID, "n_cand %d out of range 1..64", n_cand);
+  if (replicas < 1) return hb::fail(HB_ERR_INVALID, "replicas must be >= 1, got %d", replicas);
+  if (!det_rows_dev || !weight_dev || !cand_dev || !filler_dev || !rows_out_dev || !forced_out_dev || !done_out_dev || !n_played_out_dev)
+    return hb::fail(HB_ERR_INVALID, "null argument");
+  if (m > ((static_cast<int64_t>(1) << 31) - 1) / (static_cast<int64_t>(n_cand) * replicas))
+    return hb::fail(HB_ERR_INVALID, "m * n_cand * replicas must stay below 2^31 rollout games: split the roots");
+  if (m == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  LayoutArgs a{};
+  a.det = det_rows_dev; a.weight = weight_dev; a.cand = cand_dev; a.filler = filler_dev;
+  a.rows = rows_out_dev; a.forced = forced_out_dev; a.done = done_out_dev; a.n_played = n_played_out_dev;
+  a.n_src = m * replicas;
+  a.C = n_cand; a.R = replicas;
+  a.SW = hb_state_words(cfg);
+  const unsigned blocks = static_cast<unsigned>((a.n_src + 3) / 4);   // four wavefronts = four source rows per workgroup
+  hipLaunchKernelGGL(search_layout_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+extern "C" int hb_search_compare(const int8_t* score_dev, const uint32_t* weight_dev, const int32_t* cand_dev, const int32_t* base_slot_dev,
+                                 int64_t m, int32_t n_cand, int32_t replicas, double* diff_dev, double* se_dev, int32_t* n_pair_dev,
+                                 void* stream) {
+  if (m < 0) return hb::fail(HB_ERR_INVALID, "m must be >= 0");
+  if (n_cand < 1 || n_cand > 64) return hb::fail(HB_ERR_INVALID, "n_cand %d out of range 1..64", n_cand);
+  if (replicas < 1 || replicas > (1 << 20)) return hb::fail(HB_ERR_INVALID, "replicas %d out of range 1..2^20 (64-bit sums)", replicas);
+  if (!score_dev || !weight_dev || !cand_dev || !base_slot_dev || !diff_dev || !se_dev || !n_pair_dev)
+    return hb::fail(HB_ERR_INVALID, "null argument");
+  if (m > ((static_cast<int64_t>(1) << 31) - 1) / (static_cast<int64_t>(n_cand) * replicas))
+    return hb::fail(HB_ERR_INVALID, "m * n_cand * replicas must stay below 2^31 rollout games");
+  if (m == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  const unsigned blocks = static_cast<unsigned>((m + 3) / 4);
+  hipLaunchKernelGGL(search_compare_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), score_dev, weight_dev, cand_dev,
+                     base_slot_dev, static_cast<long long>(m), n_cand, replicas, diff_dev, se_dev, n_pair_dev);
   HB_HIP(hipGetLastError());
   return HB_OK;
 }

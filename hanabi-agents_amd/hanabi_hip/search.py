@@ -13,8 +13,12 @@
   the blueprint, in lock step, exactly like `Evaluator.run`: `eval_moves` of the seat to act (Philox seed = the search's
   `seed`, draw = turn + 1, rollout game j keyed by game id first_game_id + j), `HanabiEnv.step`, `hb_eval_tally`. The final
   scores are reduced by hb_search_reduce: value = sum w * score / sum w in exact integer sums.
+* `RolloutSearch.run_candidates` is the same search over a per-root candidate list [m, C] instead of all A actions
+  (hb_search_layout builds the [m, C, replicas] games on the device); with `base_slot` it also gives every candidate's paired
+  difference to the baseline's score, replica by replica, and that difference's standard error (hb_search_compare).
+  `RolloutSearch.confirm` re-measures {blueprint move, challenger} of every root on fresh replicas: screen, then confirm.
 * `SearchPlayer` is an agent for `Evaluator.run`: the blueprint's move unless the search finds one that is better by more than
-  `threshold`.
+  `threshold` and, with `z` / `confirm_replicas`, by more than z standard errors of the paired difference.
 
 Colour-shuffled envs are refused: the rollout env's game ids would draw other permutations than the source's.
 """
@@ -95,14 +99,63 @@ def search_reduce(scores, weights, legal):
     return value, wsum, n_live, best
 
 
+def search_layout(cfg, det_rows, weights, cand, filler, replicas, out=None):
+    """hb_search_layout: det_rows [m * R, SW] int32, weights [m * R] (u32 bits in int32), cand [m, C] int32 (uid, or -1: no
+    candidate in this slot), filler [m] int32 -> (rows [m * C * R, SW] int32, forced [m * C * R] int32, done [m * C * R] uint8,
+    n_played [m] int32). `out`: an optional tuple of these four buffers to write into."""
+    m, Cn = cand.shape
+    R, SW = int(replicas), det_rows.shape[1]
+    n, dev = m * Cn * R, det_rows.device
+    assert det_rows.shape == (m * R, SW) and det_rows.dtype == torch.int32 and det_rows.is_contiguous()
+    assert weights.shape == (m * R,) and weights.dtype == torch.int32 and weights.is_contiguous()
+    assert cand.dtype == torch.int32 and cand.is_contiguous()
+    assert filler.shape == (m,) and filler.dtype == torch.int32 and filler.is_contiguous()
+    if out is None:
+        out = (torch.empty((n, SW), dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+               torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(m, dtype=torch.int32, device=dev))
+    rows, forced, done, n_played = out
+    assert rows.shape == (n, SW) and rows.dtype == torch.int32 and rows.is_contiguous()
+    assert forced.shape == (n,) and forced.dtype == torch.int32 and forced.is_contiguous()
+    assert done.shape == (n,) and done.dtype == torch.uint8 and done.is_contiguous()
+    assert n_played.shape == (m,) and n_played.dtype == torch.int32 and n_played.is_contiguous()
+    with torch.cuda.device(dev):
+        K.check(K.lib().hb_search_layout(C.byref(cfg), K.dptr(det_rows), K.dptr(weights), K.dptr(cand), K.dptr(filler), m, Cn, R,
+                                         K.dptr(rows), K.dptr(forced), K.dptr(done), K.dptr(n_played), K.current_stream()))
+    return rows, forced, done, n_played
+
+
+def search_compare(scores, weights, cand, base_slot):
+    """hb_search_compare: scores [m, C, R] int8, weights [m, R] (u32 bits in int32), cand [m, C] int32, base_slot [m] int32 ->
+    (diff [m, C] f64, se [m, C] f64, n_pair [m] int32): every slot's paired difference to the base slot and its standard error."""
+    m, Cn, R = scores.shape
+    assert scores.dtype == torch.int8 and scores.is_contiguous()
+    assert weights.shape == (m, R) and weights.dtype == torch.int32 and weights.is_contiguous()
+    assert cand.shape == (m, Cn) and cand.dtype == torch.int32 and cand.is_contiguous()
+    assert base_slot.shape == (m,) and base_slot.dtype == torch.int32 and base_slot.is_contiguous()
+    dev = scores.device
+    diff = torch.empty((m, Cn), dtype=torch.float64, device=dev)
+    se = torch.empty((m, Cn), dtype=torch.float64, device=dev)
+    n_pair = torch.empty(m, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        K.check(K.lib().hb_search_compare(K.dptr(scores), K.dptr(weights), K.dptr(cand), K.dptr(base_slot), m, Cn, R, K.dptr(diff),
+                                          K.dptr(se), K.dptr(n_pair), K.current_stream()))
+    return diff, se, n_pair
+
+
 class SearchResult:
     """value [m, A] f32 (NaN: illegal at the root, or no live replica), wsum [m, A] int64, n_live [m, A] int32, best [m] int32
     (-1: no action has a value), rollouts = games played, turns = turns of the longest rollout, dead = replicas of weight 0
-    among the running roots' replicas. Device tensors."""
+    among the running roots' replicas. Device tensors. From run_candidates the second axis is the candidate slot: `cand` [m, C]
+    int32 the uids searched, `best` the best slot and `best_uid` [m] int32 its uid (-1: none). With a baseline: `diff` [m, C] f64
+    the weighted mean over the replicas of score[slot] - score[baseline], `se` [m, C] f64 its standard error (inf with fewer
+    than two live replicas; both 0 in the baseline's slot, NaN where there is no candidate, no baseline or no live replica) and
+    `n_pair` [m] int32 the live replicas (hb_search_compare). None when not computed."""
 
-    def __init__(self, value, wsum, n_live, best, rollouts, turns, dead=0, replicas=0):
+    def __init__(self, value, wsum, n_live, best, rollouts, turns, dead=0, replicas=0, diff=None, se=None, n_pair=None, cand=None,
+                 best_uid=None):
         self.value, self.wsum, self.n_live, self.best = value, wsum, n_live, best
         self.rollouts, self.turns, self.dead, self.replicas = int(rollouts), int(turns), int(dead), int(replicas)
+        self.diff, self.se, self.n_pair, self.cand, self.best_uid = diff, se, n_pair, cand, best_uid
 
     def __repr__(self):
         return f"SearchResult(roots={self.value.shape[0]}, rollouts={self.rollouts}, turns={self.turns})"
@@ -144,7 +197,8 @@ class RolloutSearch:
     """Value of every root action under `blueprint` by belief-sampled rollouts; see the module docstring.
 
     first_game_id: global id of rollout game 0 (keys the blueprint's draws, like Evaluator's). The rollout env and every
-    buffer are built by the first run() of a size and kept for the next."""
+    buffer are built by the first run() of a size and kept for the next; run_candidates() keeps its own per (m, C, replicas),
+    so that a screening stage's env survives the confirming stage's."""
 
     def __init__(self, game="Hanabi-Full", players=2, replicas=32, seed=1, device=None, config=None, check_every=8, first_game_id=0):
         self.cfg = _config(game, players, config)
@@ -161,31 +215,45 @@ class RolloutSearch:
         self.n_counters = K.lib().hb_eval_counters(C.byref(self.cfg))
         self._sized = {}   # m -> buffers of that size
         self._scratch = weakref.WeakKeyDictionary()   # agent -> the buffers its eval_moves writes
+        self._cand_sized = {}   # (m, C, replicas) -> buffers of run_candidates, each with the scratch of its own env
+
+    def _buffers(self, m, Cn, R, first_game_id, dev):
+        SW = self.det.state_words
+        n = m * Cn * R
+        env = HanabiEnv(config=self.cfg, n_games=n, seed=self.seed, first_game_id=first_game_id, device=dev, packed=True)
+        return dict(env=env, det_rows=torch.empty((m * R, SW), dtype=torch.int32, device=dev),
+                    weights=torch.empty(m * R, dtype=torch.int32, device=dev),
+                    rows=torch.empty((n, SW), dtype=torch.int32, device=dev),
+                    forced=torch.empty(n, dtype=torch.int32, device=dev), act=torch.empty(n, dtype=torch.int32, device=dev),
+                    done=torch.empty(n, dtype=torch.uint8, device=dev), final_score=torch.empty(n, dtype=torch.int8, device=dev),
+                    length=torch.empty(n, dtype=torch.int16, device=dev),
+                    counters=torch.empty(self.n_counters, dtype=torch.int64, device=dev),
+                    n_played=torch.empty(m, dtype=torch.int32, device=dev))
 
     def _setup(self, m, dev):
         b = self._sized.get(m)
         if b is not None:
             return b
         self._sized.clear()   # one size at a time: a rollout env of the old size is memory the new one needs
-        A, R, SW = self.num_actions, self.replicas, self.det.state_words
-        n = m * A * R
-        env = HanabiEnv(config=self.cfg, n_games=n, seed=self.seed, first_game_id=self.first_game_id, device=dev, packed=True)
-        b = dict(env=env, det_rows=torch.empty((m * R, SW), dtype=torch.int32, device=dev),
-                 weights=torch.empty(m * R, dtype=torch.int32, device=dev),
-                 rows=torch.empty((n, SW), dtype=torch.int32, device=dev),
-                 forced=torch.empty(n, dtype=torch.int32, device=dev), act=torch.empty(n, dtype=torch.int32, device=dev),
-                 done=torch.empty(n, dtype=torch.uint8, device=dev), final_score=torch.empty(n, dtype=torch.int8, device=dev),
-                 length=torch.empty(n, dtype=torch.int16, device=dev),
-                 counters=torch.empty(self.n_counters, dtype=torch.int64, device=dev),
-                 uid=torch.arange(A, dtype=torch.int32, device=dev).view(1, A, 1))
+        A = self.num_actions
+        b = self._buffers(m, A, self.replicas, self.first_game_id, dev)
+        b["uid"] = torch.arange(A, dtype=torch.int32, device=dev).view(1, A)
         self._sized[m] = b
         return b
 
-    @torch.no_grad()
-    def run(self, rows, legal, blueprint, draw, seat=None):
-        """rows [m, state_words] int32 state rows (hb_env_export_state), legal [m, A] int8 the legal mask of each root's seat to
-        act, blueprint: one agent per seat with eval_moves, draw: Philox draw of the determinization (with the search's seed).
-        All running roots must have the same current player (`seat`, when given, must be that player)."""
+    def _setup_candidates(self, m, Cn, R, first_game_id, dev):
+        b = self._cand_sized.get((m, Cn, R))
+        if b is None:
+            for k in [k for k in self._cand_sized if k[1:] == (Cn, R)]:   # the same stage at another number of roots
+                del self._cand_sized[k]
+            b = self._cand_sized[(m, Cn, R)] = self._buffers(m, Cn, R, first_game_id, dev)
+            b["scratch"] = weakref.WeakKeyDictionary()
+        # a rollout env never deals (auto-reset off, states imported): its game ids key the blueprint's draws only
+        b["env"].first_game_id = first_game_id
+        return b
+
+    def _roots(self, rows, blueprint, seat):
+        """The checks run() and run_candidates() share -> (rows on the device, blueprint, running [m] bool, current players)."""
         blueprint = list(blueprint)
         if len(blueprint) != self.players:
             raise ValueError(f"one blueprint agent per seat: {self.players} players, {len(blueprint)} agents")
@@ -193,13 +261,8 @@ class RolloutSearch:
             if not hasattr(a, "eval_moves"):
                 raise TypeError(f"{type(a).__name__} has no eval_moves()")
         r = _rows(rows, self.det.state_words, self.device)
-        dev = r.device
-        m, A, R = r.shape[0], self.num_actions, self.replicas
-        if m < 1:
+        if r.shape[0] < 1:
             raise ValueError("no roots")
-        lg = torch.as_tensor(legal).to(device=dev, dtype=torch.int8).contiguous()
-        if lg.shape != (m, A):
-            raise ValueError(f"legal has shape ({m}, {A}), got {tuple(lg.shape)}")
         w0 = r[:, 0]
         running = ((w0 >> 19) & 3) == 0
         cps = torch.unique(((w0 >> 13) & 7)[running]).tolist()
@@ -207,40 +270,147 @@ class RolloutSearch:
             raise ValueError(f"all roots must have the same current player, got seats {cps}")
         if seat is not None and cps and cps[0] != int(seat):
             raise ValueError(f"the roots' current player is seat {cps[0]}, not seat {seat}")
-        b = self._setup(m, dev)
-        if not cps:   # no root is running: nothing to play
-            z = torch.zeros((m, A), dtype=torch.int64, device=dev)
-            return SearchResult(torch.full((m, A), float("nan"), device=dev), z, z.int(), torch.full((m,), -1, dtype=torch.int32, device=dev),
-                                0, 0)
-        cp = int(cps[0])
+        return r, blueprint, running, cps
+
+    def _nothing(self, m, Cn, dev, cand=None, compared=False):
+        """The result when no root is running: nothing to play."""
+        z = torch.zeros((m, Cn), dtype=torch.int64, device=dev)
+        none = torch.full((m,), -1, dtype=torch.int32, device=dev)
+        res = SearchResult(torch.full((m, Cn), float("nan"), device=dev), z, z.int(), none, 0, 0)
+        if cand is not None:
+            res.cand, res.best_uid = cand, none.clone()
+        if compared:
+            res.diff = torch.full((m, Cn), float("nan"), dtype=torch.float64, device=dev)
+            res.se, res.n_pair = res.diff.clone(), torch.zeros(m, dtype=torch.int32, device=dev)
+        return res
+
+    def _play(self, b, r, cand, filler, R, cp, blueprint, draw, first_row_id, scratch):
+        """Determinize the roots `r` R times, lay the replicas out as [m, C, R] games of b's env (hb_search_layout) and play them
+        to the end. Leaves the final scores in b["final_score"]; returns (games played as a device scalar, turns)."""
         env = b["env"]
+        self.det.sample(r, seat=cp, replicas=R, seed=self.seed, draw=draw, first_row_id=first_row_id, out=(b["det_rows"], b["weights"]))
+        # [m, C, R]: block c of root i holds the same R replicas. A slot without a candidate (an illegal action, in run()) is
+        # never counted (done up front); its games move in step with the others on the root's filler move, so that no illegal
+        # move reaches the env
+        search_layout(self.cfg, b["det_rows"], b["weights"], cand, filler, R, out=(b["rows"], b["forced"], b["done"], b["n_played"]))
+        b["final_score"].zero_()
+        b["length"].zero_()
+        b["counters"].zero_()
+        b["counters"][0] = b["n_played"].sum()
+        rollouts = b["counters"][0].clone()
+        env.import_state(b["rows"])
+        illegal0 = env.illegal_count()
+        turns = rollout(env, self.cfg, blueprint, self.seed, cp, b["forced"], b["done"], b["final_score"], b["length"], b["counters"],
+                        b["act"], scratch, self.check_every)
+        illegal = env.illegal_count() - illegal0
+        if illegal:
+            raise RuntimeError(f"{illegal} illegal moves in the rollouts (a candidate that is illegal at its root, or the blueprint's)")
+        return rollouts, turns
+
+    @torch.no_grad()
+    def run(self, rows, legal, blueprint, draw, seat=None, baseline=None):
+        """rows [m, state_words] int32 state rows (hb_env_export_state), legal [m, A] int8 the legal mask of each root's seat to
+        act, blueprint: one agent per seat with eval_moves, draw: Philox draw of the determinization (with the search's seed).
+        All running roots must have the same current player (`seat`, when given, must be that player). baseline: optional [m]
+        int32 uids (the blueprint's moves): the result's diff / se / n_pair are then every action's paired difference to it."""
+        r, blueprint, running, cps = self._roots(rows, blueprint, seat)
+        dev = r.device
+        m, A, R = r.shape[0], self.num_actions, self.replicas
+        lg = torch.as_tensor(legal).to(device=dev, dtype=torch.int8).contiguous()
+        if lg.shape != (m, A):
+            raise ValueError(f"legal has shape ({m}, {A}), got {tuple(lg.shape)}")
+        if baseline is not None:
+            baseline = torch.as_tensor(baseline).to(device=dev, dtype=torch.int32).contiguous()
+            if baseline.shape != (m,):
+                raise ValueError(f"baseline has shape ({m},), got {tuple(baseline.shape)}")
+        b = self._setup(m, dev)
+        if not cps:
+            return self._nothing(m, A, dev, compared=baseline is not None)
+        cp = int(cps[0])
         with torch.cuda.device(dev):
-            self.det.sample(r, seat=cp, replicas=R, seed=self.seed, draw=draw, first_row_id=0, out=(b["det_rows"], b["weights"]))
-            SW = self.det.state_words
-            # [m, A, R]: block a of root i holds the same R replicas
-            b["rows"].view(m, A, R, SW).copy_(b["det_rows"].view(m, 1, R, SW).expand(m, A, R, SW))
             lgb = lg != 0
-            played = lgb.view(m, A, 1) & (b["weights"].view(m, 1, R) != 0)
-            # an illegal action's block is never counted (done up front); its games move in step with the others on the
-            # root's lowest legal uid, so that no illegal move reaches the env
-            first_legal = lgb.int().argmax(1).int().view(m, 1, 1)
-            b["forced"].view(m, A, R).copy_(torch.where(lgb.view(m, A, 1), b["uid"], first_legal).expand(m, A, R))
-            b["done"].view(m, A, R).copy_(torch.where(played, 0, 0x80).to(torch.uint8))
-            b["final_score"].zero_()
-            b["length"].zero_()
-            b["counters"].zero_()
-            b["counters"][0] = played.sum()
-            rollouts = b["counters"][0].clone()
+            cand = torch.where(lgb, b["uid"], -1).int().contiguous()
+            filler = lgb.int().argmax(1).int()   # the root's lowest legal uid
+            rollouts, turns = self._play(b, r, cand, filler, R, cp, blueprint, draw, 0, self._scratch)
             dead = (running.view(m, 1) & (b["weights"].view(m, R) == 0)).sum()
-            env.import_state(b["rows"])
-            illegal0 = env.illegal_count()
-            turns = rollout(env, self.cfg, blueprint, self.seed, cp, b["forced"], b["done"], b["final_score"], b["length"],
-                            b["counters"], b["act"], self._scratch, self.check_every)
-            illegal = env.illegal_count() - illegal0
-            if illegal:
-                raise RuntimeError(f"the blueprint chose {illegal} illegal moves in the rollouts")
             value, wsum, n_live, best = search_reduce(b["final_score"].view(m, A, R), b["weights"].view(m, R), lg)
-        return SearchResult(value, wsum, n_live, best, int(rollouts.item()), turns, dead=int(dead.item()), replicas=int(running.sum().item()) * R)
+            res = SearchResult(value, wsum, n_live, best, int(rollouts.item()), turns, dead=int(dead.item()),
+                               replicas=int(running.sum().item()) * R)
+            if baseline is not None:   # (slot = uid here)
+                res.diff, res.se, res.n_pair = search_compare(b["final_score"].view(m, A, R), b["weights"].view(m, R), cand, baseline)
+        return res
+
+    @torch.no_grad()
+    def run_candidates(self, rows, cand, filler, blueprint, draw, replicas=None, first_row_id=0, first_game_id=None, base_slot=None):
+        """run() over a candidate list: cand [m, C] int32 (C <= 64) holds the uids to play first at each root (-1: no candidate
+        in this slot; a candidate must be legal at its root), filler [m] int32 the move that the games of empty slots make (the
+        root's lowest legal uid). replicas: per candidate (default: the search's); first_row_id: row id of replica 0 of root 0
+        (keys the determinization, with the search's seed and `draw`); first_game_id: game id of rollout game 0 (default: the
+        search's). The result's second axis is the slot: `best` is the best slot, `best_uid` its uid, `cand` the list. base_slot:
+        optional [m] int32 slot of each root's baseline (-1: none): fills diff / se / n_pair (hb_search_compare)."""
+        r, blueprint, running, cps = self._roots(rows, blueprint, None)
+        dev = r.device
+        m = r.shape[0]
+        R = self.replicas if replicas is None else int(replicas)
+        if R < 1:
+            raise ValueError(f"replicas must be >= 1, got {replicas}")
+        cand = torch.as_tensor(cand).to(device=dev, dtype=torch.int32).contiguous()
+        if cand.dim() != 2 or cand.shape[0] != m or not 1 <= cand.shape[1] <= 64:
+            raise ValueError(f"cand has shape ({m}, C) with C in 1..64, got {tuple(cand.shape)}")
+        Cn = cand.shape[1]
+        filler = torch.as_tensor(filler).to(device=dev, dtype=torch.int32).contiguous()
+        if filler.shape != (m,):
+            raise ValueError(f"filler has shape ({m},), got {tuple(filler.shape)}")
+        if base_slot is not None:
+            base_slot = torch.as_tensor(base_slot).to(device=dev, dtype=torch.int32).contiguous()
+            if base_slot.shape != (m,):
+                raise ValueError(f"base_slot has shape ({m},), got {tuple(base_slot.shape)}")
+        gid = self.first_game_id if first_game_id is None else int(first_game_id)
+        b = self._setup_candidates(m, Cn, R, gid, dev)
+        if not cps:
+            return self._nothing(m, Cn, dev, cand=cand, compared=base_slot is not None)
+        cp = int(cps[0])
+        with torch.cuda.device(dev):
+            rollouts, turns = self._play(b, r, cand, filler, R, cp, blueprint, draw, int(first_row_id), b["scratch"])
+            dead = (running.view(m, 1) & (b["weights"].view(m, R) == 0)).sum()
+            scores, weights = b["final_score"].view(m, Cn, R), b["weights"].view(m, R)
+            value, wsum, n_live, best = search_reduce(scores, weights, (cand >= 0).to(torch.int8))
+            best_uid = torch.where(best >= 0, cand.gather(1, best.long().clamp(min=0).view(m, 1)).view(m), best)
+            res = SearchResult(value, wsum, n_live, best, int(rollouts.item()), turns, dead=int(dead.item()),
+                               replicas=int(running.sum().item()) * R, cand=cand, best_uid=best_uid)
+            if base_slot is not None:
+                res.diff, res.se, res.n_pair = search_compare(scores, weights, cand, base_slot)
+        return res
+
+    @torch.no_grad()
+    def confirm(self, rows, legal, blueprint, draw, baseline, challenger, replicas):
+        """The second stage of screen-then-confirm: re-measure {baseline[i], challenger[i]} (uids, [m] int32) of every root on
+        `replicas` replicas that run() did not see, and compare the two on those alone: slot 0 is the baseline, slot 1 the
+        challenger, diff[:, 1] / se[:, 1] the challenger's paired difference to the baseline. A root plays nothing (both slots
+        -1, diff and se NaN) when it has no challenger (< 0), the challenger is the baseline, either move is illegal, or it is
+        not running. Fresh randomness by construction: the replicas' row ids start behind run()'s (m * self.replicas), the
+        rollout games' ids behind run()'s (first_game_id + m * A * self.replicas)."""
+        r = _rows(rows, self.det.state_words, self.device)
+        dev = r.device
+        m, A = r.shape[0], self.num_actions
+        lg = torch.as_tensor(legal).to(device=dev, dtype=torch.int8).contiguous()
+        if lg.shape != (m, A):
+            raise ValueError(f"legal has shape ({m}, {A}), got {tuple(lg.shape)}")
+        pair = []
+        for name, x in (("baseline", baseline), ("challenger", challenger)):
+            x = torch.as_tensor(x).to(device=dev, dtype=torch.int32).contiguous()
+            if x.shape != (m,):
+                raise ValueError(f"{name} has shape ({m},), got {tuple(x.shape)}")
+            pair.append(x)
+        bl, ch = pair
+        lgb = lg != 0
+        is_legal = lambda u: (u >= 0) & (u < A) & lgb.gather(1, u.long().clamp(0, A - 1).view(m, 1)).view(m)
+        running = ((r[:, 0] >> 19) & 3) == 0
+        ok = running & (ch != bl) & is_legal(bl) & is_legal(ch)
+        cand = torch.where(ok.view(m, 1), torch.stack([bl, ch], 1), -1).int().contiguous()
+        return self.run_candidates(r, cand, lgb.int().argmax(1).int(), blueprint, draw, replicas=replicas,
+                                   first_row_id=m * self.replicas, first_game_id=self.first_game_id + m * A * self.replicas,
+                                   base_slot=torch.zeros(m, dtype=torch.int32, device=dev))
 
 
 class SearchPlayer:
@@ -251,10 +421,24 @@ class SearchPlayer:
     Its move per game is the blueprint's own move b unless value[best] - value[b] > threshold and both have live replicas
     (SPARTA's deviation rule); finished games and roots without a live replica get the blueprint's move. The blueprint's move is
     computed with the caller's seed and draw, exactly as Evaluator.run(blueprint) would; the search uses this player's `seed`
-    and the caller's draw. Counters: `moves` (moves made in live games), `deviations` (those that left the blueprint),
-    `dead_replicas` / `replicas_drawn`."""
+    and the caller's draw.
 
-    def __init__(self, blueprint, seat, replicas=32, threshold=0.0, seed=1, check_every=8):
+    z, confirm_replicas (defaults None, 0: the rule above alone) add a test on the paired difference d of the two moves' scores,
+    replica by replica, and its standard error (hb_search_compare). The challenger is `best` where the rule above holds.
+    confirm_replicas = 0: it is played iff d > z * se on the search's own replicas. confirm_replicas > 0 (screen, then confirm):
+    {b, challenger} are re-measured on that many fresh replicas (RolloutSearch.confirm) and the challenger is played iff
+    d > z * se on those alone (z = None counts as 0 there): the estimate that picked the challenger is not the one that tests
+    it. A standard error that is not finite (fewer than two live replicas) never deviates.
+    z stays None by default. Measured on Full, 2 players, [Piers, Piers], 1 024 games (DESIGN.md section 11f's table,
+    profiles/search/confirm_probe.json): z = 2 is the setting to try first — with both seats searching at 32 replicas it scores
+    19.32 where the threshold alone scores 16.45 (blueprint 17.20), at the same cost; confirm_replicas = 256 with z = 2 scores
+    19.81 for 1.75 times the rollouts, z = 2 at 128 replicas 20.01 for four times.
+
+    Counters: `moves` (moves made in live games), `deviations` (those that left the blueprint), `dead_replicas` /
+    `replicas_drawn` (of the first stage), `confirmed` (challengers that went to the second stage), `rejected` (of those, the
+    ones not played), `rollouts` (games played, both stages)."""
+
+    def __init__(self, blueprint, seat, replicas=32, threshold=0.0, seed=1, check_every=8, z=None, confirm_replicas=0):
         self.blueprint = list(blueprint)
         self.seat = int(seat)
         if not 0 <= self.seat < len(self.blueprint):
@@ -264,9 +448,15 @@ class SearchPlayer:
             if not hasattr(a, "eval_moves"):
                 raise TypeError(f"{type(a).__name__} has no eval_moves()")
         self.replicas, self.threshold, self.seed, self.check_every = int(replicas), float(threshold), int(seed), int(check_every)
+        self.z = None if z is None else float(z)
+        if self.z is not None and not self.z >= 0:
+            raise ValueError(f"z must be >= 0 (or None), got {z}")
+        self.confirm_replicas = int(confirm_replicas)
+        if self.confirm_replicas < 0:
+            raise ValueError(f"confirm_replicas must be >= 0, got {confirm_replicas}")
         self._search = None
-        self._moves = self._dev = None
-        self.dead_replicas = self.replicas_drawn = self.searches = 0
+        self._moves = self._dev = self._confirmed = self._rejected = None
+        self.dead_replicas = self.replicas_drawn = self.searches = self.rollouts = 0
 
     def requires_vectorized_observation(self):
         return self.own.requires_vectorized_observation()
@@ -279,9 +469,21 @@ class SearchPlayer:
     def deviations(self):
         return 0 if self._dev is None else int(self._dev.item())
 
+    @property
+    def confirmed(self):
+        return 0 if self._confirmed is None else int(self._confirmed.item())
+
+    @property
+    def rejected(self):
+        return 0 if self._rejected is None else int(self._rejected.item())
+
     def reset_stats(self):
-        self._moves = self._dev = None
-        self.dead_replicas = self.replicas_drawn = self.searches = 0
+        self._moves = self._dev = self._confirmed = self._rejected = None
+        self.dead_replicas = self.replicas_drawn = self.searches = self.rollouts = 0
+
+    def _significant(self, diff, se, z):
+        """diff > z * se, never with a standard error that is not finite (0 * inf must not pass) or a NaN."""
+        return torch.isfinite(se) & (diff > z * se)
 
     @torch.no_grad()
     def eval_moves(self, observations, seed, draw, actions_out, scratch=None):
@@ -300,17 +502,33 @@ class SearchPlayer:
             self._search = RolloutSearch(config=env.cfg, replicas=self.replicas, seed=self.seed, device=env.device,
                                          check_every=self.check_every)
         rows = env.export_state()
-        res = self._search.run(rows, env.legal, self.blueprint, draw, seat=self.seat)
+        staged = self.z is not None or self.confirm_replicas > 0
+        res = self._search.run(rows, env.legal, self.blueprint, draw, seat=self.seat,
+                               baseline=actions_out if self.z is not None else None)
         live = ((rows[:, 0] >> 19) & 3) == 0
         bp = actions_out.long().clamp(0, env.num_actions - 1).view(-1, 1)
         best = res.best.long().clamp(min=0).view(-1, 1)
         v_bp, v_best = res.value.gather(1, bp), res.value.gather(1, best)
         ok = (res.best.view(-1, 1) >= 0) & (res.n_live.gather(1, bp) > 0) & (res.n_live.gather(1, best) > 0)
         deviate = (ok & ((v_best - v_bp) > self.threshold)).view(-1) & live   # (NaN compares false)
-        actions_out.copy_(torch.where(deviate, res.best, actions_out))
         if self._moves is None:
-            self._moves = torch.zeros((), dtype=torch.int64, device=rows.device)
-            self._dev = torch.zeros((), dtype=torch.int64, device=rows.device)
+            self._moves, self._dev, self._confirmed, self._rejected = (torch.zeros((), dtype=torch.int64, device=rows.device)
+                                                                       for _ in range(4))
+        self.rollouts += res.rollouts
+        if staged:
+            challenger = deviate & (res.best != actions_out)
+            if self.confirm_replicas > 0:
+                deviate = torch.zeros_like(challenger)
+                if bool(challenger.any().item()):   # (nothing to confirm: no second stage)
+                    second = self._search.confirm(rows, env.legal, self.blueprint, draw, actions_out,
+                                                  torch.where(challenger, res.best, -1), self.confirm_replicas)
+                    deviate = challenger & self._significant(second.diff[:, 1], second.se[:, 1], self.z or 0.0)
+                    self.rollouts += second.rollouts
+                self._confirmed += challenger.sum()
+                self._rejected += (challenger & ~deviate).sum()
+            else:
+                deviate = challenger & self._significant(res.diff.gather(1, best).view(-1), res.se.gather(1, best).view(-1), self.z)
+        actions_out.copy_(torch.where(deviate, res.best, actions_out))
         self._moves += live.sum()
         self._dev += deviate.sum()
         self.dead_replicas += res.dead

@@ -799,11 +799,38 @@ int hb_train_tally(const hb_config* cfg, int64_t n_games, int32_t seat, const in
  *   wsum_dev [m, A] int64 = sum w; n_live_dev [m, A] int32 = replicas with w > 0;
  *   best_dev [m] int32 (may be NULL) = the legal action of the largest value, the lowest uid winning ties; -1 when there is none.
  * An action that is illegal at the root, and every action of a root with sum w = 0: value NaN, wsum 0, n_live 0.
- * Both check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                         */
+ * hb_search_layout: the determinized rows laid out as the rollout games of a per-root candidate list. det_rows_dev [m * replicas,
+ * hb_state_words()] and weight_dev [m * replicas] as hb_belief_determinize wrote them, cand_dev [m, n_cand] int32 (an action uid,
+ * or -1: no candidate in this slot), filler_dev [m] int32 (the move that games which are not played make, so that they stay in
+ * lock step with the others: the root's lowest legal uid). Game (i, c, r) = index (i * n_cand + c) * replicas + r gets source row
+ * i * replicas + r: every candidate of a root starts from the same replicas. It is PLAYED iff cand[i, c] >= 0 and
+ * weight[i * replicas + r] != 0:
+ *   rows_out_dev [m * n_cand * replicas, hb_state_words()]; forced_out_dev int32 = cand[i, c] where it is >= 0, else filler[i]
+ *   (a dead replica is an unchanged copy of its root, so the candidate is as legal there; it is not counted);
+ *   done_out_dev uint8 = 0 if played, else 0x80 (hb_eval_tally's "never counted"); n_played_out_dev [m] int32 = the played games
+ *   of root i (one lane writes it, no atomics; the caller sums it into the tally's live count).
+ * 1 <= n_cand <= 64, replicas >= 1, m * n_cand * replicas < 2^31. With n_cand = hb_num_actions() and cand[i, a] = a where a is
+ * legal, -1 elsewhere, this is the [m, A, replicas] layout of RolloutSearch.run.
+ * hb_search_compare: score_dev [m, n_cand, replicas] int8, weight_dev [m, replicas] u32, cand_dev [m, n_cand] int32,
+ * base_slot_dev [m] int32 (the slot of the root's baseline candidate, the blueprint's move; < 0 or >= n_cand: none) -> per slot c
+ * the paired difference to the baseline over the replicas with w_r > 0, d_r = score[i, c, r] - score[i, base, r]:
+ *   diff_dev [m, n_cand] f64 = double(sum w_r d_r) / double(sum w_r), both sums exact in 64-bit integers;
+ *   se_dev [m, n_cand] f64 = sqrt(sum (w_r (d_r - diff))^2) / sum w_r * sqrt(n / (n - 1)), the sum in double over non-negative
+ *   terms (each lane its replicas r = lane, lane + 64, ... in ascending order, then the xor butterfly of the 64 lanes): with
+ *   constant weights — every state reached by play — the textbook s / sqrt(n) of the paired differences; n < 2: +inf;
+ *   n_pair_dev [m] int32 = n = replicas with w_r > 0.
+ * c == base: diff = se = 0. cand[i, c] < 0, no baseline (or cand[i, base] < 0), or sum w = 0: both NaN.
+ * 1 <= n_cand <= 64, 1 <= replicas <= 2^20, m * n_cand * replicas < 2^31.
+ * All four check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                     */
 int hb_belief_determinize(const hb_config* cfg, const uint32_t* src_rows_dev, int64_t m, int32_t seat, int32_t replicas, uint64_t seed,
                           uint64_t draw, int64_t first_row_id, uint32_t* out_rows_dev, uint32_t* weight_dev, void* stream);
 int hb_search_reduce(const int8_t* score_dev, const uint32_t* weight_dev, const int8_t* legal_dev, int64_t m, int32_t n_actions,
                      int32_t replicas, float* value_dev, int64_t* wsum_dev, int32_t* n_live_dev, int32_t* best_dev, void* stream);
+int hb_search_layout(const hb_config* cfg, const uint32_t* det_rows_dev, const uint32_t* weight_dev, const int32_t* cand_dev,
+                     const int32_t* filler_dev, int64_t m, int32_t n_cand, int32_t replicas, uint32_t* rows_out_dev,
+                     int32_t* forced_out_dev, uint8_t* done_out_dev, int32_t* n_played_out_dev, void* stream);
+int hb_search_compare(const int8_t* score_dev, const uint32_t* weight_dev, const int32_t* cand_dev, const int32_t* base_slot_dev,
+                      int64_t m, int32_t n_cand, int32_t replicas, double* diff_dev, double* se_dev, int32_t* n_pair_dev, void* stream);
 
 /* ---- One host call per step: hb_chain_run (csrc/chain.hip, round 3) ------------------------------------------------------
  * The session that drives DQNAgent (rlax_rainbow.py:277-339: explore / add_experience / update once per env step) issues ~25
