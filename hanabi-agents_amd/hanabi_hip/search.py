@@ -17,6 +17,10 @@
   (hb_search_layout builds the [m, C, replicas] games on the device); with `base_slot` it also gives every candidate's paired
   difference to the baseline's score, replica by replica, and that difference's standard error (hb_search_compare).
   `RolloutSearch.confirm` re-measures {blueprint move, challenger} of every root on fresh replicas: screen, then confirm.
+* `ConditionedDeterminizer.sample` conditions that belief on the partner's last move: `replicas * oversample` candidates, the
+  state the partner moved from with each candidate hand spliced in (hb_belief_splice), the partner's `eval_moves` on those with
+  the real turn's Philox keys, and the first `replicas` candidates under which it makes the move it made (hb_belief_select).
+  `history=` hands it to run / run_candidates / confirm; `SearchPlayer(condition=True)` keeps the history itself (2 players).
 * `SearchPlayer` is an agent for `Evaluator.run`: the blueprint's move unless the search finds one that is better by more than
   `threshold` and, with `z` / `confirm_replicas`, by more than z standard errors of the paired difference.
 
@@ -142,6 +146,155 @@ def search_compare(scores, weights, cand, base_slot):
     return diff, se, n_pair
 
 
+def belief_splice(cfg, prev_rows, det_rows, seat, n_cand, out=None):
+    """hb_belief_splice: prev_rows [m, SW] int32, det_rows [m * K, SW] int32 (candidate (i, k) = row i * K + k) ->
+    rows [K, m, SW] int32, candidate-major: slab k = prev_rows with word 10 + seat of every row taken from candidate (i, k)."""
+    m, SW = prev_rows.shape
+    Kn, dev = int(n_cand), prev_rows.device
+    assert prev_rows.dtype == torch.int32 and prev_rows.is_contiguous()
+    assert det_rows.shape == (m * Kn, SW) and det_rows.dtype == torch.int32 and det_rows.is_contiguous()
+    if out is None:
+        out = torch.empty((max(Kn, 0), m, SW), dtype=torch.int32, device=dev)
+    assert out.shape == (Kn, m, SW) and out.dtype == torch.int32 and out.is_contiguous()
+    with torch.cuda.device(dev):
+        K.check(K.lib().hb_belief_splice(C.byref(cfg), K.dptr(prev_rows), K.dptr(det_rows), m, int(seat), Kn, K.dptr(out),
+                                         K.current_stream()))
+    return out
+
+
+def belief_select(cfg, src_rows, det_rows, weights, hyp_moves, actual, valid, replicas, out=None):
+    """hb_belief_select: src_rows [m, SW] int32, det_rows [m * K, SW] int32, weights [m * K] (u32 bits in int32), hyp_moves [K, m]
+    int32, actual [m] int32, valid [m] uint8 or None -> (rows [m * R, SW] int32, weights [m * R] int32, n_surv [m] int32,
+    fallback [m] uint8). `out`: an optional tuple of these four buffers to write into."""
+    m, SW = src_rows.shape
+    Kn, R, dev = hyp_moves.shape[0], int(replicas), src_rows.device
+    assert src_rows.dtype == torch.int32 and src_rows.is_contiguous()
+    assert det_rows.shape == (m * Kn, SW) and det_rows.dtype == torch.int32 and det_rows.is_contiguous()
+    assert weights.shape == (m * Kn,) and weights.dtype == torch.int32 and weights.is_contiguous()
+    assert hyp_moves.shape == (Kn, m) and hyp_moves.dtype == torch.int32 and hyp_moves.is_contiguous()
+    assert actual.shape == (m,) and actual.dtype == torch.int32 and actual.is_contiguous()
+    assert valid is None or (valid.shape == (m,) and valid.dtype == torch.uint8 and valid.is_contiguous())
+    if out is None:
+        out = (torch.empty((m * max(R, 0), SW), dtype=torch.int32, device=dev), torch.empty(m * max(R, 0), dtype=torch.int32, device=dev),
+               torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.uint8, device=dev))
+    rows, w, n_surv, fallback = out
+    assert rows.shape == (m * R, SW) and rows.dtype == torch.int32 and rows.is_contiguous()
+    assert w.shape == (m * R,) and w.dtype == torch.int32 and w.is_contiguous()
+    assert n_surv.shape == (m,) and n_surv.dtype == torch.int32 and n_surv.is_contiguous()
+    assert fallback.shape == (m,) and fallback.dtype == torch.uint8 and fallback.is_contiguous()
+    with torch.cuda.device(dev):
+        K.check(K.lib().hb_belief_select(C.byref(cfg), K.dptr(src_rows), K.dptr(det_rows), K.dptr(weights), K.dptr(hyp_moves),
+                                         K.dptr(actual), K.dptr(valid), m, Kn, R, K.dptr(rows), K.dptr(w), K.dptr(n_surv),
+                                         K.dptr(fallback), K.current_stream()))
+    return rows, w, n_surv, fallback
+
+
+def last_move_uid(cfg, rows):
+    """The uid (App. A.2 order, in the frame of the seat that made it) of the last move recorded in word 2 of each state row
+    (DESIGN.md section 3): [m] int32, -1 where the word's valid bit is 0 (no move yet in this deal)."""
+    r = torch.as_tensor(rows)
+    if r.dim() != 2 or r.shape[1] < 3:
+        raise ValueError(f"state rows have shape [m, state_words], got {tuple(r.shape)}")
+    w2 = r[:, 2].long() & 0xFFFFFFFF
+    H, P, Cn, Rn = cfg.hand_size, cfg.players, cfg.colors, cfg.ranks
+    kind, idx, off = (w2 >> 4) & 3, (w2 >> 6) & 7, ((w2 >> 9) & 7) - 1
+    col, rank = (w2 >> 12) & 7, (w2 >> 15) & 7
+    uid = torch.where(kind == 1, idx, torch.where(kind == 0, H + idx, torch.where(
+        kind == 2, 2 * H + off * Cn + col, 2 * H + (P - 1) * Cn + off * Rn + rank)))
+    return torch.where((w2 & 1) != 0, uid, -1).to(torch.int32)
+
+
+def _history(history, m, words, dev):
+    """(prev_rows, partner_seed, partner_draw, first_game_id[, valid]) checked -> the same with tensors on the device."""
+    if not isinstance(history, (tuple, list)) or len(history) not in (4, 5):
+        raise ValueError("history is (prev_rows, partner_seed, partner_draw, first_game_id[, valid])")
+    prev = torch.as_tensor(history[0])
+    if prev.dim() != 2 or tuple(prev.shape) != (m, words):
+        raise ValueError(f"history's previous rows have shape ({m}, {words}), got {tuple(prev.shape)}")
+    prev = prev.to(device=dev, dtype=torch.int32).contiguous()
+    valid = None
+    if len(history) == 5 and history[4] is not None:
+        valid = torch.as_tensor(history[4])
+        if tuple(valid.shape) != (m,):
+            raise ValueError(f"history's valid mask has shape ({m},), got {tuple(valid.shape)}")
+        valid = (valid.to(dev) != 0).to(torch.uint8).contiguous()
+    return prev, int(history[1]), int(history[2]), int(history[3]), valid
+
+
+class ConditionedDeterminizer:
+    """The V0 belief conditioned on the partner's last move: candidates from `Determinizer`, the previous
+    state with each candidate hand spliced in (hb_belief_splice), the partner's move in each of them (its `eval_moves` on an
+    m-game scratch env, one slab of candidates at a time), and the first `replicas` candidates under which that move is the one
+    the partner made (hb_belief_select). The scratch env and the buffers are kept per (m, K)."""
+
+    def __init__(self, game="Hanabi-Full", players=2, config=None):
+        self.det = Determinizer(game, players, config)
+        self.cfg, self.players, self.state_words = self.det.cfg, self.det.players, self.det.state_words
+        self._sized = {}   # (m, K) -> scratch env and buffers
+        self._scratch = weakref.WeakKeyDictionary()   # agent -> the buffers its eval_moves writes
+
+    def _setup(self, m, Kn, dev):
+        b = self._sized.get((m, Kn))
+        if b is None:
+            self._sized.clear()   # one size at a time
+            SW = self.state_words
+            b = self._sized[(m, Kn)] = dict(
+                env=HanabiEnv(config=self.cfg, n_games=m, device=dev, packed=True),
+                cand_rows=torch.empty((m * Kn, SW), dtype=torch.int32, device=dev),
+                cand_w=torch.empty(m * Kn, dtype=torch.int32, device=dev),
+                hyp_rows=torch.empty((Kn, m, SW), dtype=torch.int32, device=dev),
+                hyp_moves=torch.empty((Kn, m), dtype=torch.int32, device=dev))
+        return b
+
+    @torch.no_grad()
+    def sample(self, rows, prev_rows, partner, seat, replicas, oversample, seed, draw, partner_seed, partner_draw, first_game_id,
+               valid=None, first_row_id=0, out=None):
+        """rows [m, SW] the current states (seat `seat` to act), prev_rows [m, SW] the states the partner moved from, partner:
+        the agent that moved (its eval_moves is called with partner_seed / partner_draw on games first_game_id + i: what it was
+        called with in the real game), valid [m] (0: no usable previous state; the root keeps the unconditioned belief). K =
+        replicas * oversample candidates per root are drawn with (seed, draw) and row ids first_row_id + i * K + k.
+        -> (rows_out [m * replicas, SW] int32, weights [m * replicas] int64, n_surv [m] int32, fallback [m] uint8). `out`: an
+        optional (rows_out, weights_u32) pair to write into (the weights then come back as the int32 buffer)."""
+        r = _rows(rows, self.state_words)
+        m, R, ov = r.shape[0], int(replicas), int(oversample)
+        if R < 1 or ov < 1:
+            raise ValueError(f"replicas and oversample must be >= 1, got {replicas} and {oversample}")
+        if not 0 <= int(seat) < self.players:
+            raise ValueError(f"seat {seat} out of range for {self.players} players")
+        if not hasattr(partner, "eval_moves"):
+            raise TypeError(f"{type(partner).__name__} has no eval_moves()")
+        dev, Kn = r.device, R * ov
+        prev, _, _, _, valid = _history((prev_rows, 0, 0, 0, valid), m, self.state_words, dev)
+        b = self._setup(m, Kn, dev)
+        env = b["env"]
+        with torch.cuda.device(dev):
+            running = ((r[:, 0] >> 19) & 3) == 0
+            usable = running if valid is None else running & (valid != 0)
+            # a root without a usable previous state is never filtered: its slab rows only have to be states the partner's
+            # policy can be run on, and the current row is one
+            prev = torch.where(usable.view(m, 1), prev, r).contiguous()
+            self.det.sample(r, seat=int(seat), replicas=Kn, seed=seed, draw=draw, first_row_id=first_row_id,
+                            out=(b["cand_rows"], b["cand_w"]))
+            belief_splice(self.cfg, prev, b["cand_rows"], int(seat), Kn, out=b["hyp_rows"])
+            env.first_game_id = int(first_game_id)   # (the scratch env never deals: its game ids key the partner's draws only)
+            vec = partner.requires_vectorized_observation()
+            for k in range(Kn):
+                env.import_state(b["hyp_rows"][k])
+                if vec:   # import_state moves the rows only: the acting seat's observation and legal mask are encoded here
+                    env.observe()
+                    partner.eval_moves((env, (env.net_obs, env.legal)), int(partner_seed), int(partner_draw), b["hyp_moves"][k],
+                                       scratch=self._scratch.setdefault(partner, {}))
+                else:
+                    partner.eval_moves(env, int(partner_seed), int(partner_draw), b["hyp_moves"][k])
+            res = belief_select(self.cfg, r, b["cand_rows"], b["cand_w"], b["hyp_moves"], last_move_uid(self.cfg, r),
+                                usable.to(torch.uint8), R,
+                                out=None if out is None else (out[0], out[1], torch.empty(m, dtype=torch.int32, device=dev),
+                                                              torch.empty(m, dtype=torch.uint8, device=dev)))
+        if out is not None:
+            return res
+        return res[0], res[1].long() & 0xFFFFFFFF, res[2], res[3]
+
+
 class SearchResult:
     """value [m, A] f32 (NaN: illegal at the root, or no live replica), wsum [m, A] int64, n_live [m, A] int32, best [m] int32
     (-1: no action has a value), rollouts = games played, turns = turns of the longest rollout, dead = replicas of weight 0
@@ -149,13 +302,15 @@ class SearchResult:
     int32 the uids searched, `best` the best slot and `best_uid` [m] int32 its uid (-1: none). With a baseline: `diff` [m, C] f64
     the weighted mean over the replicas of score[slot] - score[baseline], `se` [m, C] f64 its standard error (inf with fewer
     than two live replicas; both 0 in the baseline's slot, NaN where there is no candidate, no baseline or no live replica) and
-    `n_pair` [m] int32 the live replicas (hb_search_compare). None when not computed."""
+    `n_pair` [m] int32 the live replicas (hb_search_compare). None when not computed. With `history` (the belief conditioned on
+    the partner's last move): `n_surv` [m] int32 and `fallback` [m] uint8 of hb_belief_select; None without."""
 
     def __init__(self, value, wsum, n_live, best, rollouts, turns, dead=0, replicas=0, diff=None, se=None, n_pair=None, cand=None,
-                 best_uid=None):
+                 best_uid=None, n_surv=None, fallback=None):
         self.value, self.wsum, self.n_live, self.best = value, wsum, n_live, best
         self.rollouts, self.turns, self.dead, self.replicas = int(rollouts), int(turns), int(dead), int(replicas)
         self.diff, self.se, self.n_pair, self.cand, self.best_uid = diff, se, n_pair, cand, best_uid
+        self.n_surv, self.fallback = n_surv, fallback
 
     def __repr__(self):
         return f"SearchResult(roots={self.value.shape[0]}, rollouts={self.rollouts}, turns={self.turns})"
@@ -198,9 +353,15 @@ class RolloutSearch:
 
     first_game_id: global id of rollout game 0 (keys the blueprint's draws, like Evaluator's). The rollout env and every
     buffer are built by the first run() of a size and kept for the next; run_candidates() keeps its own per (m, C, replicas),
-    so that a screening stage's env survives the confirming stage's."""
+    so that a screening stage's env survives the confirming stage's.
 
-    def __init__(self, game="Hanabi-Full", players=2, replicas=32, seed=1, device=None, config=None, check_every=8, first_game_id=0):
+    history = (prev_rows, partner_seed, partner_draw, first_game_id[, valid]) to run / run_candidates / confirm: the replicas
+    come from `ConditionedDeterminizer` (the belief conditioned on the last move, made from prev_rows by the seat before the
+    roots' current player with those Philox keys) with `oversample` candidates per replica; everything after the
+    determinization is the same."""
+
+    def __init__(self, game="Hanabi-Full", players=2, replicas=32, seed=1, device=None, config=None, check_every=8, first_game_id=0,
+                 oversample=8):
         self.cfg = _config(game, players, config)
         self.players = self.cfg.players
         self.replicas = int(replicas)
@@ -211,6 +372,10 @@ class RolloutSearch:
         self.device = device
         self.check_every = max(1, int(check_every))
         self.det = Determinizer(config=self.cfg)
+        self.oversample = int(oversample)
+        if self.oversample < 1:
+            raise ValueError(f"oversample must be >= 1, got {oversample}")
+        self.cdet = None   # ConditionedDeterminizer, built by the first search with a history
         self.num_actions = K.lib().hb_num_actions(C.byref(self.cfg))
         self.n_counters = K.lib().hb_eval_counters(C.byref(self.cfg))
         self._sized = {}   # m -> buffers of that size
@@ -284,11 +449,22 @@ class RolloutSearch:
             res.se, res.n_pair = res.diff.clone(), torch.zeros(m, dtype=torch.int32, device=dev)
         return res
 
-    def _play(self, b, r, cand, filler, R, cp, blueprint, draw, first_row_id, scratch):
+    def _play(self, b, r, cand, filler, R, cp, blueprint, draw, first_row_id, scratch, history=None):
         """Determinize the roots `r` R times, lay the replicas out as [m, C, R] games of b's env (hb_search_layout) and play them
-        to the end. Leaves the final scores in b["final_score"]; returns (games played as a device scalar, turns)."""
+        to the end. Leaves the final scores in b["final_score"]; returns (games played as a device scalar, turns, n_surv,
+        fallback), the last two None without a history."""
         env = b["env"]
-        self.det.sample(r, seat=cp, replicas=R, seed=self.seed, draw=draw, first_row_id=first_row_id, out=(b["det_rows"], b["weights"]))
+        n_surv = fallback = None
+        if history is None:
+            self.det.sample(r, seat=cp, replicas=R, seed=self.seed, draw=draw, first_row_id=first_row_id,
+                            out=(b["det_rows"], b["weights"]))
+        else:
+            prev, p_seed, p_draw, gid, valid = history
+            if self.cdet is None:
+                self.cdet = ConditionedDeterminizer(config=self.cfg)
+            _, _, n_surv, fallback = self.cdet.sample(r, prev, blueprint[(cp - 1) % self.players], cp, R, self.oversample, self.seed,
+                                                      draw, p_seed, p_draw, gid, valid=valid, first_row_id=first_row_id,
+                                                      out=(b["det_rows"], b["weights"]))
         # [m, C, R]: block c of root i holds the same R replicas. A slot without a candidate (an illegal action, in run()) is
         # never counted (done up front); its games move in step with the others on the root's filler move, so that no illegal
         # move reaches the env
@@ -305,17 +481,20 @@ class RolloutSearch:
         illegal = env.illegal_count() - illegal0
         if illegal:
             raise RuntimeError(f"{illegal} illegal moves in the rollouts (a candidate that is illegal at its root, or the blueprint's)")
-        return rollouts, turns
+        return rollouts, turns, n_surv, fallback
 
     @torch.no_grad()
-    def run(self, rows, legal, blueprint, draw, seat=None, baseline=None):
+    def run(self, rows, legal, blueprint, draw, seat=None, baseline=None, history=None):
         """rows [m, state_words] int32 state rows (hb_env_export_state), legal [m, A] int8 the legal mask of each root's seat to
         act, blueprint: one agent per seat with eval_moves, draw: Philox draw of the determinization (with the search's seed).
         All running roots must have the same current player (`seat`, when given, must be that player). baseline: optional [m]
-        int32 uids (the blueprint's moves): the result's diff / se / n_pair are then every action's paired difference to it."""
+        int32 uids (the blueprint's moves): the result's diff / se / n_pair are then every action's paired difference to it.
+        history: see the class docstring."""
         r, blueprint, running, cps = self._roots(rows, blueprint, seat)
         dev = r.device
         m, A, R = r.shape[0], self.num_actions, self.replicas
+        if history is not None:
+            history = _history(history, m, self.det.state_words, dev)
         lg = torch.as_tensor(legal).to(device=dev, dtype=torch.int8).contiguous()
         if lg.shape != (m, A):
             raise ValueError(f"legal has shape ({m}, {A}), got {tuple(lg.shape)}")
@@ -331,26 +510,30 @@ class RolloutSearch:
             lgb = lg != 0
             cand = torch.where(lgb, b["uid"], -1).int().contiguous()
             filler = lgb.int().argmax(1).int()   # the root's lowest legal uid
-            rollouts, turns = self._play(b, r, cand, filler, R, cp, blueprint, draw, 0, self._scratch)
+            rollouts, turns, n_surv, fallback = self._play(b, r, cand, filler, R, cp, blueprint, draw, 0, self._scratch, history)
             dead = (running.view(m, 1) & (b["weights"].view(m, R) == 0)).sum()
             value, wsum, n_live, best = search_reduce(b["final_score"].view(m, A, R), b["weights"].view(m, R), lg)
             res = SearchResult(value, wsum, n_live, best, int(rollouts.item()), turns, dead=int(dead.item()),
-                               replicas=int(running.sum().item()) * R)
+                               replicas=int(running.sum().item()) * R, n_surv=n_surv, fallback=fallback)
             if baseline is not None:   # (slot = uid here)
                 res.diff, res.se, res.n_pair = search_compare(b["final_score"].view(m, A, R), b["weights"].view(m, R), cand, baseline)
         return res
 
     @torch.no_grad()
-    def run_candidates(self, rows, cand, filler, blueprint, draw, replicas=None, first_row_id=0, first_game_id=None, base_slot=None):
+    def run_candidates(self, rows, cand, filler, blueprint, draw, replicas=None, first_row_id=0, first_game_id=None, base_slot=None,
+                       history=None):
         """run() over a candidate list: cand [m, C] int32 (C <= 64) holds the uids to play first at each root (-1: no candidate
         in this slot; a candidate must be legal at its root), filler [m] int32 the move that the games of empty slots make (the
         root's lowest legal uid). replicas: per candidate (default: the search's); first_row_id: row id of replica 0 of root 0
         (keys the determinization, with the search's seed and `draw`); first_game_id: game id of rollout game 0 (default: the
         search's). The result's second axis is the slot: `best` is the best slot, `best_uid` its uid, `cand` the list. base_slot:
-        optional [m] int32 slot of each root's baseline (-1: none): fills diff / se / n_pair (hb_search_compare)."""
+        optional [m] int32 slot of each root's baseline (-1: none): fills diff / se / n_pair (hb_search_compare). history: see
+        the class docstring (the candidates' row ids then start at first_row_id and take replicas * oversample per root)."""
         r, blueprint, running, cps = self._roots(rows, blueprint, None)
         dev = r.device
         m = r.shape[0]
+        if history is not None:
+            history = _history(history, m, self.det.state_words, dev)
         R = self.replicas if replicas is None else int(replicas)
         if R < 1:
             raise ValueError(f"replicas must be >= 1, got {replicas}")
@@ -371,25 +554,27 @@ class RolloutSearch:
             return self._nothing(m, Cn, dev, cand=cand, compared=base_slot is not None)
         cp = int(cps[0])
         with torch.cuda.device(dev):
-            rollouts, turns = self._play(b, r, cand, filler, R, cp, blueprint, draw, int(first_row_id), b["scratch"])
+            rollouts, turns, n_surv, fallback = self._play(b, r, cand, filler, R, cp, blueprint, draw, int(first_row_id), b["scratch"],
+                                                           history)
             dead = (running.view(m, 1) & (b["weights"].view(m, R) == 0)).sum()
             scores, weights = b["final_score"].view(m, Cn, R), b["weights"].view(m, R)
             value, wsum, n_live, best = search_reduce(scores, weights, (cand >= 0).to(torch.int8))
             best_uid = torch.where(best >= 0, cand.gather(1, best.long().clamp(min=0).view(m, 1)).view(m), best)
             res = SearchResult(value, wsum, n_live, best, int(rollouts.item()), turns, dead=int(dead.item()),
-                               replicas=int(running.sum().item()) * R, cand=cand, best_uid=best_uid)
+                               replicas=int(running.sum().item()) * R, cand=cand, best_uid=best_uid, n_surv=n_surv, fallback=fallback)
             if base_slot is not None:
                 res.diff, res.se, res.n_pair = search_compare(scores, weights, cand, base_slot)
         return res
 
     @torch.no_grad()
-    def confirm(self, rows, legal, blueprint, draw, baseline, challenger, replicas):
+    def confirm(self, rows, legal, blueprint, draw, baseline, challenger, replicas, history=None):
         """The second stage of screen-then-confirm: re-measure {baseline[i], challenger[i]} (uids, [m] int32) of every root on
         `replicas` replicas that run() did not see, and compare the two on those alone: slot 0 is the baseline, slot 1 the
         challenger, diff[:, 1] / se[:, 1] the challenger's paired difference to the baseline. A root plays nothing (both slots
         -1, diff and se NaN) when it has no challenger (< 0), the challenger is the baseline, either move is illegal, or it is
         not running. Fresh randomness by construction: the replicas' row ids start behind run()'s (m * self.replicas), the
-        rollout games' ids behind run()'s (first_game_id + m * A * self.replicas)."""
+        rollout games' ids behind run()'s (first_game_id + m * A * self.replicas). With a history the row ids start behind run()'s
+        candidates instead (m * self.replicas * self.oversample)."""
         r = _rows(rows, self.det.state_words, self.device)
         dev = r.device
         m, A = r.shape[0], self.num_actions
@@ -409,8 +594,9 @@ class RolloutSearch:
         ok = running & (ch != bl) & is_legal(bl) & is_legal(ch)
         cand = torch.where(ok.view(m, 1), torch.stack([bl, ch], 1), -1).int().contiguous()
         return self.run_candidates(r, cand, lgb.int().argmax(1).int(), blueprint, draw, replicas=replicas,
-                                   first_row_id=m * self.replicas, first_game_id=self.first_game_id + m * A * self.replicas,
-                                   base_slot=torch.zeros(m, dtype=torch.int32, device=dev))
+                                   first_row_id=m * self.replicas * (1 if history is None else self.oversample),
+                                   first_game_id=self.first_game_id + m * A * self.replicas,
+                                   base_slot=torch.zeros(m, dtype=torch.int32, device=dev), history=history)
 
 
 class SearchPlayer:
@@ -434,11 +620,23 @@ class SearchPlayer:
     19.32 where the threshold alone scores 16.45 (blueprint 17.20), at the same cost; confirm_replicas = 256 with z = 2 scores
     19.81 for 1.75 times the rollouts, z = 2 at 128 replicas 20.01 for four times.
 
+    condition=True (2 players; default False): the belief of every stage is conditioned on the partner's last move
+    (ConditionedDeterminizer, `oversample` candidates per replica). After each call the player remembers
+    the rows it searched and the move it finally played; on the next call it rebuilds the state the partner moved from (those
+    rows stepped with that move in a scratch env) and hands it to the search with the caller's seed and draw - 1 — what the
+    partner's eval_moves was called with —, assuming the partner plays blueprint[partner] on the caller's random stream. A root
+    is conditioned only if the remembered call was on the same env object at draw - 2, the game was running then and is
+    running now, and word 2 of its row names the partner as the last mover; every other root (a seat's first move of a game
+    among them) is searched unconditioned.
+
     Counters: `moves` (moves made in live games), `deviations` (those that left the blueprint), `dead_replicas` /
     `replicas_drawn` (of the first stage), `confirmed` (challengers that went to the second stage), `rejected` (of those, the
-    ones not played), `rollouts` (games played, both stages)."""
+    ones not played), `rollouts` (games played, both stages); with condition=True, of the first stage: `conditioned` (live roots
+    searched with the filter), `unconditioned` (live roots without), `survivors` / `candidates` (sums over the conditioned
+    roots), `fallbacks` (conditioned roots without a survivor)."""
 
-    def __init__(self, blueprint, seat, replicas=32, threshold=0.0, seed=1, check_every=8, z=None, confirm_replicas=0):
+    def __init__(self, blueprint, seat, replicas=32, threshold=0.0, seed=1, check_every=8, z=None, confirm_replicas=0,
+                 condition=False, oversample=8):
         self.blueprint = list(blueprint)
         self.seat = int(seat)
         if not 0 <= self.seat < len(self.blueprint):
@@ -454,8 +652,16 @@ class SearchPlayer:
         self.confirm_replicas = int(confirm_replicas)
         if self.confirm_replicas < 0:
             raise ValueError(f"confirm_replicas must be >= 0, got {confirm_replicas}")
+        self.condition, self.oversample = bool(condition), int(oversample)
+        if self.oversample < 1:
+            raise ValueError(f"oversample must be >= 1, got {oversample}")
+        if self.condition and len(self.blueprint) != 2:
+            raise ValueError(f"condition=True is built for 2 players, got {len(self.blueprint)}")
         self._search = None
-        self._moves = self._dev = self._confirmed = self._rejected = None
+        self.last_result = None   # the SearchResult of the last call's first stage
+        self._memory = None    # condition: (env, draw, rows, moves played) of the last call
+        self._prev_env = None  # condition: the scratch env that rebuilds the partner's state
+        self._moves = self._dev = self._confirmed = self._rejected = self._cond = None
         self.dead_replicas = self.replicas_drawn = self.searches = self.rollouts = 0
 
     def requires_vectorized_observation(self):
@@ -477,9 +683,37 @@ class SearchPlayer:
     def rejected(self):
         return 0 if self._rejected is None else int(self._rejected.item())
 
+    def _cond_counter(self, j):
+        return 0 if self._cond is None else int(self._cond[j].item())
+
+    conditioned = property(lambda self: self._cond_counter(0))
+    unconditioned = property(lambda self: self._cond_counter(1))
+    survivors = property(lambda self: self._cond_counter(2))
+    candidates = property(lambda self: self._cond_counter(3))
+    fallbacks = property(lambda self: self._cond_counter(4))
+
     def reset_stats(self):
-        self._moves = self._dev = self._confirmed = self._rejected = None
+        self._moves = self._dev = self._confirmed = self._rejected = self._cond = None
         self.dead_replicas = self.replicas_drawn = self.searches = self.rollouts = 0
+
+    def _previous(self, env, rows, draw):
+        """history for this call: the remembered rows stepped with the remembered moves, and which roots that is usable for."""
+        m, dev = rows.shape[0], rows.device
+        partner = 1 - self.seat
+        mem = self._memory
+        if mem is None or mem[0]() is not env or mem[1] != int(draw) - 2 or mem[2].shape != rows.shape:
+            return rows, torch.zeros(m, dtype=torch.uint8, device=dev)
+        _, _, then_rows, then_moves = mem
+        pe = self._prev_env
+        if pe is None or pe.n != m or pe.device != dev or pe.cfg.players != env.cfg.players:
+            pe = self._prev_env = HanabiEnv(config=_config(None, None, env.cfg), n_games=m, device=dev, packed=True)
+        pe.import_state(then_rows)
+        pe.step(then_moves)
+        prev = pe.export_state()
+        w2 = rows[:, 2]
+        valid = ((((then_rows[:, 0] >> 19) & 3) == 0) & (((rows[:, 0] >> 19) & 3) == 0) & ((w2 & 1) != 0) & (((w2 >> 1) & 7) == partner)
+                 & (((prev[:, 0] >> 19) & 3) == 0) & (((prev[:, 0] >> 13) & 7) == partner))
+        return prev, valid.to(torch.uint8)
 
     def _significant(self, diff, se, z):
         """diff > z * se, never with a standard error that is not finite (0 * inf must not pass) or a NaN."""
@@ -498,13 +732,20 @@ class SearchPlayer:
             self.own.eval_moves(observations, seed, draw, actions_out, scratch=scratch)
         else:
             self.own.eval_moves(env, seed, draw, actions_out)
+        if self.condition and env.cfg.players != 2:
+            raise ValueError(f"condition=True is built for 2 players, the env has {env.cfg.players}")
         if self._search is None or self._search.cfg.players != env.cfg.players:
             self._search = RolloutSearch(config=env.cfg, replicas=self.replicas, seed=self.seed, device=env.device,
-                                         check_every=self.check_every)
+                                         check_every=self.check_every, oversample=self.oversample)
         rows = env.export_state()
         staged = self.z is not None or self.confirm_replicas > 0
+        history = None
+        if self.condition:
+            prev, valid = self._previous(env, rows, draw)
+            history = (prev, int(seed), int(draw) - 1, env.first_game_id, valid)
         res = self._search.run(rows, env.legal, self.blueprint, draw, seat=self.seat,
-                               baseline=actions_out if self.z is not None else None)
+                               baseline=actions_out if self.z is not None else None, history=history)
+        self.last_result = res
         live = ((rows[:, 0] >> 19) & 3) == 0
         bp = actions_out.long().clamp(0, env.num_actions - 1).view(-1, 1)
         best = res.best.long().clamp(min=0).view(-1, 1)
@@ -521,7 +762,7 @@ class SearchPlayer:
                 deviate = torch.zeros_like(challenger)
                 if bool(challenger.any().item()):   # (nothing to confirm: no second stage)
                     second = self._search.confirm(rows, env.legal, self.blueprint, draw, actions_out,
-                                                  torch.where(challenger, res.best, -1), self.confirm_replicas)
+                                                  torch.where(challenger, res.best, -1), self.confirm_replicas, history=history)
                     deviate = challenger & self._significant(second.diff[:, 1], second.se[:, 1], self.z or 0.0)
                     self.rollouts += second.rollouts
                 self._confirmed += challenger.sum()
@@ -529,6 +770,14 @@ class SearchPlayer:
             else:
                 deviate = challenger & self._significant(res.diff.gather(1, best).view(-1), res.se.gather(1, best).view(-1), self.z)
         actions_out.copy_(torch.where(deviate, res.best, actions_out))
+        if self.condition:
+            self._memory = (weakref.ref(env), int(draw), rows, actions_out.clone())
+            if res.fallback is not None:   # (None: no root was running)
+                if self._cond is None:
+                    self._cond = torch.zeros(5, dtype=torch.int64, device=rows.device)
+                filtered = live & (res.fallback != 2)
+                self._cond += torch.stack([filtered.sum(), (live & (res.fallback == 2)).sum(), (res.n_surv * filtered).sum(),
+                                           filtered.sum() * (self.replicas * self.oversample), (filtered & (res.fallback == 1)).sum()])
         self._moves += live.sum()
         self._dev += deviate.sum()
         self.dead_replicas += res.dead

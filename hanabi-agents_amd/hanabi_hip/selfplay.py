@@ -417,12 +417,14 @@ class SelfPlaySession:
                                                    device=self.env.device, color_shuffle=color_shuffle)
         return ev.run(self.agents if partners is None else partners)
 
-    def search(self, blueprint=None, replicas=32, seed=1, draw=None):
+    def search(self, blueprint=None, replicas=32, seed=1, draw=None, history=None, oversample=8):
         """Belief-sampled rollout search (hanabi_hip.search) from the session env's current states: a
         SearchResult with the value of every move of the seat to act in every game, should it be played now and everybody follow
         `blueprint` (one agent per seat; default: the session's agents) afterwards. `draw` keys the determinization (default:
         the number of env steps taken). As evaluate(): updates in flight are completed first, and the session, its env and its
-        agents are left exactly as they were. The RolloutSearch (its env and buffers) is kept for the next call."""
+        agents are left exactly as they were. The RolloutSearch (its env and buffers) is kept for the next call. history =
+        (prev_rows, partner_seed, partner_draw, first_game_id[, valid]): the belief is conditioned on the last move
+        (RolloutSearch's docstring), with `oversample` candidates per replica."""
         if blueprint is None and self.pool is not None:
             raise ValueError("a session with a partner pool has no single team: pass the blueprint (one agent per seat)")
         if getattr(self.env, "color_shuffled", False):
@@ -437,8 +439,9 @@ class SelfPlaySession:
             # (data-parallel: each rank's rollout games get their own ids, as its env's games have)
             rs = self._searches[key] = RolloutSearch(config=self.env.cfg, replicas=replicas, seed=seed, device=self.env.device,
                                                      first_game_id=self.env.first_game_id * self.env.num_actions * int(replicas))
+        rs.oversample = max(1, int(oversample))
         return rs.run(self.env.export_state(), self.env.legal.clone(), self.agents if blueprint is None else blueprint,
-                      self.env_steps if draw is None else int(draw))
+                      self.env_steps if draw is None else int(draw), history=history)
 
     def crossplay(self, pool, n_games=4096, seed=1, teams=None, color_shuffle=False):
         """Cross-play of a pool of agents (the session's own and others, DQN and rule-based mixed) on `n_games` fresh deals keyed

@@ -821,7 +821,28 @@ int hb_train_tally(const hb_config* cfg, int64_t n_games, int32_t seat, const in
  *   n_pair_dev [m] int32 = n = replicas with w_r > 0.
  * c == base: diff = se = 0. cand[i, c] < 0, no baseline (or cand[i, base] < 0), or sum w = 0: both NaN.
  * 1 <= n_cand <= 64, 1 <= replicas <= 2^20, m * n_cand * replicas < 2^31.
- * All four check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                     */
+ * hb_belief_splice: "what the partner would have seen". prev_rows_dev [m, hb_state_words()] the states the last mover moved from,
+ * det_rows_dev [m * n_cand, SW] hb_belief_determinize's candidates for the observer `seat` (candidate (i, k) = row i * n_cand + k).
+ * out_rows_dev [n_cand * m, SW], candidate-major: row k * m + i = prev row i with ONLY word 10 + seat (the observer's hand word)
+ * replaced by that word of candidate (i, k); knowledge, deck bytes and everything else stay the previous state's (another seat's
+ * observation and legal mask read the observer's cards, the public state and the deck size, never the deck's order). Slab k is m
+ * contiguous rows in the roots' order: it imports into an m-game env whose game ids are the real games'. seat in 0 .. players - 1
+ * (no -1: the observer is not the previous state's current player). A pure copy: finished rows are spliced like any other.
+ * hb_belief_select: keep the first `replicas` candidates under which the last mover's policy plays the move it played.
+ * src_rows_dev [m, SW] the current states, det_rows_dev [m * n_cand, SW] / weight_dev [m * n_cand] u32 the candidates,
+ * hyp_moves_dev [n_cand * m] int32 (candidate-major: [k * m + i] = the move under candidate (i, k)), actual_dev [m] int32 the
+ * move made, valid_dev [m] u8 or NULL (all valid). Candidate (i, k) SURVIVES iff weight[i, k] != 0 and hyp[k, i] == actual[i].
+ * Per root, candidates in ascending k:
+ *   n_surv_dev [m] int32 = survivors among all n_cand; the j-th survivor (j < replicas) becomes output replica i * replicas + j:
+ *   its determinized row copied whole into out_rows_dev [m * replicas, SW], its weight into out_weight_dev [m * replicas] u32;
+ *   0 < n_surv < replicas: replicas j >= n_surv get weight 0 and an unchanged copy of src row i (the dead-replica convention);
+ *   n_surv == 0: fallback_dev [m] u8 = 1 and the outputs are candidates 0 .. replicas - 1 with their own weights (the
+ *   unconditioned belief: a policy the partner does not follow must not leave the searcher without one);
+ *   a root that is not running (status bits of src word 0) or has valid[i] == 0: the same outputs, fallback = 2, n_surv = 0,
+ *   hyp and actual are not read for it. Otherwise fallback = 0.
+ * One wavefront per root, candidates 64 at a time: a ballot of the predicate, a prefix popcount and a running base give each
+ * survivor its rank; no atomics, no LDS, a pure function of the inputs. n_cand >= replicas >= 1, m * n_cand * SW < 2^31.
+ * All six check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                      */
 int hb_belief_determinize(const hb_config* cfg, const uint32_t* src_rows_dev, int64_t m, int32_t seat, int32_t replicas, uint64_t seed,
                           uint64_t draw, int64_t first_row_id, uint32_t* out_rows_dev, uint32_t* weight_dev, void* stream);
 int hb_search_reduce(const int8_t* score_dev, const uint32_t* weight_dev, const int8_t* legal_dev, int64_t m, int32_t n_actions,
@@ -831,6 +852,12 @@ int hb_search_layout(const hb_config* cfg, const uint32_t* det_rows_dev, const u
                      int32_t* forced_out_dev, uint8_t* done_out_dev, int32_t* n_played_out_dev, void* stream);
 int hb_search_compare(const int8_t* score_dev, const uint32_t* weight_dev, const int32_t* cand_dev, const int32_t* base_slot_dev,
                       int64_t m, int32_t n_cand, int32_t replicas, double* diff_dev, double* se_dev, int32_t* n_pair_dev, void* stream);
+int hb_belief_splice(const hb_config* cfg, const uint32_t* prev_rows_dev, const uint32_t* det_rows_dev, int64_t m, int32_t seat,
+                     int32_t n_cand, uint32_t* out_rows_dev, void* stream);
+int hb_belief_select(const hb_config* cfg, const uint32_t* src_rows_dev, const uint32_t* det_rows_dev, const uint32_t* weight_dev,
+                     const int32_t* hyp_moves_dev, const int32_t* actual_dev, const uint8_t* valid_dev, int64_t m, int32_t n_cand,
+                     int32_t replicas, uint32_t* out_rows_dev, uint32_t* out_weight_dev, int32_t* n_surv_dev, uint8_t* fallback_dev,
+                     void* stream);
 
 /* ---- One host call per step: hb_chain_run (csrc/chain.hip, round 3) ------------------------------------------------------
  * The session that drives DQNAgent (rlax_rainbow.py:277-339: explore / add_experience / update once per env step) issues ~25
