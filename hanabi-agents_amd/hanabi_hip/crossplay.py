@@ -33,7 +33,7 @@ import torch
 
 from . import _capi as K
 from .env import HanabiEnv
-from .evaluate import EvalResult, max_turns, shuffle_mask
+from .evaluate import EvalResult, eval_config, max_turns, shuffle_mask
 
 TILE = 128   # rows per workgroup of the one-kernel actor, and per hb_fused_tile
 
@@ -148,12 +148,7 @@ class CrossPlay:
             raise ValueError(f"n_games must be >= 1, got {n_games}")
         if int(max_rows) < 1:
             raise ValueError(f"max_rows must be >= 1, got {max_rows}")
-        if config is not None:
-            cfg = K.HbConfig(config.players, config.colors, config.ranks, config.hand_size, config.max_info, config.max_life, 0)
-        else:
-            cfg = K.make_config(game, players, 0)
-        if K.lib().hb_config_validate(C.byref(cfg)) != 0:
-            raise ValueError(f"invalid configuration {cfg!r}: {K.lib().hb_last_error().decode()}")
+        cfg = eval_config(game, players, config)
         self.cfg = cfg
         self.players = cfg.players
         self.n = n_games

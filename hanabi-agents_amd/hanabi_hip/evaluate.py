@@ -47,6 +47,18 @@ def max_turns(cfg):
     return draws + (cfg.max_info + draws + cfg.colors) + cfg.players
 
 
+def eval_config(game, players, config=None):
+    """The configuration of games played to the end: the preset `game` / `players`, or `config` with its flags dropped (no
+    auto-reset, scores without leniency). Validated: ValueError on a bad one."""
+    if config is not None:
+        cfg = K.HbConfig(config.players, config.colors, config.ranks, config.hand_size, config.max_info, config.max_life, 0)
+    else:
+        cfg = K.make_config(game, players, 0)
+    if K.lib().hb_config_validate(C.byref(cfg)) != 0:
+        raise ValueError(f"invalid configuration {cfg!r}: {K.lib().hb_last_error().decode()}")
+    return cfg
+
+
 MOVE_KINDS = ("discard", "play", "reveal_color", "reveal_rank")
 
 
@@ -133,12 +145,7 @@ class Evaluator:
         if n_games < 1:
             raise ValueError(f"n_games must be >= 1, got {n_games}")
         self.color_shuffle = bool(color_shuffle)
-        if config is not None:
-            cfg = K.HbConfig(config.players, config.colors, config.ranks, config.hand_size, config.max_info, config.max_life, 0)
-        else:
-            cfg = K.make_config(game, players, 0)
-        if K.lib().hb_config_validate(C.byref(cfg)) != 0:
-            raise ValueError(f"invalid configuration {cfg!r}: {K.lib().hb_last_error().decode()}")
+        cfg = eval_config(game, players, config)
         self.cfg = cfg
         self.players = cfg.players
         self.n = n_games

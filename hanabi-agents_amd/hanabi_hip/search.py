@@ -17,6 +17,8 @@
   (hb_search_layout builds the [m, C, replicas] games on the device); with `base_slot` it also gives every candidate's paired
   difference to the baseline's score, replica by replica, and that difference's standard error (hb_search_compare).
   `RolloutSearch.confirm` re-measures {blueprint move, challenger} of every root on fresh replicas: screen, then confirm.
+  There is one rollout path: `run` is `run_candidates` with every legal action as the candidate of slot = uid, and both go
+  through one cache of rollout envs and buffers keyed (m, C, replicas).
 * `ConditionedDeterminizer.sample` conditions that belief on the partner's last move: `replicas * oversample` candidates, the
   state the partner moved from with each candidate hand spliced in (hb_belief_splice), the partner's `eval_moves` on those with
   the real turn's Philox keys, and the first `replicas` candidates under which it makes the move it made (hb_belief_select).
@@ -33,17 +35,7 @@ import torch
 
 from . import _capi as K
 from .env import HanabiEnv
-from .evaluate import max_turns
-
-
-def _config(game, players, config):
-    if config is not None:
-        cfg = K.HbConfig(config.players, config.colors, config.ranks, config.hand_size, config.max_info, config.max_life, 0)
-    else:
-        cfg = K.make_config(game, players, 0)
-    if K.lib().hb_config_validate(C.byref(cfg)) != 0:
-        raise ValueError(f"invalid configuration {cfg!r}: {K.lib().hb_last_error().decode()}")
-    return cfg
+from .evaluate import eval_config, max_turns
 
 
 def _rows(rows, words, device=None):
@@ -56,11 +48,32 @@ def _rows(rows, words, device=None):
     return r
 
 
+def _bufs(dev, given, *specs):
+    """One tensor per (shape, dtype) of `specs`: the caller's `given` ones, each checked (shape, dtype, contiguous), or, with
+    `given` None, new ones on `dev`. The kernels index what they are handed by these shapes alone."""
+    if given is None:
+        return tuple(torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in specs)
+    assert len(given) == len(specs)
+    for t, (shape, dtype) in zip(given, specs):
+        assert t.shape == tuple(shape) and t.dtype == dtype and t.is_contiguous(), \
+            f"expected a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}"
+    return tuple(given)
+
+
+def _ask(agent, env, seed, draw, out, scratch):
+    """agent.eval_moves on the env's current states (observed, for an agent that reads observations) -> out. scratch: agent ->
+    the buffers its eval_moves writes."""
+    if agent.requires_vectorized_observation():
+        agent.eval_moves((env, (env.net_obs, env.legal)), seed, draw, out, scratch=scratch.setdefault(agent, {}))
+    else:
+        agent.eval_moves(env, seed, draw, out)
+
+
 class Determinizer:
     """hb_belief_determinize on torch tensors; see the module docstring and include/hanabi_hip.h."""
 
     def __init__(self, game="Hanabi-Full", players=2, config=None):
-        self.cfg = _config(game, players, config)
+        self.cfg = eval_config(game, players, config)
         self.players = self.cfg.players
         self.state_words = K.lib().hb_state_words(C.byref(self.cfg))
 
@@ -70,13 +83,8 @@ class Determinizer:
         optional (rows_out, weights_u32) pair of buffers to write into (weights int32 holding the u32 bits)."""
         r = _rows(rows, self.state_words)
         m, replicas = r.shape[0], int(replicas)
-        if out is None:
-            rows_out = torch.empty((m * max(replicas, 0), self.state_words), dtype=torch.int32, device=r.device)
-            w = torch.empty(m * max(replicas, 0), dtype=torch.int32, device=r.device)
-        else:
-            rows_out, w = out
-            assert rows_out.shape == (m * replicas, self.state_words) and rows_out.dtype == torch.int32 and rows_out.is_contiguous()
-            assert w.shape == (m * replicas,) and w.dtype == torch.int32 and w.is_contiguous()
+        n = m * max(replicas, 0)   # (a negative count is the kernel's to refuse)
+        rows_out, w = _bufs(r.device, out, ((n, self.state_words), torch.int32), ((n,), torch.int32))
         with torch.cuda.device(r.device):
             K.check(K.lib().hb_belief_determinize(C.byref(self.cfg), K.dptr(r), m, int(seat), replicas, int(seed), int(draw),
                                                   int(first_row_id), K.dptr(rows_out), K.dptr(w), K.current_stream()))
@@ -88,15 +96,10 @@ class Determinizer:
 def search_reduce(scores, weights, legal):
     """hb_search_reduce: scores [m, A, R] int8, weights [m, R] (u32 bits in int32), legal [m, A] int8 ->
     (value [m, A] f32, wsum [m, A] int64, n_live [m, A] int32, best [m] int32)."""
-    m, A, R = scores.shape
-    assert scores.dtype == torch.int8 and scores.is_contiguous()
-    assert weights.shape == (m, R) and weights.dtype == torch.int32 and weights.is_contiguous()
-    assert legal.shape == (m, A) and legal.dtype == torch.int8 and legal.is_contiguous()
-    dev = scores.device
-    value = torch.empty((m, A), dtype=torch.float32, device=dev)
-    wsum = torch.empty((m, A), dtype=torch.int64, device=dev)
-    n_live = torch.empty((m, A), dtype=torch.int32, device=dev)
-    best = torch.empty(m, dtype=torch.int32, device=dev)
+    (m, A, R), dev = scores.shape, scores.device
+    _bufs(dev, (scores, weights, legal), ((m, A, R), torch.int8), ((m, R), torch.int32), ((m, A), torch.int8))
+    value, wsum, n_live, best = _bufs(dev, None, ((m, A), torch.float32), ((m, A), torch.int64), ((m, A), torch.int32),
+                                      ((m,), torch.int32))
     with torch.cuda.device(dev):
         K.check(K.lib().hb_search_reduce(K.dptr(scores), K.dptr(weights), K.dptr(legal), m, A, R, K.dptr(value), K.dptr(wsum),
                                          K.dptr(n_live), K.dptr(best), K.current_stream()))
@@ -110,18 +113,10 @@ def search_layout(cfg, det_rows, weights, cand, filler, replicas, out=None):
     m, Cn = cand.shape
     R, SW = int(replicas), det_rows.shape[1]
     n, dev = m * Cn * R, det_rows.device
-    assert det_rows.shape == (m * R, SW) and det_rows.dtype == torch.int32 and det_rows.is_contiguous()
-    assert weights.shape == (m * R,) and weights.dtype == torch.int32 and weights.is_contiguous()
-    assert cand.dtype == torch.int32 and cand.is_contiguous()
-    assert filler.shape == (m,) and filler.dtype == torch.int32 and filler.is_contiguous()
-    if out is None:
-        out = (torch.empty((n, SW), dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
-               torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(m, dtype=torch.int32, device=dev))
-    rows, forced, done, n_played = out
-    assert rows.shape == (n, SW) and rows.dtype == torch.int32 and rows.is_contiguous()
-    assert forced.shape == (n,) and forced.dtype == torch.int32 and forced.is_contiguous()
-    assert done.shape == (n,) and done.dtype == torch.uint8 and done.is_contiguous()
-    assert n_played.shape == (m,) and n_played.dtype == torch.int32 and n_played.is_contiguous()
+    _bufs(dev, (det_rows, weights, cand, filler), ((m * R, SW), torch.int32), ((m * R,), torch.int32), ((m, Cn), torch.int32),
+          ((m,), torch.int32))
+    rows, forced, done, n_played = _bufs(dev, out, ((n, SW), torch.int32), ((n,), torch.int32), ((n,), torch.uint8),
+                                         ((m,), torch.int32))
     with torch.cuda.device(dev):
         K.check(K.lib().hb_search_layout(C.byref(cfg), K.dptr(det_rows), K.dptr(weights), K.dptr(cand), K.dptr(filler), m, Cn, R,
                                          K.dptr(rows), K.dptr(forced), K.dptr(done), K.dptr(n_played), K.current_stream()))
@@ -131,15 +126,10 @@ def search_layout(cfg, det_rows, weights, cand, filler, replicas, out=None):
 def search_compare(scores, weights, cand, base_slot):
     """hb_search_compare: scores [m, C, R] int8, weights [m, R] (u32 bits in int32), cand [m, C] int32, base_slot [m] int32 ->
     (diff [m, C] f64, se [m, C] f64, n_pair [m] int32): every slot's paired difference to the base slot and its standard error."""
-    m, Cn, R = scores.shape
-    assert scores.dtype == torch.int8 and scores.is_contiguous()
-    assert weights.shape == (m, R) and weights.dtype == torch.int32 and weights.is_contiguous()
-    assert cand.shape == (m, Cn) and cand.dtype == torch.int32 and cand.is_contiguous()
-    assert base_slot.shape == (m,) and base_slot.dtype == torch.int32 and base_slot.is_contiguous()
-    dev = scores.device
-    diff = torch.empty((m, Cn), dtype=torch.float64, device=dev)
-    se = torch.empty((m, Cn), dtype=torch.float64, device=dev)
-    n_pair = torch.empty(m, dtype=torch.int32, device=dev)
+    (m, Cn, R), dev = scores.shape, scores.device
+    _bufs(dev, (scores, weights, cand, base_slot), ((m, Cn, R), torch.int8), ((m, R), torch.int32), ((m, Cn), torch.int32),
+          ((m,), torch.int32))
+    diff, se, n_pair = _bufs(dev, None, ((m, Cn), torch.float64), ((m, Cn), torch.float64), ((m,), torch.int32))
     with torch.cuda.device(dev):
         K.check(K.lib().hb_search_compare(K.dptr(scores), K.dptr(weights), K.dptr(cand), K.dptr(base_slot), m, Cn, R, K.dptr(diff),
                                           K.dptr(se), K.dptr(n_pair), K.current_stream()))
@@ -151,11 +141,8 @@ def belief_splice(cfg, prev_rows, det_rows, seat, n_cand, out=None):
     rows [K, m, SW] int32, candidate-major: slab k = prev_rows with word 10 + seat of every row taken from candidate (i, k)."""
     m, SW = prev_rows.shape
     Kn, dev = int(n_cand), prev_rows.device
-    assert prev_rows.dtype == torch.int32 and prev_rows.is_contiguous()
-    assert det_rows.shape == (m * Kn, SW) and det_rows.dtype == torch.int32 and det_rows.is_contiguous()
-    if out is None:
-        out = torch.empty((max(Kn, 0), m, SW), dtype=torch.int32, device=dev)
-    assert out.shape == (Kn, m, SW) and out.dtype == torch.int32 and out.is_contiguous()
+    _bufs(dev, (prev_rows, det_rows), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32))
+    out, = _bufs(dev, None if out is None else (out,), ((max(Kn, 0), m, SW), torch.int32))
     with torch.cuda.device(dev):
         K.check(K.lib().hb_belief_splice(C.byref(cfg), K.dptr(prev_rows), K.dptr(det_rows), m, int(seat), Kn, K.dptr(out),
                                          K.current_stream()))
@@ -168,25 +155,27 @@ def belief_select(cfg, src_rows, det_rows, weights, hyp_moves, actual, valid, re
     fallback [m] uint8). `out`: an optional tuple of these four buffers to write into."""
     m, SW = src_rows.shape
     Kn, R, dev = hyp_moves.shape[0], int(replicas), src_rows.device
-    assert src_rows.dtype == torch.int32 and src_rows.is_contiguous()
-    assert det_rows.shape == (m * Kn, SW) and det_rows.dtype == torch.int32 and det_rows.is_contiguous()
-    assert weights.shape == (m * Kn,) and weights.dtype == torch.int32 and weights.is_contiguous()
-    assert hyp_moves.shape == (Kn, m) and hyp_moves.dtype == torch.int32 and hyp_moves.is_contiguous()
-    assert actual.shape == (m,) and actual.dtype == torch.int32 and actual.is_contiguous()
-    assert valid is None or (valid.shape == (m,) and valid.dtype == torch.uint8 and valid.is_contiguous())
-    if out is None:
-        out = (torch.empty((m * max(R, 0), SW), dtype=torch.int32, device=dev), torch.empty(m * max(R, 0), dtype=torch.int32, device=dev),
-               torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.uint8, device=dev))
-    rows, w, n_surv, fallback = out
-    assert rows.shape == (m * R, SW) and rows.dtype == torch.int32 and rows.is_contiguous()
-    assert w.shape == (m * R,) and w.dtype == torch.int32 and w.is_contiguous()
-    assert n_surv.shape == (m,) and n_surv.dtype == torch.int32 and n_surv.is_contiguous()
-    assert fallback.shape == (m,) and fallback.dtype == torch.uint8 and fallback.is_contiguous()
+    _bufs(dev, (src_rows, det_rows, weights, hyp_moves, actual), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32),
+          ((m * Kn,), torch.int32), ((Kn, m), torch.int32), ((m,), torch.int32))
+    if valid is not None:
+        _bufs(dev, (valid,), ((m,), torch.uint8))
+    n = m * max(R, 0)
+    rows, w, n_surv, fallback = _bufs(dev, out, ((n, SW), torch.int32), ((n,), torch.int32), ((m,), torch.int32), ((m,), torch.uint8))
     with torch.cuda.device(dev):
         K.check(K.lib().hb_belief_select(C.byref(cfg), K.dptr(src_rows), K.dptr(det_rows), K.dptr(weights), K.dptr(hyp_moves),
                                          K.dptr(actual), K.dptr(valid), m, Kn, R, K.dptr(rows), K.dptr(w), K.dptr(n_surv),
                                          K.dptr(fallback), K.current_stream()))
     return rows, w, n_surv, fallback
+
+
+def running(rows):
+    """[m] bool: the game of each state row has not ended (the status bits of word 0 are 0)."""
+    return ((rows[:, 0] >> 19) & 3) == 0
+
+
+def current_player(rows):
+    """[m]: the seat to act in each state row (word 0)."""
+    return (rows[:, 0] >> 13) & 7
 
 
 def last_move_uid(cfg, rows):
@@ -268,8 +257,7 @@ class ConditionedDeterminizer:
         b = self._setup(m, Kn, dev)
         env = b["env"]
         with torch.cuda.device(dev):
-            running = ((r[:, 0] >> 19) & 3) == 0
-            usable = running if valid is None else running & (valid != 0)
+            usable = running(r) if valid is None else running(r) & (valid != 0)
             # a root without a usable previous state is never filtered: its slab rows only have to be states the partner's
             # policy can be run on, and the current row is one
             prev = torch.where(usable.view(m, 1), prev, r).contiguous()
@@ -282,14 +270,10 @@ class ConditionedDeterminizer:
                 env.import_state(b["hyp_rows"][k])
                 if vec:   # import_state moves the rows only: the acting seat's observation and legal mask are encoded here
                     env.observe()
-                    partner.eval_moves((env, (env.net_obs, env.legal)), int(partner_seed), int(partner_draw), b["hyp_moves"][k],
-                                       scratch=self._scratch.setdefault(partner, {}))
-                else:
-                    partner.eval_moves(env, int(partner_seed), int(partner_draw), b["hyp_moves"][k])
+                _ask(partner, env, int(partner_seed), int(partner_draw), b["hyp_moves"][k], self._scratch)
             res = belief_select(self.cfg, r, b["cand_rows"], b["cand_w"], b["hyp_moves"], last_move_uid(self.cfg, r),
                                 usable.to(torch.uint8), R,
-                                out=None if out is None else (out[0], out[1], torch.empty(m, dtype=torch.int32, device=dev),
-                                                              torch.empty(m, dtype=torch.uint8, device=dev)))
+                                out=None if out is None else tuple(out) + _bufs(dev, None, ((m,), torch.int32), ((m,), torch.uint8)))
         if out is not None:
             return res
         return res[0], res[1].long() & 0xFFFFFFFF, res[2], res[3]
@@ -331,11 +315,8 @@ def rollout(env, cfg, blueprint, seed, first_seat, forced, done, final_score, le
         if t == 0:
             moves = forced
         else:
-            agent, moves = blueprint[seat], act
-            if agent.requires_vectorized_observation():
-                agent.eval_moves((env, (env.net_obs, env.legal)), seed, t + 1, act, scratch=scratch.setdefault(agent, {}))
-            else:
-                agent.eval_moves(env, seed, t + 1, act)
+            moves = act
+            _ask(blueprint[seat], env, seed, t + 1, act, scratch)
         env.step(moves)
         K.check(L.hb_eval_tally(cfg_ref, n, seat, t, K.dptr(moves), *bufs, K.current_stream()))
         t += 1
@@ -352,8 +333,9 @@ class RolloutSearch:
     """Value of every root action under `blueprint` by belief-sampled rollouts; see the module docstring.
 
     first_game_id: global id of rollout game 0 (keys the blueprint's draws, like Evaluator's). The rollout env and every
-    buffer are built by the first run() of a size and kept for the next; run_candidates() keeps its own per (m, C, replicas),
-    so that a screening stage's env survives the confirming stage's.
+    buffer are built by the first search of a size (m roots, C slots — run(): the A actions —, replicas) and kept for the next,
+    one entry per (C, replicas): a screening stage's env survives the confirming stage's, and another number of roots replaces
+    the entry of its stage.
 
     history = (prev_rows, partner_seed, partner_draw, first_game_id[, valid]) to run / run_candidates / confirm: the replicas
     come from `ConditionedDeterminizer` (the belief conditioned on the last move, made from prev_rows by the seat before the
@@ -362,7 +344,7 @@ class RolloutSearch:
 
     def __init__(self, game="Hanabi-Full", players=2, replicas=32, seed=1, device=None, config=None, check_every=8, first_game_id=0,
                  oversample=8):
-        self.cfg = _config(game, players, config)
+        self.cfg = eval_config(game, players, config)
         self.players = self.cfg.players
         self.replicas = int(replicas)
         if self.replicas < 1:
@@ -378,47 +360,33 @@ class RolloutSearch:
         self.cdet = None   # ConditionedDeterminizer, built by the first search with a history
         self.num_actions = K.lib().hb_num_actions(C.byref(self.cfg))
         self.n_counters = K.lib().hb_eval_counters(C.byref(self.cfg))
-        self._sized = {}   # m -> buffers of that size
-        self._scratch = weakref.WeakKeyDictionary()   # agent -> the buffers its eval_moves writes
-        self._cand_sized = {}   # (m, C, replicas) -> buffers of run_candidates, each with the scratch of its own env
+        self._sized = {}   # (m, C, replicas) -> the rollout env and buffers of that size, with the scratch of its blueprint
+        self._uid = None   # [1, A] int32: every uid, on the device (built by the first run())
 
-    def _buffers(self, m, Cn, R, first_game_id, dev):
-        SW = self.det.state_words
-        n = m * Cn * R
-        env = HanabiEnv(config=self.cfg, n_games=n, seed=self.seed, first_game_id=first_game_id, device=dev, packed=True)
-        return dict(env=env, det_rows=torch.empty((m * R, SW), dtype=torch.int32, device=dev),
-                    weights=torch.empty(m * R, dtype=torch.int32, device=dev),
-                    rows=torch.empty((n, SW), dtype=torch.int32, device=dev),
-                    forced=torch.empty(n, dtype=torch.int32, device=dev), act=torch.empty(n, dtype=torch.int32, device=dev),
-                    done=torch.empty(n, dtype=torch.uint8, device=dev), final_score=torch.empty(n, dtype=torch.int8, device=dev),
-                    length=torch.empty(n, dtype=torch.int16, device=dev),
-                    counters=torch.empty(self.n_counters, dtype=torch.int64, device=dev),
-                    n_played=torch.empty(m, dtype=torch.int32, device=dev))
-
-    def _setup(self, m, dev):
-        b = self._sized.get(m)
-        if b is not None:
-            return b
-        self._sized.clear()   # one size at a time: a rollout env of the old size is memory the new one needs
-        A = self.num_actions
-        b = self._buffers(m, A, self.replicas, self.first_game_id, dev)
-        b["uid"] = torch.arange(A, dtype=torch.int32, device=dev).view(1, A)
-        self._sized[m] = b
-        return b
-
-    def _setup_candidates(self, m, Cn, R, first_game_id, dev):
-        b = self._cand_sized.get((m, Cn, R))
+    def _setup(self, m, Cn, R, first_game_id, dev):
+        b = self._sized.get((m, Cn, R))
         if b is None:
-            for k in [k for k in self._cand_sized if k[1:] == (Cn, R)]:   # the same stage at another number of roots
-                del self._cand_sized[k]
-            b = self._cand_sized[(m, Cn, R)] = self._buffers(m, Cn, R, first_game_id, dev)
-            b["scratch"] = weakref.WeakKeyDictionary()
+            # the same stage at another number of roots: a rollout env of the old size is memory the new one needs
+            for k in [k for k in self._sized if k[1:] == (Cn, R)]:
+                del self._sized[k]
+            SW, n = self.det.state_words, m * Cn * R
+            env = HanabiEnv(config=self.cfg, n_games=n, seed=self.seed, first_game_id=first_game_id, device=dev, packed=True)
+            b = self._sized[(m, Cn, R)] = dict(
+                env=env, det_rows=torch.empty((m * R, SW), dtype=torch.int32, device=dev),
+                weights=torch.empty(m * R, dtype=torch.int32, device=dev),
+                rows=torch.empty((n, SW), dtype=torch.int32, device=dev),
+                forced=torch.empty(n, dtype=torch.int32, device=dev), act=torch.empty(n, dtype=torch.int32, device=dev),
+                done=torch.empty(n, dtype=torch.uint8, device=dev), final_score=torch.empty(n, dtype=torch.int8, device=dev),
+                length=torch.empty(n, dtype=torch.int16, device=dev),
+                counters=torch.empty(self.n_counters, dtype=torch.int64, device=dev),
+                n_played=torch.empty(m, dtype=torch.int32, device=dev),
+                scratch=weakref.WeakKeyDictionary())   # agent -> the buffers its eval_moves writes
         # a rollout env never deals (auto-reset off, states imported): its game ids key the blueprint's draws only
         b["env"].first_game_id = first_game_id
         return b
 
     def _roots(self, rows, blueprint, seat):
-        """The checks run() and run_candidates() share -> (rows on the device, blueprint, running [m] bool, current players)."""
+        """The checks run() and run_candidates() share -> (rows on the device, blueprint, live [m] bool, current players)."""
         blueprint = list(blueprint)
         if len(blueprint) != self.players:
             raise ValueError(f"one blueprint agent per seat: {self.players} players, {len(blueprint)} agents")
@@ -428,60 +396,73 @@ class RolloutSearch:
         r = _rows(rows, self.det.state_words, self.device)
         if r.shape[0] < 1:
             raise ValueError("no roots")
-        w0 = r[:, 0]
-        running = ((w0 >> 19) & 3) == 0
-        cps = torch.unique(((w0 >> 13) & 7)[running]).tolist()
+        live = running(r)
+        cps = torch.unique(current_player(r)[live]).tolist()
         if len(cps) > 1:
             raise ValueError(f"all roots must have the same current player, got seats {cps}")
         if seat is not None and cps and cps[0] != int(seat):
             raise ValueError(f"the roots' current player is seat {cps[0]}, not seat {seat}")
-        return r, blueprint, running, cps
+        return r, blueprint, live, cps
 
-    def _nothing(self, m, Cn, dev, cand=None, compared=False):
+    def _nothing(self, m, Cn, dev, compared):
         """The result when no root is running: nothing to play."""
         z = torch.zeros((m, Cn), dtype=torch.int64, device=dev)
-        none = torch.full((m,), -1, dtype=torch.int32, device=dev)
-        res = SearchResult(torch.full((m, Cn), float("nan"), device=dev), z, z.int(), none, 0, 0)
-        if cand is not None:
-            res.cand, res.best_uid = cand, none.clone()
+        res = SearchResult(torch.full((m, Cn), float("nan"), device=dev), z, z.int(), torch.full((m,), -1, dtype=torch.int32, device=dev),
+                           0, 0)
         if compared:
             res.diff = torch.full((m, Cn), float("nan"), dtype=torch.float64, device=dev)
             res.se, res.n_pair = res.diff.clone(), torch.zeros(m, dtype=torch.int32, device=dev)
         return res
 
-    def _play(self, b, r, cand, filler, R, cp, blueprint, draw, first_row_id, scratch, history=None):
-        """Determinize the roots `r` R times, lay the replicas out as [m, C, R] games of b's env (hb_search_layout) and play them
-        to the end. Leaves the final scores in b["final_score"]; returns (games played as a device scalar, turns, n_surv,
-        fallback), the last two None without a history."""
-        env = b["env"]
+    def _run(self, roots, cand, filler, R, draw, first_row_id, first_game_id, base_slot, history):
+        """The search itself, for run() and run_candidates() alike (arguments checked): determinize the roots R times, lay the
+        replicas out as the [m, C, R] games of this size's env (hb_search_layout), play them to the end with the blueprint, reduce
+        the final scores per slot (hb_search_reduce) and, with a base_slot, compare the slots to it (hb_search_compare). The
+        result's cand and best_uid stay None."""
+        r, blueprint, live, cps = roots
+        (m, Cn), dev = cand.shape, r.device
+        b = self._setup(m, Cn, R, first_game_id, dev)
+        if not cps:
+            return self._nothing(m, Cn, dev, compared=base_slot is not None)
+        cp, env = int(cps[0]), b["env"]
         n_surv = fallback = None
-        if history is None:
-            self.det.sample(r, seat=cp, replicas=R, seed=self.seed, draw=draw, first_row_id=first_row_id,
-                            out=(b["det_rows"], b["weights"]))
-        else:
-            prev, p_seed, p_draw, gid, valid = history
-            if self.cdet is None:
-                self.cdet = ConditionedDeterminizer(config=self.cfg)
-            _, _, n_surv, fallback = self.cdet.sample(r, prev, blueprint[(cp - 1) % self.players], cp, R, self.oversample, self.seed,
-                                                      draw, p_seed, p_draw, gid, valid=valid, first_row_id=first_row_id,
-                                                      out=(b["det_rows"], b["weights"]))
-        # [m, C, R]: block c of root i holds the same R replicas. A slot without a candidate (an illegal action, in run()) is
-        # never counted (done up front); its games move in step with the others on the root's filler move, so that no illegal
-        # move reaches the env
-        search_layout(self.cfg, b["det_rows"], b["weights"], cand, filler, R, out=(b["rows"], b["forced"], b["done"], b["n_played"]))
-        b["final_score"].zero_()
-        b["length"].zero_()
-        b["counters"].zero_()
-        b["counters"][0] = b["n_played"].sum()
-        rollouts = b["counters"][0].clone()
-        env.import_state(b["rows"])
-        illegal0 = env.illegal_count()
-        turns = rollout(env, self.cfg, blueprint, self.seed, cp, b["forced"], b["done"], b["final_score"], b["length"], b["counters"],
-                        b["act"], scratch, self.check_every)
-        illegal = env.illegal_count() - illegal0
-        if illegal:
-            raise RuntimeError(f"{illegal} illegal moves in the rollouts (a candidate that is illegal at its root, or the blueprint's)")
-        return rollouts, turns, n_surv, fallback
+        with torch.cuda.device(dev):
+            if history is None:
+                self.det.sample(r, seat=cp, replicas=R, seed=self.seed, draw=draw, first_row_id=first_row_id,
+                                out=(b["det_rows"], b["weights"]))
+            else:
+                prev, p_seed, p_draw, gid, valid = history
+                if self.cdet is None:
+                    self.cdet = ConditionedDeterminizer(config=self.cfg)
+                _, _, n_surv, fallback = self.cdet.sample(r, prev, blueprint[(cp - 1) % self.players], cp, R, self.oversample,
+                                                          self.seed, draw, p_seed, p_draw, gid, valid=valid,
+                                                          first_row_id=first_row_id, out=(b["det_rows"], b["weights"]))
+            # [m, C, R]: block c of root i holds the same R replicas. A slot without a candidate (an illegal action, in run()) is
+            # never counted (done up front); its games move in step with the others on the root's filler move, so that no illegal
+            # move reaches the env
+            search_layout(self.cfg, b["det_rows"], b["weights"], cand, filler, R, out=(b["rows"], b["forced"], b["done"], b["n_played"]))
+            b["final_score"].zero_()
+            b["length"].zero_()
+            b["counters"].zero_()
+            b["counters"][0] = b["n_played"].sum()
+            scores, weights = b["final_score"].view(m, Cn, R), b["weights"].view(m, R)
+            # enqueued ahead of the rollouts, read after them: games played, dead replicas of the running roots, running roots
+            counts = torch.stack([b["counters"][0], (live.view(m, 1) & (weights == 0)).sum(), live.sum()])
+            slots = (cand >= 0).to(torch.int8)
+            env.import_state(b["rows"])
+            illegal0 = env.illegal_count()
+            turns = rollout(env, self.cfg, blueprint, self.seed, cp, b["forced"], b["done"], b["final_score"], b["length"],
+                            b["counters"], b["act"], b["scratch"], self.check_every)
+            illegal = env.illegal_count() - illegal0
+            if illegal:
+                raise RuntimeError(f"{illegal} illegal moves in the rollouts (a candidate that is illegal at its root, or the blueprint's)")
+            value, wsum, n_live, best = search_reduce(scores, weights, slots)
+            rollouts, dead, roots = counts.tolist()
+            res = SearchResult(value, wsum, n_live, best, rollouts, turns, dead=dead, replicas=roots * R, n_surv=n_surv,
+                               fallback=fallback)
+            if base_slot is not None:
+                res.diff, res.se, res.n_pair = search_compare(scores, weights, cand, base_slot)
+        return res
 
     @torch.no_grad()
     def run(self, rows, legal, blueprint, draw, seat=None, baseline=None, history=None):
@@ -490,9 +471,10 @@ class RolloutSearch:
         All running roots must have the same current player (`seat`, when given, must be that player). baseline: optional [m]
         int32 uids (the blueprint's moves): the result's diff / se / n_pair are then every action's paired difference to it.
         history: see the class docstring."""
-        r, blueprint, running, cps = self._roots(rows, blueprint, seat)
+        roots = self._roots(rows, blueprint, seat)
+        r = roots[0]
         dev = r.device
-        m, A, R = r.shape[0], self.num_actions, self.replicas
+        m, A = r.shape[0], self.num_actions
         if history is not None:
             history = _history(history, m, self.det.state_words, dev)
         lg = torch.as_tensor(legal).to(device=dev, dtype=torch.int8).contiguous()
@@ -502,22 +484,13 @@ class RolloutSearch:
             baseline = torch.as_tensor(baseline).to(device=dev, dtype=torch.int32).contiguous()
             if baseline.shape != (m,):
                 raise ValueError(f"baseline has shape ({m},), got {tuple(baseline.shape)}")
-        b = self._setup(m, dev)
-        if not cps:
-            return self._nothing(m, A, dev, compared=baseline is not None)
-        cp = int(cps[0])
-        with torch.cuda.device(dev):
-            lgb = lg != 0
-            cand = torch.where(lgb, b["uid"], -1).int().contiguous()
-            filler = lgb.int().argmax(1).int()   # the root's lowest legal uid
-            rollouts, turns, n_surv, fallback = self._play(b, r, cand, filler, R, cp, blueprint, draw, 0, self._scratch, history)
-            dead = (running.view(m, 1) & (b["weights"].view(m, R) == 0)).sum()
-            value, wsum, n_live, best = search_reduce(b["final_score"].view(m, A, R), b["weights"].view(m, R), lg)
-            res = SearchResult(value, wsum, n_live, best, int(rollouts.item()), turns, dead=int(dead.item()),
-                               replicas=int(running.sum().item()) * R, n_surv=n_surv, fallback=fallback)
-            if baseline is not None:   # (slot = uid here)
-                res.diff, res.se, res.n_pair = search_compare(b["final_score"].view(m, A, R), b["weights"].view(m, R), cand, baseline)
-        return res
+        if self._uid is None:
+            self._uid = torch.arange(A, dtype=torch.int32, device=dev).view(1, A)
+        # run_candidates() with every legal action as the candidate of its own slot (slot = uid: the baseline is its own slot)
+        lgb = lg != 0
+        cand = torch.where(lgb, self._uid, -1).int().contiguous()
+        filler = lgb.int().argmax(1).int()   # the root's lowest legal uid
+        return self._run(roots, cand, filler, self.replicas, draw, 0, self.first_game_id, baseline, history)
 
     @torch.no_grad()
     def run_candidates(self, rows, cand, filler, blueprint, draw, replicas=None, first_row_id=0, first_game_id=None, base_slot=None,
@@ -529,9 +502,9 @@ class RolloutSearch:
         search's). The result's second axis is the slot: `best` is the best slot, `best_uid` its uid, `cand` the list. base_slot:
         optional [m] int32 slot of each root's baseline (-1: none): fills diff / se / n_pair (hb_search_compare). history: see
         the class docstring (the candidates' row ids then start at first_row_id and take replicas * oversample per root)."""
-        r, blueprint, running, cps = self._roots(rows, blueprint, None)
-        dev = r.device
-        m = r.shape[0]
+        roots = self._roots(rows, blueprint, None)
+        dev = roots[0].device
+        m = roots[0].shape[0]
         if history is not None:
             history = _history(history, m, self.det.state_words, dev)
         R = self.replicas if replicas is None else int(replicas)
@@ -540,7 +513,6 @@ class RolloutSearch:
         cand = torch.as_tensor(cand).to(device=dev, dtype=torch.int32).contiguous()
         if cand.dim() != 2 or cand.shape[0] != m or not 1 <= cand.shape[1] <= 64:
             raise ValueError(f"cand has shape ({m}, C) with C in 1..64, got {tuple(cand.shape)}")
-        Cn = cand.shape[1]
         filler = torch.as_tensor(filler).to(device=dev, dtype=torch.int32).contiguous()
         if filler.shape != (m,):
             raise ValueError(f"filler has shape ({m},), got {tuple(filler.shape)}")
@@ -548,22 +520,10 @@ class RolloutSearch:
             base_slot = torch.as_tensor(base_slot).to(device=dev, dtype=torch.int32).contiguous()
             if base_slot.shape != (m,):
                 raise ValueError(f"base_slot has shape ({m},), got {tuple(base_slot.shape)}")
-        gid = self.first_game_id if first_game_id is None else int(first_game_id)
-        b = self._setup_candidates(m, Cn, R, gid, dev)
-        if not cps:
-            return self._nothing(m, Cn, dev, cand=cand, compared=base_slot is not None)
-        cp = int(cps[0])
-        with torch.cuda.device(dev):
-            rollouts, turns, n_surv, fallback = self._play(b, r, cand, filler, R, cp, blueprint, draw, int(first_row_id), b["scratch"],
-                                                           history)
-            dead = (running.view(m, 1) & (b["weights"].view(m, R) == 0)).sum()
-            scores, weights = b["final_score"].view(m, Cn, R), b["weights"].view(m, R)
-            value, wsum, n_live, best = search_reduce(scores, weights, (cand >= 0).to(torch.int8))
-            best_uid = torch.where(best >= 0, cand.gather(1, best.long().clamp(min=0).view(m, 1)).view(m), best)
-            res = SearchResult(value, wsum, n_live, best, int(rollouts.item()), turns, dead=int(dead.item()),
-                               replicas=int(running.sum().item()) * R, cand=cand, best_uid=best_uid, n_surv=n_surv, fallback=fallback)
-            if base_slot is not None:
-                res.diff, res.se, res.n_pair = search_compare(scores, weights, cand, base_slot)
+        res = self._run(roots, cand, filler, R, draw, int(first_row_id),
+                        self.first_game_id if first_game_id is None else int(first_game_id), base_slot, history)
+        res.cand = cand
+        res.best_uid = torch.where(res.best >= 0, cand.gather(1, res.best.long().clamp(min=0).view(m, 1)).view(m), res.best)
         return res
 
     @torch.no_grad()
@@ -590,8 +550,7 @@ class RolloutSearch:
         bl, ch = pair
         lgb = lg != 0
         is_legal = lambda u: (u >= 0) & (u < A) & lgb.gather(1, u.long().clamp(0, A - 1).view(m, 1)).view(m)
-        running = ((r[:, 0] >> 19) & 3) == 0
-        ok = running & (ch != bl) & is_legal(bl) & is_legal(ch)
+        ok = running(r) & (ch != bl) & is_legal(bl) & is_legal(ch)
         cand = torch.where(ok.view(m, 1), torch.stack([bl, ch], 1), -1).int().contiguous()
         return self.run_candidates(r, cand, lgb.int().argmax(1).int(), blueprint, draw, replicas=replicas,
                                    first_row_id=m * self.replicas * (1 if history is None else self.oversample),
@@ -635,6 +594,8 @@ class SearchPlayer:
     searched with the filter), `unconditioned` (live roots without), `survivors` / `candidates` (sums over the conditioned
     roots), `fallbacks` (conditioned roots without a survivor)."""
 
+    COUNTERS = ("moves", "deviations", "confirmed", "rejected", "conditioned", "unconditioned", "survivors", "candidates", "fallbacks")
+
     def __init__(self, blueprint, seat, replicas=32, threshold=0.0, seed=1, check_every=8, z=None, confirm_replicas=0,
                  condition=False, oversample=8):
         self.blueprint = list(blueprint)
@@ -661,39 +622,13 @@ class SearchPlayer:
         self.last_result = None   # the SearchResult of the last call's first stage
         self._memory = None    # condition: (env, draw, rows, moves played) of the last call
         self._prev_env = None  # condition: the scratch env that rebuilds the partner's state
-        self._moves = self._dev = self._confirmed = self._rejected = self._cond = None
-        self.dead_replicas = self.replicas_drawn = self.searches = self.rollouts = 0
+        self.reset_stats()
 
     def requires_vectorized_observation(self):
         return self.own.requires_vectorized_observation()
 
-    @property
-    def moves(self):
-        return 0 if self._moves is None else int(self._moves.item())
-
-    @property
-    def deviations(self):
-        return 0 if self._dev is None else int(self._dev.item())
-
-    @property
-    def confirmed(self):
-        return 0 if self._confirmed is None else int(self._confirmed.item())
-
-    @property
-    def rejected(self):
-        return 0 if self._rejected is None else int(self._rejected.item())
-
-    def _cond_counter(self, j):
-        return 0 if self._cond is None else int(self._cond[j].item())
-
-    conditioned = property(lambda self: self._cond_counter(0))
-    unconditioned = property(lambda self: self._cond_counter(1))
-    survivors = property(lambda self: self._cond_counter(2))
-    candidates = property(lambda self: self._cond_counter(3))
-    fallbacks = property(lambda self: self._cond_counter(4))
-
     def reset_stats(self):
-        self._moves = self._dev = self._confirmed = self._rejected = self._cond = None
+        self._stats = None   # [len(COUNTERS)] int64 on the device, built by the first eval_moves: read through the properties
         self.dead_replicas = self.replicas_drawn = self.searches = self.rollouts = 0
 
     def _previous(self, env, rows, draw):
@@ -706,13 +641,13 @@ class SearchPlayer:
         _, _, then_rows, then_moves = mem
         pe = self._prev_env
         if pe is None or pe.n != m or pe.device != dev or pe.cfg.players != env.cfg.players:
-            pe = self._prev_env = HanabiEnv(config=_config(None, None, env.cfg), n_games=m, device=dev, packed=True)
+            pe = self._prev_env = HanabiEnv(config=eval_config(None, None, env.cfg), n_games=m, device=dev, packed=True)
         pe.import_state(then_rows)
         pe.step(then_moves)
         prev = pe.export_state()
-        w2 = rows[:, 2]
-        valid = ((((then_rows[:, 0] >> 19) & 3) == 0) & (((rows[:, 0] >> 19) & 3) == 0) & ((w2 & 1) != 0) & (((w2 >> 1) & 7) == partner)
-                 & (((prev[:, 0] >> 19) & 3) == 0) & (((prev[:, 0] >> 13) & 7) == partner))
+        w2 = rows[:, 2]   # the last move of this deal: bit 0 set once there is one, bits 1-3 the seat that made it
+        partner_moved_last = ((w2 & 1) != 0) & (((w2 >> 1) & 7) == partner)
+        valid = running(then_rows) & running(rows) & partner_moved_last & running(prev) & (current_player(prev) == partner)
         return prev, valid.to(torch.uint8)
 
     def _significant(self, diff, se, z):
@@ -721,14 +656,13 @@ class SearchPlayer:
 
     @torch.no_grad()
     def eval_moves(self, observations, seed, draw, actions_out, scratch=None):
-        vec = self.own.requires_vectorized_observation()
         env = observations[0] if isinstance(observations, (tuple, list)) else observations
         if not hasattr(env, "h"):
             raise TypeError("SearchPlayer reads the env's state rows: pass (env, (obs, legal)) or the HanabiEnv itself")
         if env.color_shuffled:
             raise ValueError("search on a colour-shuffled env is not supported: the rollout env's game ids would draw other "
                              "permutations (DESIGN.md section 11f)")
-        if vec:
+        if self.own.requires_vectorized_observation():   # (the caller's observation and scratch, as it handed them over)
             self.own.eval_moves(observations, seed, draw, actions_out, scratch=scratch)
         else:
             self.own.eval_moves(env, seed, draw, actions_out)
@@ -746,15 +680,13 @@ class SearchPlayer:
         res = self._search.run(rows, env.legal, self.blueprint, draw, seat=self.seat,
                                baseline=actions_out if self.z is not None else None, history=history)
         self.last_result = res
-        live = ((rows[:, 0] >> 19) & 3) == 0
+        live = running(rows)
         bp = actions_out.long().clamp(0, env.num_actions - 1).view(-1, 1)
         best = res.best.long().clamp(min=0).view(-1, 1)
         v_bp, v_best = res.value.gather(1, bp), res.value.gather(1, best)
         ok = (res.best.view(-1, 1) >= 0) & (res.n_live.gather(1, bp) > 0) & (res.n_live.gather(1, best) > 0)
         deviate = (ok & ((v_best - v_bp) > self.threshold)).view(-1) & live   # (NaN compares false)
-        if self._moves is None:
-            self._moves, self._dev, self._confirmed, self._rejected = (torch.zeros((), dtype=torch.int64, device=rows.device)
-                                                                       for _ in range(4))
+        counts = {}   # this call's share of the device counters
         self.rollouts += res.rollouts
         if staged:
             challenger = deviate & (res.best != actions_out)
@@ -765,22 +697,27 @@ class SearchPlayer:
                                                   torch.where(challenger, res.best, -1), self.confirm_replicas, history=history)
                     deviate = challenger & self._significant(second.diff[:, 1], second.se[:, 1], self.z or 0.0)
                     self.rollouts += second.rollouts
-                self._confirmed += challenger.sum()
-                self._rejected += (challenger & ~deviate).sum()
+                counts.update(confirmed=challenger.sum(), rejected=(challenger & ~deviate).sum())
             else:
                 deviate = challenger & self._significant(res.diff.gather(1, best).view(-1), res.se.gather(1, best).view(-1), self.z)
         actions_out.copy_(torch.where(deviate, res.best, actions_out))
         if self.condition:
             self._memory = (weakref.ref(env), int(draw), rows, actions_out.clone())
             if res.fallback is not None:   # (None: no root was running)
-                if self._cond is None:
-                    self._cond = torch.zeros(5, dtype=torch.int64, device=rows.device)
                 filtered = live & (res.fallback != 2)
-                self._cond += torch.stack([filtered.sum(), (live & (res.fallback == 2)).sum(), (res.n_surv * filtered).sum(),
-                                           filtered.sum() * (self.replicas * self.oversample), (filtered & (res.fallback == 1)).sum()])
-        self._moves += live.sum()
-        self._dev += deviate.sum()
+                counts.update(conditioned=filtered.sum(), unconditioned=(live & (res.fallback == 2)).sum(),
+                              survivors=(res.n_surv * filtered).sum(), candidates=filtered.sum() * (self.replicas * self.oversample),
+                              fallbacks=(filtered & (res.fallback == 1)).sum())
+        counts.update(moves=live.sum(), deviations=deviate.sum())
+        if self._stats is None:
+            self._stats = torch.zeros(len(self.COUNTERS), dtype=torch.int64, device=rows.device)
+        zero = self._stats.new_zeros(())
+        self._stats += torch.stack([counts.get(name, zero) for name in self.COUNTERS])
         self.dead_replicas += res.dead
         self.replicas_drawn += res.replicas
         self.searches += 1
         return actions_out
+
+
+for _j, _name in enumerate(SearchPlayer.COUNTERS):   # the device counters as read-only ints: 0 before the first call
+    setattr(SearchPlayer, _name, property(lambda self, j=_j: 0 if self._stats is None else int(self._stats[j].item())))

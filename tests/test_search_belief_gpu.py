@@ -4,12 +4,9 @@ ConditionedDeterminizer.sample against a rerun by hand, the reconstruction of th
 guarantees of SearchPlayer(condition=True) and session.search(history=)."""
 import numpy as np
 import pytest
+from search_util import _dqn, _u32
 
 pytestmark = pytest.mark.gpu
-
-
-def _u32(t):
-    return t.cpu().numpy().view(np.uint32) if t.dtype.itemsize == 4 else t.cpu().numpy()
 
 
 def _played(game, players, n, turns, seed=3):
@@ -322,8 +319,6 @@ def test_search_player_conditioned():
 def test_search_player_conditions_on_a_dqn_partner():
     """Small, bf16, bit-packed observations: the partner's hypothetical moves come through the vectorized path (observe() on the
     scratch env, eval_moves with its own scratch buffers), and so do the searcher's own."""
-    from test_search_gpu import _dqn
-
     import hanabi_hip
     from hanabi_agents.rule_based import RulebasedAgent, predefined_rules as PR
     from hanabi_hip import Evaluator, SearchPlayer

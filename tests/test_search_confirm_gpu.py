@@ -5,21 +5,16 @@ import math
 
 import numpy as np
 import pytest
+from search_util import _mid_game_env, _team, _u32
 
 pytestmark = pytest.mark.gpu
 
 
 def _roots(game, players, turns, n=37, seed=3):
     """(env, state rows [n, SW], legal [n, A]) of n games `turns` random legal moves in."""
-    from test_search_gpu import _mid_game_env
-
     env = _mid_game_env(game, players, n, turns, seed=seed)
     env.observe()
     return env, env.export_state(), env.legal.clone()
-
-
-def _u32(t):
-    return t.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
 
 
 @pytest.mark.parametrize("game,players,turns", [("Hanabi-Full", 2, 14), ("Hanabi-Full", 5, 17), ("Hanabi-Small", 2, 7)])
@@ -201,7 +196,6 @@ def _same_or_nan(got, want):
 @pytest.mark.parametrize("game,team_name,turns", [("Hanabi-Full", "piers_piers", 8), ("Hanabi-Small", "dqn_piers", 4)])
 def test_confirm_equals_a_rerun_by_hand(game, team_name, turns):
     import torch
-    from test_search_gpu import _team
 
     from hanabi_hip import RolloutSearch
 
@@ -256,7 +250,6 @@ def test_confirm_equals_a_rerun_by_hand(game, team_name, turns):
 
 def test_confirm_draws_fresh_replicas_and_is_deterministic():
     import torch
-    from test_search_gpu import _team
 
     from hanabi_hip import Determinizer, RolloutSearch
 
@@ -270,7 +263,7 @@ def test_confirm_draws_fresh_replicas_and_is_deterministic():
     challenger = torch.where(first.best != baseline, first.best, -1).int()
     res = rs.confirm(rows, legal, team, 3, baseline, challenger, R)
     assert res.rollouts > 0
-    rows1, rows2 = rs._sized[m]["det_rows"].view(m, R, -1), rs._cand_sized[(m, 2, R)]["det_rows"].view(m, R, -1)
+    rows1, rows2 = rs._sized[(m, 20, R)]["det_rows"].view(m, R, -1), rs._sized[(m, 2, R)]["det_rows"].view(m, R, -1)
     running = ((rows[:, 0] >> 19) & 3) == 0
     for i in torch.nonzero(running).view(-1).tolist():   # the same root, the same replica index: another state
         assert not torch.equal(rows1[i], rows2[i])
@@ -278,13 +271,44 @@ def test_confirm_draws_fresh_replicas_and_is_deterministic():
     seat = int(((rows[:, 0] >> 13) & 7)[running][0])
     assert torch.equal(rows1.reshape(m * R, -1), det.sample(rows, seat=seat, replicas=R, seed=4, draw=3, first_row_id=0)[0])
     assert torch.equal(rows2.reshape(m * R, -1), det.sample(rows, seat=seat, replicas=R, seed=4, draw=3, first_row_id=m * R)[0])
-    assert rs._sized[m]["env"].first_game_id == 0 and rs._cand_sized[(m, 2, R)]["env"].first_game_id == m * 20 * R
+    assert rs._sized[(m, 20, R)]["env"].first_game_id == 0 and rs._sized[(m, 2, R)]["env"].first_game_id == m * 20 * R
     again = rs.confirm(rows, legal, team, 3, baseline, challenger, R)
     for x, y in ((res.value, again.value), (res.diff, again.diff), (res.se, again.se)):
         assert torch.equal(x.nan_to_num(-77.0), y.nan_to_num(-77.0))
     assert torch.equal(res.n_pair, again.n_pair) and torch.equal(res.best, again.best) and res.rollouts == again.rollouts
     # and the first stage's env and buffers survived the second
     assert torch.equal(rs.run(rows, legal, team, draw=3).value.nan_to_num(-1), first.value.nan_to_num(-1))
+
+
+@pytest.mark.parametrize("game,players,m,R,turns", [("Hanabi-Small", 2, 5, 3, 4), ("Hanabi-Full", 5, 3, 2, 7)])
+def test_run_is_run_candidates_over_the_legal_actions(game, players, m, R, turns):
+    """run() against run_candidates() with every legal action in the slot of its uid and the root's lowest legal uid as the
+    filler, on a second search with the same seed: the same numbers bit for bit, a finished root among the roots."""
+    import torch
+
+    from hanabi_agents.rule_based import RulebasedAgent, predefined_rules as PR
+    from hanabi_hip import RolloutSearch
+
+    src, rows, legal = _roots(game, players, turns, n=m, seed=6)
+    A = src.num_actions
+    rows = rows.clone()
+    rows[1, 0] |= 1 << 19   # a finished root (random play may have ended others): it plays nothing
+    live = ((rows[:, 0] >> 19) & 3) == 0
+    assert bool(live.any()) and not bool(live[1])
+    team = [RulebasedAgent(PR.piers_rules, seed=40 + s) for s in range(players)]
+    lgb = legal != 0
+    uid = torch.arange(A, dtype=torch.int32, device="cuda").view(1, A)
+    first_legal = lgb.int().argmax(1).int()
+    b = (A - 1 - lgb.flip(1).int().argmax(1)).int()   # the baseline: each root's highest legal uid
+    one = RolloutSearch(game, players, replicas=R, seed=21).run(rows, legal, team, 13, baseline=b)
+    two = RolloutSearch(game, players, replicas=R, seed=21).run_candidates(rows, torch.where(lgb, uid, -1), first_legal, team, 13,
+                                                                           base_slot=b)
+    assert one.cand is None and one.best_uid is None and torch.equal(two.best_uid, two.best)
+    for name in ("value", "wsum", "n_live", "best", "diff", "se", "n_pair"):
+        assert torch.equal(getattr(one, name).nan_to_num(-77.0), getattr(two, name).nan_to_num(-77.0)), name
+    assert (one.rollouts, one.turns, one.dead) == (two.rollouts, two.turns, two.dead)
+    assert one.rollouts == R * int(lgb[live].sum()) and one.value.shape == (m, A)   # (no replica dies in a state reached by play)
+    assert bool(torch.isnan(one.value[~live]).all()) and bool((one.best[~live] == -1).all()) and bool((one.best[live] >= 0).all())
 
 
 def _small_eval():

@@ -3,18 +3,9 @@ restatement of tests/test_search_cpu.py bit for bit, the reduction against an in
 hand, and the guarantees of SelfPlaySession.search and SearchPlayer."""
 import numpy as np
 import pytest
+from search_util import _mid_game_env, _team
 
 pytestmark = pytest.mark.gpu
-
-
-def _mid_game_env(game, players, n, turns, seed=3):
-    """A non-resetting env after `turns` random legal moves per game (hints included; some games may have ended)."""
-    import hanabi_hip
-
-    env = hanabi_hip.HanabiEnv(game, players, n_games=n, seed=seed, auto_reset=False, packed=True)
-    for t in range(turns):
-        env.step(env.random_legal_actions(seed=seed + 1, draw=t))
-    return env
 
 
 def _ocfg(env):
@@ -22,24 +13,6 @@ def _ocfg(env):
 
     c = env.cfg
     return O.HbConfig(c.players, c.colors, c.ranks, c.hand_size, c.max_info, c.max_life, 0)
-
-
-def _dqn(env_like, dtype="bfloat16", seed=1):
-    from hanabi_agents.rlax_dqn import ActionSpec, DQNAgent, ObservationSpec, RlaxRainbowParams
-
-    params = RlaxRainbowParams(train_batch_size=128, experience_buffer_size=8192, compute_dtype=dtype, packed_obs=True, layers=[512],
-                               seed=seed)
-    return DQNAgent(ObservationSpec((1, env_like.obs_len)), ActionSpec(env_like.num_actions), params, device="cuda")
-
-
-def _team(name, env_like):
-    from hanabi_agents.rule_based import RulebasedAgent, predefined_rules as PR
-
-    if name == "piers_piers":
-        return [RulebasedAgent(PR.piers_rules, seed=11), RulebasedAgent(PR.piers_rules, seed=12)]
-    if name == "iggi_flawed":
-        return [RulebasedAgent(PR.iggi_rules, seed=13), RulebasedAgent(PR.flawed_rules, seed=14)]
-    return [_dqn(env_like, seed=5), RulebasedAgent(PR.piers_rules, seed=15)]
 
 
 @pytest.mark.parametrize("game,players,m,turns", [("Hanabi-Full", 2, 37, 14), ("Hanabi-Full", 3, 21, 15), ("Hanabi-Full", 5, 70, 17),
