@@ -75,7 +75,11 @@ def test_priority_buffer_matches_reference_golden_on_gpu():
 
 
 def _nstep_reference(rew, term, n_ins, cap, size, wp, i, n, gamma):
-    """Plain-Python n-step walk (hanabi_agents/rainbow/replay_memory.py:316-345 semantics on our ring)."""
+    """Plain-Python n-step walk (hanabi_agents/rainbow/replay_memory.py:316-345 semantics on our ring).
+
+    This restates the ring formula of gather_nstep_dev itself (distance to the write pointer, successor n_ins slots on): it is
+    the same-formula check. The independent one is the trajectory oracle (oracle/replay_oracle.py), which follows each game's
+    own transitions: tests/test_replay_oracle_cpu.py on the host, tests/test_replay_kernels_oracle.py on the GPU."""
     ahead = (wp - 1 - i) % cap if size >= cap else size - 1 - i
     j, R, g, m = i, rew[i], gamma, 1
     while m < n and not term[j] and m * n_ins <= ahead:
