@@ -493,9 +493,11 @@ int hb_thin_gemm(const void* x_dev, const void* wt_dev, const void* bias_dev, vo
  *            entry 1 on rows [0, batch) not at all, and of entry 0 on rows [0, batch) the 16-column tiles that hold the n_atoms
  *            columns [act[b] * n_atoms, (act[b] + 1) * n_atoms) of each sample b (grouped by action inside the kernel; act_dev
  *            int32 [batch]; values outside [0, n_actions) select nothing). batch <= 256, n_actions, n_atoms <= 64
- * batch % 32 == 0, n % 32 == 0 (layer 1: n % 64 == 0), k % 32 == 0. One wavefront per workgroup, at most 1 024 workgroups,
- * 128 B of LDS: it runs beside the policy kernel like hb_thin_gemm, with 384 (layer 1) / <= 596 (layer 2) wavefronts at the
- * 2-player shape instead of 1 024, each with the K steps of one product.                                                      */
+ * batch % 32 == 0, n % 16 == 0 (layer 1: n % 32 == 0, so that the online half [0, n / 2) is whole 16-column tiles: n = 96 is
+ * computed, three tiles of the online half on rows [0, batch)), k % 32 == 0 (an odd number of 32-wide K steps included).
+ * One wavefront per workgroup, at most 1 024 workgroups, 128 B of LDS: it runs beside the policy kernel like hb_thin_gemm, with
+ * 768 (layer 1) / 582 (layer 2, two units each) wavefronts at the 2-player shape instead of 1 024, each unit with the K steps
+ * of one product.                                                                                                             */
 int hb_thin_forward(int32_t layer, const void* x_dev, const void* wt_dev, const void* bias_dev, void* out_dev, const int32_t* act_dev,
                     int64_t batch, int32_t n, int32_t k, int32_t ldx, int32_t ldw, int32_t ldo, int64_t x_batch_stride,
                     int64_t w_batch_stride, int64_t out_batch_stride, int32_t n_actions, int32_t n_atoms, int32_t relu, void* stream);

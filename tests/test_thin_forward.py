@@ -86,6 +86,7 @@ def test_bit_equal_to_thin_gemm_where_it_writes(dtype, players, B, kind):
     lg = torch.full((2, 2 * B, Np), float("nan"), dtype=torch.float32, device="cuda")
     K.check(L.hb_thin_forward(2, _ptr(h_ref), _ptr(w2t), _ptr(b2), _ptr(lg), _ptr(act), B, Np, H, 2 * H, H, Np, H, Np * H,
                               2 * B * Np, A, K51, 2 | f16, s))
+    # (need / may: tests/test_thin_forward_cpu.py holds oracle/thin_forward_oracle.py's masks to these expressions; change both)
     cols = torch.arange(Np, device="cuda")
     a64 = act.long()
     need = (cols[None, :] >= (a64 * K51)[:, None]) & (cols[None, :] < ((a64 + 1) * K51)[:, None])          # what the loss reads
