@@ -7,6 +7,8 @@
 // workgroup (LDS), and added to HBM with ONE atomic per workgroup and counter from at most 128 workgroups: thousands of
 // atomics on one address cost ~12 ns each (env_kernel.hpp, the episode statistics). Measured: one atomic per wave and
 // counter cost 22-25 us per turn at 32 768 games (512 waves on the same few addresses) against 7 us at 4 096.
+//
+// The partner-response counts (hb_eval_response_tally, issued between the env step and the tally) are at the end of the file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -185,6 +187,120 @@ extern "C" int hb_eval_tally_grouped(const hb_config* cfg, int64_t n_blocks, int
                                  length_dev, counters_dev);
   const dim3 grid(static_cast<unsigned>(std::min<int64_t>((block_games + 255) / 256, kMaxBlocks)), static_cast<unsigned>(n_blocks));
   hipLaunchKernelGGL(eval_tally_grouped_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+// ---- partner-response counts (hb_eval_response_tally) -------------------------------------------------------------------------
+// Issued once per turn between the env step and that turn's hb_eval_tally: resp[seat][prev + 1][uid] += 1 for every game still live
+// (bit 7 of done clear: the tally of this turn has not run yet, so a game's last move is counted), then prev[g] = uid.
+//
+// One lane per game, grid-stride, at most 128 workgroups per block of games. Each workgroup keeps the (A + 1) * A bins of its seat's
+// slab as int32 in LDS (420 bins at 2 players, 2 352 at 5 players; 2 550 = 10.2 KB at the largest valid configuration): zeroed,
+// barrier, one LDS add per counted game, barrier, then one 64-bit global atomic per non-zero bin and workgroup. Only the [seat] slab
+// is touched. Every sum is an integer sum, so the result does not depend on the order of the adds: it is bit-reproducible.
+namespace {
+
+constexpr int kMaxRespBins = 51 * 50;   // (A + 1) * A at A = 2 * 5 + 4 * (5 + 5), the largest hb_num_actions of a valid config
+
+struct RespArgs {
+  long long n;
+  int P, A, seat;
+  const int32_t* actions;
+  const uint8_t* done;
+  int32_t* prev;
+  unsigned long long* resp;
+};
+
+__device__ __forceinline__ void response_body(const RespArgs& a) {
+  __shared__ unsigned int hist[kMaxRespBins];
+  const int bins = (a.A + 1) * a.A;   // <= kMaxRespBins (checked on the host)
+  for (int i = threadIdx.x; i < bins; i += 256) hist[i] = 0;
+  __syncthreads();
+  for (long long g = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x; g < a.n; g += static_cast<long long>(gridDim.x) * 256) {
+    if (a.done[g] & 0x80u) continue;   // finished before this turn: not counted, not written
+    const int u = a.actions[g];
+    if (u < 0 || u >= a.A) continue;   // not a move: not counted, prev stays
+    const int p = a.prev[g];
+    if (p >= -1 && p < a.A) atomicAdd(&hist[(p + 1) * a.A + u], 1u);   // (a prev outside -1 .. A-1 is the caller's error: no bin)
+    a.prev[g] = u;
+  }
+  __syncthreads();
+  unsigned long long* out = a.resp + static_cast<long long>(a.seat) * bins;
+  for (int i = threadIdx.x; i < bins; i += 256) {
+    const unsigned int v = hist[i];
+    if (v) atomicAdd(out + i, static_cast<unsigned long long>(v));
+  }
+}
+
+__global__ void __launch_bounds__(256) eval_response_kernel(RespArgs a) { response_body(a); }
+
+// hb_eval_response_tally_grouped: blockIdx.y selects a block of a0.n games and its own [P][A + 1][A] counts
+__global__ void __launch_bounds__(256) eval_response_grouped_kernel(RespArgs a0) {
+  const long long off = static_cast<long long>(blockIdx.y) * a0.n;
+  RespArgs a = a0;
+  a.actions += off; a.done += off; a.prev += off;
+  a.resp += static_cast<long long>(blockIdx.y) * a0.P * ((a0.A + 1) * a0.A);
+  response_body(a);
+}
+
+int check_response(const hb_config* cfg, int64_t n_games, int32_t seat, const int32_t* actions_dev, const uint8_t* done_dev,
+                   int32_t* prev_dev, int64_t* resp_dev) {
+  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  if (n_games < 0) return hb::fail(HB_ERR_INVALID, "n_games must be >= 0");
+  if (seat < 0 || seat >= cfg->players) return hb::fail(HB_ERR_INVALID, "seat %d out of range for %d players", seat, cfg->players);
+  if (!actions_dev || !done_dev || !prev_dev || !resp_dev) return hb::fail(HB_ERR_INVALID, "null argument");
+  const int A = hb_num_actions(cfg);
+  if ((A + 1) * A > kMaxRespBins) return hb::fail(HB_ERR_INVALID, "internal: %d response bins exceed the kernel's %d", (A + 1) * A, kMaxRespBins);
+  return HB_OK;
+}
+
+RespArgs response_args(const hb_config* cfg, int64_t n_games, int32_t seat, const int32_t* actions_dev, const uint8_t* done_dev,
+                       int32_t* prev_dev, int64_t* resp_dev) {
+  RespArgs a{};
+  a.n = n_games;
+  a.P = cfg->players;
+  a.A = hb_num_actions(cfg);
+  a.seat = seat;
+  a.actions = actions_dev; a.done = done_dev; a.prev = prev_dev;
+  a.resp = reinterpret_cast<unsigned long long*>(resp_dev);
+  return a;
+}
+
+}  // namespace
+
+extern "C" int hb_eval_response_bins(const hb_config* cfg) {
+  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  const int A = hb_num_actions(cfg);
+  return (A + 1) * A;
+}
+
+extern "C" int hb_eval_response_tally(const hb_config* cfg, int64_t n_games, int32_t seat, const int32_t* actions_dev,
+                                      const uint8_t* done_dev, int32_t* prev_dev, int64_t* resp_dev, void* stream) {
+  if (int rc = check_response(cfg, n_games, seat, actions_dev, done_dev, prev_dev, resp_dev)) return rc;
+  if (n_games == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  const RespArgs a = response_args(cfg, n_games, seat, actions_dev, done_dev, prev_dev, resp_dev);
+  const unsigned blocks = static_cast<unsigned>(std::min<int64_t>((n_games + 255) / 256, kMaxBlocks));
+  hipLaunchKernelGGL(eval_response_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+extern "C" int hb_eval_response_tally_grouped(const hb_config* cfg, int64_t n_blocks, int64_t block_games, int32_t seat,
+                                              const int32_t* actions_dev, const uint8_t* done_dev, int32_t* prev_dev, int64_t* resp_dev,
+                                              void* stream) {
+  if (int rc = check_response(cfg, block_games, seat, actions_dev, done_dev, prev_dev, resp_dev)) return rc;
+  if (n_blocks < 0 || n_blocks > 65535) return hb::fail(HB_ERR_INVALID, "n_blocks must be 0..65535 (one grid row per block)");
+  if (block_games >= (int64_t{1} << 31) || n_blocks * block_games >= (int64_t{1} << 31))
+    return hb::fail(HB_ERR_INVALID, "n_blocks * block_games must be < 2^31");
+  if (n_blocks == 0 || block_games == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  const RespArgs a = response_args(cfg, block_games, seat, actions_dev, done_dev, prev_dev, resp_dev);
+  const dim3 grid(static_cast<unsigned>(std::min<int64_t>((block_games + 255) / 256, kMaxBlocks)), static_cast<unsigned>(n_blocks));
+  hipLaunchKernelGGL(eval_response_grouped_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
   HB_HIP(hipGetLastError());
   return HB_OK;
 }

@@ -198,6 +198,9 @@ SIGNATURES = {
     "hb_eval_counters": (C.c_int, [_CFG]),
     "hb_eval_tally": (C.c_int, [_CFG, _I64, _I32, _I32] + [_P] * 8 + [_P]),
     "hb_eval_tally_grouped": (C.c_int, [_CFG, _I64, _I64, _I32, _I32] + [_P] * 8 + [_P]),
+    "hb_eval_response_bins": (C.c_int, [_CFG]),
+    "hb_eval_response_tally": (C.c_int, [_CFG, _I64, _I32] + [_P] * 4 + [_P]),
+    "hb_eval_response_tally_grouped": (C.c_int, [_CFG, _I64, _I64, _I32] + [_P] * 4 + [_P]),
     "hb_train_counters": (C.c_int, [_CFG]),
     "hb_train_tally_init": (C.c_int, [_CFG, _P, _I64, _P, _P, _P]),
     "hb_train_tally": (C.c_int, [_CFG, _I64, _I32] + [_P] * 5 + [_I32] + [_P] * 3 + [_P]),

@@ -24,16 +24,21 @@ teams on the same deals and returns one `EvalResult` per team, each equal to wha
 * Seeds, draws and game ids are those of Evaluator.run: Philox seed = the evaluator's seed, draw = turn + 1; a DQN agent keys
   its row r by its own first_game_id + r, a rule agent by the evaluator's first_game_id + r. No agent's draw counter,
   histogram, noise or buffers move.
+* `responses=True`: Evaluator's partner-response counts, per team: one hb_eval_response_tally_grouped per turn (a block of counts
+  per team) between the env step and the grouped tally. Every team's EvalResult carries its `responses`;
+  `CrossPlayResult.responses` stacks them in team order and `convention_distance()` compares the teams' response rows. As in
+  Evaluator, moves of colour-shuffled seats are in their mover's frame (hanabi_hip.symmetry).
 """
 import ctypes as C
 import math
 import weakref
 
+import numpy as np
 import torch
 
 from . import _capi as K
 from .env import HanabiEnv
-from .evaluate import EvalResult, eval_config, max_turns, shuffle_mask
+from .evaluate import EvalResult, eval_config, max_turns, normalize_rows, shuffle_mask, uid_kinds
 
 TILE = 128   # rows per workgroup of the one-kernel actor, and per hb_fused_tile
 
@@ -79,11 +84,47 @@ def plan_chunks(n_teams, n_pad, max_rows):
     return [(s, min(per, n_teams - s)) for s in range(0, n_teams, per)]
 
 
+def convention_distance(counts):
+    """Occupancy-weighted total variation between teams' response rows. counts: [T, P, A + 1, A] response counts (one
+    EvalResult.responses per team). Returns a symmetric [T, T] float64 matrix: with M_i team i's row-normalised counts and
+    n_i[p, r] its row sums,
+
+        D(i, j) = sum over the rows (p, r) both teams have counts in of  w[p, r] * 1/2 * sum_a |M_i[p, r, a] - M_j[p, r, a]|,
+        w[p, r] = (n_i + n_j)[p, r] / (the sum of n_i + n_j over those rows)
+
+    0 for identical play, at most 1 (disjoint answers on every shared row), NaN when the two teams share no row."""
+    c = np.asarray(counts)
+    if c.ndim != 4 or c.shape[2] != c.shape[3] + 1:
+        raise ValueError(f"counts must be [T, P, A + 1, A], got {c.shape}")
+    n = c.sum(-1).astype(np.float64)   # [T, P, A + 1]
+    m = normalize_rows(c)
+    T = c.shape[0]
+    d = np.full((T, T), np.nan)
+    for i in range(T):
+        for j in range(i, T):
+            shared = (n[i] > 0) & (n[j] > 0)
+            if not shared.any():
+                continue
+            w = (n[i] + n[j])[shared]
+            tv = 0.5 * np.abs(m[i][shared] - m[j][shared]).sum(-1)
+            d[i, j] = d[j, i] = float((w * tv).sum() / w.sum())
+    return d
+
+
 class CrossPlayResult:
-    """teams: the P-tuples of pool indices, results: one EvalResult per team (the class Evaluator returns), k: pool size."""
+    """teams: the P-tuples of pool indices, results: one EvalResult per team (the class Evaluator returns), k: pool size.
+    responses: [T, P, A + 1, A] int64 numpy, the teams' response counts in team order (CrossPlay(responses=True)), else None."""
 
     def __init__(self, teams, results, k, players, default):
         self.teams, self.results, self.k, self.players, self.default = list(teams), list(results), int(k), int(players), bool(default)
+        on = bool(self.results) and all(r.responses is not None for r in self.results)
+        self.responses = np.stack([r.responses for r in self.results]) if on else None
+
+    def convention_distance(self):
+        """[T, T] float64 over the result's teams (team order): the module's convention_distance of their response counts."""
+        if self.responses is None:
+            raise ValueError("no response counts: run CrossPlay(responses=True)")
+        return convention_distance(self.responses)
 
     def _matrix(self, value):
         if not self.default:
@@ -132,18 +173,23 @@ class _Chunk:
         self.counters = torch.empty_like(self.counters0)
         self.actions = torch.zeros(cp.max_turns if cp.record_actions else 1, rows, dtype=torch.int32, device=dev)
         self.q = torch.empty(rows, self.env.num_actions, dtype=torch.float32, device=dev)
+        if cp.responses:
+            A = self.env.num_actions
+            self.prev = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+            self.resp = torch.zeros(nb, cp.players, A + 1, A, dtype=torch.int64, device=dev)
 
 
 class CrossPlay:
     """Plays every team of a pool on the same `n_games` deals; see the module docstring.
 
-    game / players / config / seed / first_game_id / record_actions / check_every: as Evaluator. max_rows: games per chunk
+    game / players / config / seed / first_game_id / record_actions / check_every / responses: as Evaluator. max_rows: games per chunk
     (teams of one chunk run in lock-step; more teams than fit take several chunks one after another)."""
 
     def __init__(self, game="Hanabi-Full", players=2, n_games=4096, seed=1, first_game_id=0, max_rows=262144, record_actions=False,
-                 device=None, config=None, check_every=8, color_shuffle=False):
+                 device=None, config=None, check_every=8, color_shuffle=False, responses=False):
         n_games = int(n_games)
         self.color_shuffle = bool(color_shuffle)
+        self.responses = bool(responses)
         if n_games < 1:
             raise ValueError(f"n_games must be >= 1, got {n_games}")
         if int(max_rows) < 1:
@@ -299,6 +345,11 @@ class CrossPlay:
         tally_bufs = tuple(K.dptr(x) for x in (env.reward, env.terminal, env.score, ch.done, ch.final_score, ch.length, ch.counters))
         rules_p = K.dptr(rules_dev)
         n_rules_p = K.dptr(n_rules_dev)
+        resp_bufs = None
+        if self.responses:
+            ch.prev.fill_(-1)
+            ch.resp.zero_()
+            resp_bufs = tuple(K.dptr(x) for x in (ch.done, ch.prev, ch.resp))
         live, t = nb * n, 0
         while t < self.max_turns:
             seat = t % P
@@ -315,6 +366,8 @@ class CrossPlay:
             for b, a, kind in plan["generic"]:
                 self._generic_moves(ch, b, a, kind, t, act)
             env.step(act)
+            if resp_bufs is not None:   # before the tally: `done` still says which games were finished before this turn
+                K.check(L.hb_eval_response_tally_grouped(cfg_ref, nb, n_pad, seat, K.dptr(act), *resp_bufs, K.current_stream()))
             K.check(L.hb_eval_tally_grouped(cfg_ref, nb, n_pad, seat, t, K.dptr(act), *tally_bufs, K.current_stream()))
             t += 1
             if t % self.check_every == 0 or t == self.max_turns:
@@ -330,6 +383,8 @@ class CrossPlay:
         c = ch.counters.cpu()
         fs, ln = ch.final_score.cpu(), ch.length.cpu()
         B = self.max_score + 1
+        resp = ch.resp.cpu().numpy() if self.responses else None
+        kinds = uid_kinds(P, cfg.colors, cfg.hand_size, env.num_actions)
         out = []
         for b in range(nb):
             r0 = b * n_pad
@@ -340,7 +395,8 @@ class CrossPlay:
             out.append(EvalResult(fs[r0:r0 + n], lengths, self.max_score, histogram=cb[1:1 + B], bombouts=int(cb[1 + B]),
                                   moves=cb[2 + B:2 + B + 4 * P].view(P, 4), misplays=cb[2 + B + 4 * P:2 + B + 5 * P],
                                   actions=ch.actions[:tb, r0:r0 + n].clone() if self.record_actions else None, turns=tb,
-                                  perms=perms[r0:r0 + n] if perms is not None and masks[b] else None))
+                                  perms=perms[r0:r0 + n] if perms is not None and masks[b] else None,
+                                  responses=resp[b] if resp is not None else None, kinds=kinds))
         return out
 
     def _generic_moves(self, ch, b, agent, kind, t, act):

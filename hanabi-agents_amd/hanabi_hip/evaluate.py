@@ -18,11 +18,19 @@ the separate evaluation env of its external session). `Evaluator` does that with
   (the "OP score"); rule-based seats read the true state and stay unshuffled. The permutations are those
   of the deals (seed, game id, deal counter 1, seat) and come back as `EvalResult.perms`; recorded actions are in each seat's
   own frame.
+* `responses=True`: the partner-response counts, `EvalResult.responses[seat, prev + 1, uid]` = how often `seat` answered the
+  move `prev` made just before its own (row 0: the first move of a game) with `uid`. One more small launch per turn,
+  `hb_eval_response_tally`, between the env step and `hb_eval_tally`; nothing else changes, and with the switch off nothing is
+  launched or allocated for it. `EvalResult.response_matrix()` normalises the rows to P(my move | the move before mine), the
+  conditional action matrix of the Other-Play and SAD papers. With `color_shuffle=True` the combination is allowed, but every
+  move is in its mover's own frame: `prev` is in the partner's frame and `uid` in mine, so reveal-colour rows and columns of
+  shuffled seats are not in a common frame (hanabi_hip.symmetry maps uids between frames; that mapping is not applied here).
 """
 import ctypes as C
 import math
 import weakref
 
+import numpy as np
 import torch
 
 from . import _capi as K
@@ -62,6 +70,41 @@ def eval_config(game, players, config=None):
 MOVE_KINDS = ("discard", "play", "reveal_color", "reveal_rank")
 
 
+def uid_kinds(players, colors, hand_size, num_actions):
+    """[A] int64: the kind (index into MOVE_KINDS) of every move uid, App. A.2 order: H discards, H plays, (P - 1) * C colour
+    reveals, then the rank reveals. The decoding hb_eval_tally's move-kind counters use."""
+    u = np.arange(int(num_actions))
+    h, pc = int(hand_size), (int(players) - 1) * int(colors)
+    return np.where(u < h, 0, np.where(u < 2 * h, 1, np.where(u < 2 * h + pc, 2, 3))).astype(np.int64)
+
+
+def response_counts(actions, lengths, players, num_actions, first_seat=0):
+    """The partner-response counts of a recorded action log, in plain numpy (what hb_eval_response_tally accumulates on the
+    device). actions [T, n] int: turn t is seat (first_seat + t) % P's move in every game; game g is counted for
+    t < lengths[g]. Returns [P, A + 1, A] int64: out[seat, prev + 1, uid], prev = the game's previous counted move, -1 (row 0)
+    at its first. A uid outside 0 .. A-1 is not counted and does not become `prev`."""
+    actions = np.asarray(actions)
+    lengths = np.asarray(lengths).astype(np.int64)
+    P, A = int(players), int(num_actions)
+    if actions.ndim != 2 or lengths.shape != (actions.shape[1],):
+        raise ValueError("actions [T, n] and lengths [n]")
+    out = np.zeros((P, A + 1, A), np.int64)
+    prev = np.full(actions.shape[1], -1, np.int64)
+    for t in range(actions.shape[0]):
+        u = actions[t].astype(np.int64)
+        ok = (t < lengths) & (u >= 0) & (u < A)
+        np.add.at(out[(int(first_seat) + t) % P], (prev[ok] + 1, u[ok]), 1)
+        prev[ok] = u[ok]
+    return out
+
+
+def normalize_rows(counts):
+    """counts [..., A] -> float64 rows divided by their sums; a row without counts is NaN."""
+    c = np.asarray(counts, np.float64)
+    tot = c.sum(-1, keepdims=True)
+    return np.divide(c, tot, out=np.full_like(c, np.nan), where=tot > 0)
+
+
 def shuffle_mask(team):
     """Seat mask of a team's colour-shuffled seats: those whose agent reads vectorised observations (DQN-style agents).
     Rule-based agents read the true state rows and keep the true colours."""
@@ -74,10 +117,12 @@ class EvalResult:
     scores [n] int32 final scores (0 after a bomb-out), lengths [n] int32 turns played, histogram [max_score + 1] int64,
     bombouts (games that lost every life), moves [P, 4] int64 per seat and kind (MOVE_KINDS), misplays [P] int64 per seat,
     actions [turns, n] int32 (record_actions only; rows of finished games hold moves the env ignored), turns = turns played,
-    perms [n, P, C] uint8 (colour-shuffled evaluations only): perms[g, p, c] = the colour seat p saw for true colour c."""
+    perms [n, P, C] uint8 (colour-shuffled evaluations only): perms[g, p, c] = the colour seat p saw for true colour c.
+    responses [P, A + 1, A] int64 numpy (responses=True only, else None): responses[p, prev + 1, uid] = how often seat p played
+    uid right after the move prev (row 0: first move of a game); kinds [A] = the move kind of every uid (uid_kinds)."""
 
     def __init__(self, scores, lengths, max_score, histogram=None, bombouts=0, moves=None, misplays=None, actions=None, turns=None,
-                 perms=None):
+                 perms=None, responses=None, kinds=None):
         self.scores = torch.as_tensor(scores).to("cpu", torch.int32)
         self.lengths = torch.as_tensor(lengths).to("cpu", torch.int32)
         n = self.scores.numel()
@@ -92,6 +137,31 @@ class EvalResult:
         self.actions = None if actions is None else actions.cpu()
         self.turns = int(turns) if turns is not None else int(self.lengths.max())
         self.perms = None if perms is None else torch.as_tensor(perms).to("cpu", torch.uint8)
+        if responses is None:
+            self.responses = None
+        else:
+            r = responses.cpu().numpy() if isinstance(responses, torch.Tensor) else np.asarray(responses)
+            if r.ndim != 3 or r.shape[1] != r.shape[2] + 1:
+                raise ValueError(f"responses must be [P, A + 1, A], got {r.shape}")
+            self.responses = r.astype(np.int64, copy=True)
+        self.kinds = None if kinds is None else np.asarray(kinds, np.int64)
+
+    def response_matrix(self, seat=None, kinds=False):
+        """P(my move | the move made just before mine) as float64 [A + 1, A] (seat=None: the seats' counts pooled, then
+        normalised) — row 0 is the first move of a game; every row is divided by its sum and a row without counts is NaN.
+        kinds=True: both axes collapsed to move kinds first, [5, 4] = (none, *MOVE_KINDS) x MOVE_KINDS."""
+        if self.responses is None:
+            raise ValueError("no response counts: evaluate with responses=True")
+        c = self.responses
+        if kinds:
+            if self.kinds is None or self.kinds.shape != (c.shape[2],):
+                raise ValueError("kinds=True needs the uid kinds of the game (EvalResult(kinds=uid_kinds(...)))")
+            rows = np.concatenate(([0], 1 + self.kinds))
+            k = np.zeros((c.shape[0], 5, 4), np.int64)
+            np.add.at(k, (slice(None), rows[:, None], self.kinds[None, :]), c)
+            c = k
+        c = c.sum(0) if seat is None else c[int(seat)]
+        return normalize_rows(c)
 
     @property
     def n_games(self):
@@ -127,6 +197,8 @@ class EvalResult:
             d["moves"] = [dict(zip(MOVE_KINDS, row)) for row in self.moves.tolist()]
         if self.misplays is not None:
             d["misplays"] = self.misplays.tolist()
+        if self.responses is not None:
+            d["responses"] = self.responses.tolist()
         return d
 
     def __repr__(self):
@@ -140,11 +212,12 @@ class Evaluator:
     never auto-reset and score without leniency). first_game_id: global id of game 0 (keys the deals and the agents' draws)."""
 
     def __init__(self, game="Hanabi-Full", players=2, n_games=4096, seed=1, first_game_id=0, device=None, record_actions=False,
-                 config=None, check_every=8, color_shuffle=False):
+                 config=None, check_every=8, color_shuffle=False, responses=False):
         n_games = int(n_games)
         if n_games < 1:
             raise ValueError(f"n_games must be >= 1, got {n_games}")
         self.color_shuffle = bool(color_shuffle)
+        self.responses = bool(responses)
         cfg = eval_config(game, players, config)
         self.cfg = cfg
         self.players = cfg.players
@@ -176,6 +249,10 @@ class Evaluator:
         self.counters = torch.zeros(self.n_counters, dtype=torch.int64, device=dev)
         self.actions = (torch.zeros(self.max_turns, self.n, dtype=torch.int32, device=dev) if self.record_actions
                         else torch.zeros(1, self.n, dtype=torch.int32, device=dev))
+        if self.responses:
+            A = env.num_actions
+            self.prev = torch.full((self.n,), -1, dtype=torch.int32, device=dev)
+            self.resp = torch.zeros(self.players, A + 1, A, dtype=torch.int64, device=dev)
 
     @torch.no_grad()
     def run(self, agents):
@@ -203,6 +280,11 @@ class Evaluator:
         P, n = self.players, self.n
         cfg_ref = C.byref(cfg)
         bufs = tuple(K.dptr(t) for t in (env.reward, env.terminal, env.score, self.done, self.final_score, self.length, self.counters))
+        resp_bufs = None
+        if self.responses:
+            self.prev.fill_(-1)
+            self.resp.zero_()
+            resp_bufs = tuple(K.dptr(t) for t in (self.done, self.prev, self.resp))
         live, t = self.n, 0
         while t < self.max_turns:
             seat = t % P
@@ -213,6 +295,8 @@ class Evaluator:
             else:
                 agent.eval_moves(env, self.seed, t + 1, act)
             env.step(act)
+            if resp_bufs is not None:   # before the tally: `done` still says which games were finished before this turn
+                K.check(L.hb_eval_response_tally(cfg_ref, n, seat, K.dptr(act), *resp_bufs, K.current_stream()))
             K.check(L.hb_eval_tally(cfg_ref, n, seat, t, K.dptr(act), *bufs, K.current_stream()))
             t += 1
             if t % self.check_every == 0 or t == self.max_turns:
@@ -228,4 +312,6 @@ class Evaluator:
         B = self.max_score + 1
         return EvalResult(self.final_score, self.length, self.max_score, histogram=c[1:1 + B], bombouts=int(c[1 + B]),
                           moves=c[2 + B:2 + B + 4 * P].view(P, 4), misplays=c[2 + B + 4 * P:2 + B + 5 * P],
-                          actions=self.actions[:t].clone() if self.record_actions else None, turns=t, perms=perms)
+                          actions=self.actions[:t].clone() if self.record_actions else None, turns=t, perms=perms,
+                          responses=self.resp if self.responses else None,
+                          kinds=uid_kinds(P, cfg.colors, cfg.hand_size, env.num_actions))

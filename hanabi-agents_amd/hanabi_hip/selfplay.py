@@ -399,22 +399,23 @@ class SelfPlaySession:
         self.flush()
 
     # ---- greedy evaluation (hanabi_hip.evaluate) -----------------------------------------------------------------
-    def evaluate(self, n_games=4096, seed=1, partners=None, color_shuffle=False):
+    def evaluate(self, n_games=4096, seed=1, partners=None, color_shuffle=False, responses=False):
         """Greedy mean score of the session's agents (or of `partners`: one agent per seat, DQN and rule-based mixed) over a
         fixed set of `n_games` fresh deals keyed by `seed`: an EvalResult. Updates in flight are completed first (flush());
         the session's env, counters, command arrays and agents are left exactly as they were, so training continues as if
-        the evaluation had not happened. The evaluator (its env and buffers) is kept for the next call of the same size."""
+        the evaluation had not happened. The evaluator (its env and buffers) is kept for the next call of the same size.
+        responses=True: the result carries the partner-response counts (Evaluator's `responses`)."""
         if partners is None and self.pool is not None:
             raise ValueError("a session with a partner pool is evaluated member by member: use evaluate_pool()")
         self.flush()
         from .evaluate import Evaluator
 
-        key = (int(n_games), int(seed), bool(color_shuffle))
+        key = (int(n_games), int(seed), bool(color_shuffle), bool(responses))
         ev = self._evaluators.get(key)
         if ev is None:
             rank = self.env.first_game_id // self.env.n if self.env.n else 0   # (data-parallel: each rank its own deals)
             ev = self._evaluators[key] = Evaluator(config=self.env.cfg, n_games=n_games, seed=seed, first_game_id=rank * int(n_games),
-                                                   device=self.env.device, color_shuffle=color_shuffle)
+                                                   device=self.env.device, color_shuffle=color_shuffle, responses=responses)
         return ev.run(self.agents if partners is None else partners)
 
     def search(self, blueprint=None, replicas=32, seed=1, draw=None, history=None, oversample=8):
@@ -443,19 +444,20 @@ class SelfPlaySession:
         return rs.run(self.env.export_state(), self.env.legal.clone(), self.agents if blueprint is None else blueprint,
                       self.env_steps if draw is None else int(draw), history=history)
 
-    def crossplay(self, pool, n_games=4096, seed=1, teams=None, color_shuffle=False):
+    def crossplay(self, pool, n_games=4096, seed=1, teams=None, color_shuffle=False, responses=False):
         """Cross-play of a pool of agents (the session's own and others, DQN and rule-based mixed) on `n_games` fresh deals keyed
         by `seed`: a hanabi_hip.crossplay.CrossPlayResult with one EvalResult per team. As evaluate(): updates in flight are
-        completed first, the session and its agents are left exactly as they were, and the CrossPlay is kept for the next call."""
+        completed first, the session and its agents are left exactly as they were, and the CrossPlay is kept for the next call.
+        responses=True: per-team partner-response counts and CrossPlayResult.convention_distance()."""
         self.flush()
         from .crossplay import CrossPlay
 
-        key = (int(n_games), int(seed), bool(color_shuffle))
+        key = (int(n_games), int(seed), bool(color_shuffle), bool(responses))
         cp = self._crossplays.get(key)
         if cp is None:
             rank = self.env.first_game_id // self.env.n if self.env.n else 0   # (data-parallel: each rank its own deals)
             cp = self._crossplays[key] = CrossPlay(config=self.env.cfg, n_games=n_games, seed=seed, first_game_id=rank * int(n_games),
-                                                   device=self.env.device, color_shuffle=color_shuffle)
+                                                   device=self.env.device, color_shuffle=color_shuffle, responses=responses)
         return cp.run(pool, teams=teams)
 
     def evaluate_pool(self, n_games=4096, seed=1, color_shuffle=False):
@@ -474,7 +476,7 @@ class SelfPlaySession:
         agents = others + list(self.pool.members)
         seat_idx = [None if a is self.pool else next(i for i, o in enumerate(others) if a is o) for a in self.agents]
         teams = [tuple(len(others) + k if i is None else i for i in seat_idx) for k in range(len(self.pool.members))]
-        key = (int(n_games), int(seed), bool(color_shuffle))
+        key = (int(n_games), int(seed), bool(color_shuffle), False)
         cp = self._crossplays.get(key)
         if cp is None:
             rank = self.env.first_game_id // self.env.n if self.env.n else 0   # (data-parallel: each rank its own deals)

@@ -746,6 +746,32 @@ int hb_eval_tally_grouped(const hb_config* cfg, int64_t n_blocks, int64_t block_
                           const int32_t* actions_dev, const float* reward_dev, const int8_t* terminal_dev, const int8_t* score_dev,
                           uint8_t* done_dev, int8_t* final_score_dev, int16_t* length_dev, int64_t* counters_dev, void* stream);
 
+/* ---- partner-response counts (csrc/eval.hip) ------------------------------------------------------------------------------
+ * The conditional action counts "my move given the move made just before mine" of an evaluation. hb_eval_response_tally is
+ * issued once per turn AFTER hb_env_step and BEFORE that turn's hb_eval_tally, on the same stream: bit 7 of done_dev[g] then
+ * still means "game g was finished before this turn", so a game's last move is counted.
+ *   actions_dev [n] int32 the moves just stepped (seat `seat` made them in every game)
+ *   done_dev    [n] uint8 hb_eval_tally's status bytes; read only, and only bit 7
+ *   prev_dev    [n] int32 the previous move of each game, set to -1 by the caller before turn 0
+ *   resp_dev    [P][A + 1][A] int64 the counts (A = hb_num_actions(cfg)), zeroed by the caller before turn 0
+ * For every game with bit 7 of done clear and 0 <= uid < A: resp[seat][prev + 1][uid] += 1, then prev[g] = uid. Row 0
+ * (prev = -1) holds the first move of a game. A uid outside 0 .. A-1 is not counted and leaves prev[g] as it was; a finished
+ * game is neither counted nor written. (A prev outside -1 .. A-1, which only a caller can put there, selects no bin.)
+ * One lane per game, grid-stride, <= 128 workgroups; each workgroup fills an LDS histogram of hb_eval_response_bins(cfg)
+ * int32 bins and flushes every non-zero bin with one 64-bit global atomic. Only the [seat] slab is touched. All sums are
+ * integer sums: the result does not depend on the order of the adds. n == 0 is a no-op. Without a device: HB_ERR_NO_DEVICE
+ * (arguments are checked first).                                                                                             */
+int hb_eval_response_bins(const hb_config* cfg); /* bins per seat: (A + 1) * A */
+int hb_eval_response_tally(const hb_config* cfg, int64_t n_games, int32_t seat, const int32_t* actions_dev, const uint8_t* done_dev,
+                           int32_t* prev_dev, int64_t* resp_dev, void* stream);
+/* hb_eval_response_tally over n_blocks blocks of block_games games stepped together (hb_eval_tally_grouped's layout): the
+ * per-game arrays hold the blocks one after another and resp_dev is [n_blocks][P][A + 1][A]. Block b's counts and prev are
+ * exactly what hb_eval_response_tally computes on that block alone; a 2-D grid, one row of workgroups per block.
+ * n_blocks <= 65535 and n_blocks * block_games < 2^31.                                                                       */
+int hb_eval_response_tally_grouped(const hb_config* cfg, int64_t n_blocks, int64_t block_games, int32_t seat,
+                                   const int32_t* actions_dev, const uint8_t* done_dev, int32_t* prev_dev, int64_t* resp_dev,
+                                   void* stream);
+
 /* ---- training statistics against a partner pool (csrc/train_tally.hip) ----------------------------------------------------
  * A training env (auto-reset, lock-step) whose rows are cut into 128-game tiles, each tile owned by one member of a partner pool
  * (hanabi_hip.partner_pool). hb_train_tally is issued once per env step, after the step, on the same stream, and adds what that
