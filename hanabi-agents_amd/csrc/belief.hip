@@ -22,6 +22,12 @@
 // the observer's hand word taken from each candidate, candidate-major (one wavefront per output row, a plain coalesced copy).
 // Select: per root the first `replicas` candidates whose hypothetical partner move equals the real one, ranked by ballot and
 // prefix popcount (one wavefront per root, rows copied with lane j < SW holding word j). No LDS, barrier or atomic either.
+//
+// hb_belief_splice_alive / hb_belief_select_depth: the same belief conditioned on the partner's last `depth` moves. Splice-alive:
+// the splice for an OLDER previous state, in which the observer still held cards it has played or discarded since: the cards of
+// that hand it still holds (the `alive` slots) are a prefix of the candidate's hand in the same order, the others are public and
+// stay the previous row's (the lane of the hand word walks the 5 slots in registers). Select-depth: the selection over `depth`
+// predicates, a candidate's pass count = its leading matches; survivors of the deepest level that has any.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -391,6 +397,144 @@ __global__ void __launch_bounds__(256) belief_select_kernel(SelectArgs a) {
   }
 }
 
+struct SpliceAliveArgs {
+  const uint32_t* prev;
+  const uint8_t* alive;   // may be null: every slot alive
+  const uint32_t* det;
+  uint32_t* out;
+  long long m, n_out;   // n_out = K * m
+  int K, SW, hand_word;
+};
+
+// One wavefront per output row o = k * m + i, lane j < SW moves word j of previous row i. The lane of the hand word rebuilds it:
+// over the occupied slots s of the previous hand, an alive slot takes the next card of candidate (i, k)'s hand (slot j = the
+// number of alive slots before it: what is still held is a prefix of the current hand, in the same order); a dead slot, or one
+// the candidate has no card left for, keeps the previous row's card.
+__global__ void __launch_bounds__(256) belief_splice_alive_kernel(SpliceAliveArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long long o = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (o >= a.n_out || lane >= a.SW) return;
+  const long long k = o / a.m, i = o - k * a.m;
+  uint32_t w = a.prev[i * a.SW + lane];
+  if (lane == a.hand_word) {
+    const uint32_t ch = a.det[(i * a.K + k) * a.SW + lane];
+    const uint32_t alive = a.alive ? a.alive[i] : 0xFFu;
+    int j = 0;
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+      const uint32_t c = (ch >> (5 * j)) & 31u;   // (j <= s <= 4)
+      const bool take = ((w >> (5 * s)) & 31u) != 31u && ((alive >> s) & 1u) && c != 31u;
+      if (take) {
+        w = (w & ~(31u << (5 * s))) | (c << (5 * s));
+        ++j;
+      }
+    }
+  }
+  a.out[o * a.SW + lane] = w;
+}
+
+struct SelectDepthArgs {
+  const uint32_t* src;
+  const uint32_t* det;
+  const uint32_t* weight;
+  const int32_t* hyp;      // [depth][K * m]
+  const int32_t* actual;   // [depth][m]
+  const uint8_t* valid;    // [depth][m]; may be null: every entry valid
+  uint32_t* out;
+  uint32_t* out_weight;
+  int32_t* n_surv;         // [depth][m]
+  int32_t* depth_used;
+  uint8_t* fallback;
+  long long m;
+  int K, R, SW, depth;
+};
+
+constexpr int MAX_DEPTH = 8;
+
+// One wavefront per root, belief_select_kernel over `depth` predicates. L = the leading valid entries of the root (0 when it is
+// not running). Sweep 1: every lane's candidate stays `on` while its moves match, from entry 0 (never, for a weight of 0);
+// cnt[D - 1] = candidates with at least D leading matches, by ballot. used = the deepest level with a survivor (cnt never grows
+// with D). Sweep 2 places the candidates with at least `used` leading matches exactly as belief_select_kernel places its
+// survivors. The loops over the levels are unrolled to MAX_DEPTH with wave-uniform guards, so that act[] and cnt[] stay in
+// registers.
+__global__ void __launch_bounds__(256) belief_select_depth_kernel(SelectDepthArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long long i = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (i >= a.m) return;
+  const uint32_t* det = a.det + i * a.K * a.SW;
+  const uint32_t* w = a.weight + i * a.K;
+  uint32_t* out = a.out + i * a.R * a.SW;
+  uint32_t* ow = a.out_weight + i * a.R;
+  const long long slab = static_cast<long long>(a.K) * a.m;
+  const bool running = ((a.src[i * a.SW] >> 19) & 3u) == 0;
+  int L = 0;
+  if (running) {
+    while (L < a.depth && (!a.valid || a.valid[L * a.m + i] != 0)) ++L;
+  }
+  int32_t act[MAX_DEPTH];
+  int cnt[MAX_DEPTH];
+#pragma unroll
+  for (int d = 0; d < MAX_DEPTH; ++d) {
+    act[d] = d < L ? a.actual[d * a.m + i] : 0;
+    cnt[d] = 0;
+  }
+  for (int k0 = 0; k0 < a.K && L > 0; k0 += 64) {
+    const int k = k0 + lane;
+    const bool live = k < a.K && w[k] != 0u;
+    bool on = live;
+#pragma unroll
+    for (int d = 0; d < MAX_DEPTH; ++d) {
+      if (d < L) {   // (wave-uniform)
+        on = on && a.hyp[d * slab + k * a.m + i] == act[d];   // (read by the lanes still matching only)
+        cnt[d] += __popcll(__ballot(on));
+      }
+    }
+  }
+  int used = 0;
+#pragma unroll
+  for (int d = 0; d < MAX_DEPTH; ++d) used += cnt[d] > 0 ? 1 : 0;
+  int total = 0;
+#pragma unroll
+  for (int d = 0; d < MAX_DEPTH; ++d) {
+    if (d < a.depth && lane == 0) a.n_surv[d * a.m + i] = cnt[d];
+    total = d + 1 == used ? cnt[d] : total;
+  }
+  if (lane == 0) {
+    a.depth_used[i] = used;
+    a.fallback[i] = L == 0 ? 2 : used == 0 ? 1 : 0;
+  }
+  if (used == 0) {   // the unconditioned belief: candidates 0 .. R - 1 as they are
+    for (int r = 0; r < a.R; ++r)
+      if (lane < a.SW) out[r * a.SW + lane] = det[r * a.SW + lane];
+    for (int r = lane; r < a.R; r += 64) ow[r] = w[r];
+    return;
+  }
+  int base = 0;
+  for (int k0 = 0; k0 < a.K && base < a.R; k0 += 64) {
+    const int k = k0 + lane;
+    const uint32_t wk = k < a.K ? w[k] : 0u;
+    bool s = wk != 0u;   // (k >= K: wk = 0, nothing is read)
+#pragma unroll
+    for (int d = 0; d < MAX_DEPTH; ++d) {
+      if (d < used) s = s && a.hyp[d * slab + k * a.m + i] == act[d];
+    }
+    const unsigned long long mask = __ballot(s);
+    const int rank = base + __popcll(mask & ((1ull << lane) - 1ull));
+    if (s && rank < a.R) ow[rank] = wk;
+    int r = base;
+    for (unsigned long long todo = mask; todo && r < a.R; todo &= todo - 1, ++r) {
+      const int kk = k0 + __ffsll(todo) - 1;
+      if (lane < a.SW) out[r * a.SW + lane] = det[kk * a.SW + lane];
+    }
+    base += __popcll(mask);
+  }
+  const uint32_t sj = lane < a.SW ? a.src[i * a.SW + lane] : 0u;
+  for (int r = total; r < a.R; ++r) {   // fewer survivors than replicas: dead copies of the root
+    if (lane < a.SW) out[r * a.SW + lane] = sj;
+    if (lane == 0) ow[r] = 0u;
+  }
+}
+
 int have_device() {
   static const int ndev = [] {
     int n = 0;
@@ -544,6 +688,64 @@ extern "C" int hb_belief_select(const hb_config* cfg, const uint32_t* src_rows_d
   a.K = n_cand; a.R = replicas; a.SW = SW;
   const unsigned blocks = static_cast<unsigned>((m + 3) / 4);   // four wavefronts = four roots per workgroup
   hipLaunchKernelGGL(belief_select_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+extern "C" int hb_belief_splice_alive(const hb_config* cfg, const uint32_t* prev_rows_dev, const uint8_t* alive_dev,
+                                      const uint32_t* det_rows_dev, int64_t m, int32_t seat, int32_t n_cand, uint32_t* out_rows_dev,
+                                      void* stream) {
+  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  if (m < 0) return hb::fail(HB_ERR_INVALID, "m must be >= 0");
+  if (n_cand < 1) return hb::fail(HB_ERR_INVALID, "n_cand must be >= 1, got %d", n_cand);
+  if (seat < 0 || seat >= cfg->players)
+    return hb::fail(HB_ERR_INVALID, "seat %d out of range 0..%d (the observer is not the previous state's current player)", seat,
+                    cfg->players - 1);
+  if (!prev_rows_dev || !det_rows_dev || !out_rows_dev) return hb::fail(HB_ERR_INVALID, "null argument");   // (alive may be null)
+  const int SW = hb_state_words(cfg);
+  if (m > ((static_cast<int64_t>(1) << 31) - 1) / (static_cast<int64_t>(n_cand) * SW))
+    return hb::fail(HB_ERR_INVALID, "m * n_cand * state words must stay below 2^31: split the roots");
+  if (m == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  SpliceAliveArgs a{};
+  a.prev = prev_rows_dev; a.alive = alive_dev; a.det = det_rows_dev; a.out = out_rows_dev;
+  a.m = m;
+  a.n_out = m * n_cand;
+  a.K = n_cand; a.SW = SW;
+  a.hand_word = 10 + seat;
+  const unsigned blocks = static_cast<unsigned>((a.n_out + 3) / 4);   // four wavefronts = four output rows per workgroup
+  hipLaunchKernelGGL(belief_splice_alive_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+extern "C" int hb_belief_select_depth(const hb_config* cfg, const uint32_t* src_rows_dev, const uint32_t* det_rows_dev,
+                                      const uint32_t* weight_dev, const int32_t* hyp_moves_dev, const int32_t* actual_dev,
+                                      const uint8_t* valid_dev, int64_t m, int32_t n_cand, int32_t replicas, int32_t depth,
+                                      uint32_t* out_rows_dev, uint32_t* out_weight_dev, int32_t* n_surv_dev, int32_t* depth_used_dev,
+                                      uint8_t* fallback_dev, void* stream) {
+  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  if (m < 0) return hb::fail(HB_ERR_INVALID, "m must be >= 0");
+  if (replicas < 1) return hb::fail(HB_ERR_INVALID, "replicas must be >= 1, got %d", replicas);
+  if (n_cand < replicas) return hb::fail(HB_ERR_INVALID, "n_cand %d must be >= replicas %d", n_cand, replicas);
+  if (depth < 1 || depth > MAX_DEPTH) return hb::fail(HB_ERR_INVALID, "depth %d out of range 1..%d", depth, MAX_DEPTH);
+  if (!src_rows_dev || !det_rows_dev || !weight_dev || !hyp_moves_dev || !actual_dev || !out_rows_dev || !out_weight_dev || !n_surv_dev ||
+      !depth_used_dev || !fallback_dev)
+    return hb::fail(HB_ERR_INVALID, "null argument");
+  const int SW = hb_state_words(cfg);
+  if (m > ((static_cast<int64_t>(1) << 31) - 1) / (static_cast<int64_t>(n_cand) * SW))
+    return hb::fail(HB_ERR_INVALID, "m * n_cand * state words must stay below 2^31: split the roots");
+  if (m == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  SelectDepthArgs a{};
+  a.src = src_rows_dev; a.det = det_rows_dev; a.weight = weight_dev; a.hyp = hyp_moves_dev; a.actual = actual_dev; a.valid = valid_dev;
+  a.out = out_rows_dev; a.out_weight = out_weight_dev; a.n_surv = n_surv_dev; a.depth_used = depth_used_dev; a.fallback = fallback_dev;
+  a.m = m;
+  a.K = n_cand; a.R = replicas; a.SW = SW; a.depth = depth;
+  const unsigned blocks = static_cast<unsigned>((m + 3) / 4);   // four wavefronts = four roots per workgroup
+  hipLaunchKernelGGL(belief_select_depth_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   HB_HIP(hipGetLastError());
   return HB_OK;
 }

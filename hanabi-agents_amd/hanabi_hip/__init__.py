@@ -5,7 +5,7 @@ PyTorch is used only for device memory and streams: every call hands raw device 
 There is no CPU path: constructing an env or a tree without the compiled library or
 without a GPU raises.
 
-Public names: `HanabiEnv`, `SumTree`, `Evaluator`, `EvalResult`, `CrossPlay`, `CrossPlayResult`, `PartnerPool`, `PartnerStats`, `Determinizer`, `ConditionedDeterminizer`, `RolloutSearch`, `SearchPlayer`, `SearchResult`, `belief_splice`, `belief_select`, `last_move_uid`, `make_config`, `HbConfig`, `lib`, flag constants.
+Public names: `HanabiEnv`, `SumTree`, `Evaluator`, `EvalResult`, `CrossPlay`, `CrossPlayResult`, `PartnerPool`, `PartnerStats`, `Determinizer`, `ConditionedDeterminizer`, `RolloutSearch`, `SearchPlayer`, `SearchResult`, `belief_splice`, `belief_select`, `belief_splice_alive`, `belief_select_depth`, `PartnerHistory`, `last_move_uid`, `make_config`, `HbConfig`, `lib`, flag constants.
 """
 from ._capi import (FLAG_AUTO_RESET, FLAG_LENIENT_REWARD, FLAG_RESET_START_NEXT, GAME_TYPES, HbConfig, HbError,
                     lib, library_path, make_config)
@@ -14,9 +14,10 @@ from .env import HanabiEnv
 from .evaluate import EvalResult, Evaluator
 from .crossplay import CrossPlay, CrossPlayResult
 from .partner_pool import PartnerPool, PartnerStats
-from .search import (ConditionedDeterminizer, Determinizer, RolloutSearch, SearchPlayer, SearchResult, belief_select, belief_splice,
+from .search import (ConditionedDeterminizer, Determinizer, PartnerHistory, RolloutSearch, SearchPlayer, SearchResult, belief_select,
+                     belief_select_depth, belief_splice, belief_splice_alive,
                      last_move_uid)
 from .tree import SumTree
 
-__all__ = ["ops", "HanabiEnv", "SumTree", "Evaluator", "EvalResult", "CrossPlay", "CrossPlayResult", "PartnerPool", "PartnerStats", "Determinizer", "ConditionedDeterminizer", "RolloutSearch", "SearchPlayer", "SearchResult", "belief_splice", "belief_select", "last_move_uid", "make_config", "HbConfig", "HbError", "lib", "library_path", "GAME_TYPES",
+__all__ = ["ops", "HanabiEnv", "SumTree", "Evaluator", "EvalResult", "CrossPlay", "CrossPlayResult", "PartnerPool", "PartnerStats", "Determinizer", "ConditionedDeterminizer", "RolloutSearch", "SearchPlayer", "SearchResult", "belief_splice", "belief_select", "belief_splice_alive", "belief_select_depth", "PartnerHistory", "last_move_uid", "make_config", "HbConfig", "HbError", "lib", "library_path", "GAME_TYPES",
            "FLAG_AUTO_RESET", "FLAG_RESET_START_NEXT", "FLAG_LENIENT_REWARD"]

@@ -23,6 +23,10 @@
   state the partner moved from with each candidate hand spliced in (hb_belief_splice), the partner's `eval_moves` on those with
   the real turn's Philox keys, and the first `replicas` candidates under which it makes the move it made (hb_belief_select).
   `history=` hands it to run / run_candidates / confirm; `SearchPlayer(condition=True)` keeps the history itself (2 players).
+* `ConditionedDeterminizer.sample_history` conditions it on the partner's last `depth` moves, kept in a `PartnerHistory`: the
+  same candidates carried back to every earlier state the partner moved from (hb_belief_splice_alive: the cards of that older
+  hand I still hold are a prefix of the candidate's hand, the others are public), the partner's `eval_moves` on each, and one
+  hb_belief_select_depth. `SearchPlayer(condition=True, depth=L)` keeps the stack itself.
 * `SearchPlayer` is an agent for `Evaluator.run`: the blueprint's move unless the search finds one that is better by more than
   `threshold` and, with `z` / `confirm_replicas`, by more than z standard errors of the paired difference.
 
@@ -168,6 +172,47 @@ def belief_select(cfg, src_rows, det_rows, weights, hyp_moves, actual, valid, re
     return rows, w, n_surv, fallback
 
 
+def belief_splice_alive(cfg, prev_rows, alive, det_rows, seat, n_cand, out=None):
+    """hb_belief_splice_alive: belief_splice for an older previous state; alive [m] uint8 (or None: every slot alive) marks the
+    slots of `seat`'s hand in prev_rows whose card is still in its hand now. -> rows [K, m, SW] int32, candidate-major."""
+    m, SW = prev_rows.shape
+    Kn, dev = int(n_cand), prev_rows.device
+    _bufs(dev, (prev_rows, det_rows), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32))
+    if alive is not None:
+        _bufs(dev, (alive,), ((m,), torch.uint8))
+    out, = _bufs(dev, None if out is None else (out,), ((max(Kn, 0), m, SW), torch.int32))
+    with torch.cuda.device(dev):
+        K.check(K.lib().hb_belief_splice_alive(C.byref(cfg), K.dptr(prev_rows), K.dptr(alive), K.dptr(det_rows), m, int(seat), Kn,
+                                               K.dptr(out), K.current_stream()))
+    return out
+
+
+def belief_select_depth(cfg, src_rows, det_rows, weights, hyp_moves, actual, valid, replicas, out=None):
+    """hb_belief_select_depth: src_rows [m, SW] int32, det_rows [m * K, SW] int32, weights [m * K] (u32 bits in int32), hyp_moves
+    [D, K, m] int32, actual [D, m] int32, valid [D, m] uint8 or None (entry 0 = the most recent move) -> (rows [m * R, SW] int32,
+    weights [m * R] int32, n_surv [D, m] int32, depth_used [m] int32, fallback [m] uint8). `out`: an optional tuple of these five
+    buffers to write into."""
+    m, SW = src_rows.shape
+    if hyp_moves.dim() != 3:
+        raise ValueError(f"hyp_moves has shape [depth, K, m], got {tuple(hyp_moves.shape)}")
+    D, Kn, R, dev = hyp_moves.shape[0], hyp_moves.shape[1], int(replicas), src_rows.device
+    _bufs(dev, (src_rows, det_rows, weights, hyp_moves, actual), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32),
+          ((m * Kn,), torch.int32), ((D, Kn, m), torch.int32), ((D, m), torch.int32))
+    if valid is not None:
+        _bufs(dev, (valid,), ((D, m), torch.uint8))
+    n = m * max(R, 0)
+    rows, w, n_surv, depth_used, fallback = _bufs(dev, out, ((n, SW), torch.int32), ((n,), torch.int32), ((D, m), torch.int32),
+                                                  ((m,), torch.int32), ((m,), torch.uint8))
+    with torch.cuda.device(dev):
+        K.check(K.lib().hb_belief_select_depth(C.byref(cfg), K.dptr(src_rows), K.dptr(det_rows), K.dptr(weights), K.dptr(hyp_moves),
+                                               K.dptr(actual), K.dptr(valid), m, Kn, R, D, K.dptr(rows), K.dptr(w), K.dptr(n_surv),
+                                               K.dptr(depth_used), K.dptr(fallback), K.current_stream()))
+    return rows, w, n_surv, depth_used, fallback
+
+
+MAX_DEPTH = 8   # hb_belief_select_depth's
+
+
 def running(rows):
     """[m] bool: the game of each state row has not ended (the status bits of word 0 are 0)."""
     return ((rows[:, 0] >> 19) & 3) == 0
@@ -208,6 +253,83 @@ def _history(history, m, words, dev):
             raise ValueError(f"history's valid mask has shape ({m},), got {tuple(valid.shape)}")
         valid = (valid.to(dev) != 0).to(torch.uint8).contiguous()
     return prev, int(history[1]), int(history[2]), int(history[3]), valid
+
+
+class PartnerHistory:
+    """The partner's last `depth` moves as one observer sees them, newest first:
+
+        prev_rows [depth, m, SW] int32   the states the partner moved from
+        moves     [depth, m] int32       the uid it played (last_move_uid of the state after it)
+        draws     [depth] ints           the Philox draw of that turn (a list on the host)
+        alive     [depth, m] uint8       bit s: the card in slot s of MY hand in prev_rows[d] is still in my hand now
+        valid     [depth, m] uint8       0: no usable entry (the entries behind it are then not used either)
+
+    own_move() before I play, push() once the partner has answered. partner_seed / first_game_id: what the partner's eval_moves
+    was keyed with in the real game; RolloutSearch hands them to ConditionedDeterminizer.sample_history. The tensors live on
+    `device` (any torch device: the mask rule is plain torch); `filled` counts the entries pushed since the last clear()."""
+
+    def __init__(self, cfg, m, depth, device, partner_seed=0, first_game_id=0):
+        self.cfg, self.m, self.depth = cfg, int(m), int(depth)
+        if not 1 <= self.depth <= MAX_DEPTH:
+            raise ValueError(f"depth must be in 1..{MAX_DEPTH}, got {depth}")
+        if self.m < 1:
+            raise ValueError(f"m must be >= 1, got {m}")
+        self.state_words = K.lib().hb_state_words(C.byref(cfg))
+        self.partner_seed, self.first_game_id = int(partner_seed), int(first_game_id)
+        D = self.depth
+        self.prev_rows = torch.zeros((D, self.m, self.state_words), dtype=torch.int32, device=device)
+        self.moves = torch.zeros((D, self.m), dtype=torch.int32, device=device)
+        self.alive = torch.zeros((D, self.m), dtype=torch.uint8, device=device)
+        self.valid = torch.zeros((D, self.m), dtype=torch.uint8, device=device)
+        self._slot = torch.arange(5, device=device).view(1, 1, 5)
+        self.clear()
+
+    def clear(self):
+        self.valid.zero_()
+        self.alive.zero_()
+        self.draws, self.filled = [0] * self.depth, 0
+
+    def own_move(self, uids):
+        """I am about to play uids [m]: a play or discard of slot s takes the s-th card I still hold out of every entry (the
+        s-th set bit of its alive mask; a card drawn after the entry — s >= popcount — leaves it unchanged). Hints change
+        nothing."""
+        H = self.cfg.hand_size
+        u = torch.as_tensor(uids).to(self.alive.device).long()
+        if tuple(u.shape) != (self.m,):
+            raise ValueError(f"uids has shape ({self.m},), got {tuple(u.shape)}")
+        card = ((u >= 0) & (u < 2 * H)).view(1, self.m, 1)
+        s = (u % H).view(1, self.m, 1)
+        bits = (self.alive.long().unsqueeze(-1) >> self._slot) & 1   # [depth, m, 5]
+        before = bits.cumsum(-1) - bits                              # set bits below each slot
+        kill = (bits != 0) & (before == s) & card
+        self.alive.copy_(self.alive.long() & ~((kill.long() << self._slot).sum(-1)))
+
+    def push(self, prev_rows, moves, draw, valid, seat=None):
+        """A new newest entry: every entry shifts down by one, the oldest is dropped. Its alive mask is every occupied slot of
+        my hand in prev_rows (seat: my seat; default: the seat after prev_rows' current player, row by row)."""
+        dev = self.alive.device
+        prev = torch.as_tensor(prev_rows).to(device=dev, dtype=torch.int32)
+        if tuple(prev.shape) != (self.m, self.state_words):
+            raise ValueError(f"history's previous rows have shape ({self.m}, {self.state_words}), got {tuple(prev.shape)}")
+        mv, vl = torch.as_tensor(moves).to(dev), torch.as_tensor(valid).to(dev)
+        if tuple(mv.shape) != (self.m,) or tuple(vl.shape) != (self.m,):
+            raise ValueError(f"moves and valid have shape ({self.m},), got {tuple(mv.shape)} and {tuple(vl.shape)}")
+        for t in (self.prev_rows, self.moves, self.alive, self.valid):
+            if self.depth > 1:
+                t[1:] = t[:-1].clone()
+        if seat is None:
+            st = (current_player(prev).long() + 1) % self.cfg.players
+        else:
+            if not 0 <= int(seat) < self.cfg.players:
+                raise ValueError(f"seat {seat} out of range for {self.cfg.players} players")
+            st = torch.full((self.m,), int(seat), dtype=torch.long, device=dev)
+        hand = prev.gather(1, (10 + st).view(self.m, 1)).long().view(self.m, 1)
+        occupied = ((hand >> (5 * self._slot.view(1, 5))) & 31) != 31
+        self.prev_rows[0], self.moves[0] = prev, mv.to(torch.int32)
+        self.alive[0] = (occupied.long() << self._slot.view(1, 5)).sum(-1).to(torch.uint8)
+        self.valid[0] = (vl != 0).to(torch.uint8)
+        self.draws = [int(draw)] + self.draws[:-1]
+        self.filled = min(self.filled + 1, self.depth)
 
 
 class ConditionedDeterminizer:
@@ -278,6 +400,58 @@ class ConditionedDeterminizer:
             return res
         return res[0], res[1].long() & 0xFFFFFFFF, res[2], res[3]
 
+    @torch.no_grad()
+    def sample_history(self, rows, history, partner, seat, replicas, oversample, seed, draw, partner_seed, first_game_id,
+                       first_row_id=0, out=None):
+        """sample() over the partner's last history.depth moves (a PartnerHistory of these m roots, observer `seat`): the
+        candidates are drawn ONCE, as in sample(); for each entry d they are carried back to its previous state with its alive
+        mask (hb_belief_splice_alive) and the partner's eval_moves runs on the K slabs with (partner_seed, history.draws[d]);
+        one hb_belief_select_depth keeps, per root, the first `replicas` candidates that reproduce the most leading moves.
+        Entries that were never pushed cost no slab pass. -> (rows_out [m * replicas, SW] int32, weights [m * replicas] int64,
+        n_surv [depth, m] int32, depth_used [m] int32, fallback [m] uint8); `out` as in sample()."""
+        r = _rows(rows, self.state_words)
+        m, R, ov = r.shape[0], int(replicas), int(oversample)
+        if R < 1 or ov < 1:
+            raise ValueError(f"replicas and oversample must be >= 1, got {replicas} and {oversample}")
+        if not 0 <= int(seat) < self.players:
+            raise ValueError(f"seat {seat} out of range for {self.players} players")
+        if not hasattr(partner, "eval_moves"):
+            raise TypeError(f"{type(partner).__name__} has no eval_moves()")
+        if not isinstance(history, PartnerHistory):
+            raise TypeError(f"history must be a PartnerHistory, got {type(history).__name__}")
+        if history.m != m or history.state_words != self.state_words:
+            raise ValueError(f"the history holds {history.m} roots of {history.state_words} words, the rows are {tuple(r.shape)}")
+        dev, Kn, D = r.device, R * ov, history.depth
+        if history.alive.device != dev:
+            raise ValueError(f"the history lives on {history.alive.device}, the rows on {dev}")
+        b = self._setup(m, Kn, dev)
+        env = b["env"]
+        hyp = b.get("hyp_depth")
+        if hyp is None or hyp.shape[0] != D:
+            hyp = b["hyp_depth"] = torch.zeros((D, Kn, m), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            # the chain of usable entries, root by root: an entry behind an invalid one is never read, so its slab rows only
+            # have to be states the partner's policy can be run on, and the current row is one (as in sample())
+            chain = ((history.valid != 0) & running(r).view(1, m)).long().cumprod(0).to(torch.uint8).contiguous()
+            self.det.sample(r, seat=int(seat), replicas=Kn, seed=seed, draw=draw, first_row_id=first_row_id,
+                            out=(b["cand_rows"], b["cand_w"]))
+            env.first_game_id = int(first_game_id)
+            vec = partner.requires_vectorized_observation()
+            for d in range(min(D, history.filled)):
+                prev = torch.where((chain[d] != 0).view(m, 1), history.prev_rows[d], r).contiguous()
+                belief_splice_alive(self.cfg, prev, history.alive[d].contiguous(), b["cand_rows"], int(seat), Kn, out=b["hyp_rows"])
+                for k in range(Kn):
+                    env.import_state(b["hyp_rows"][k])
+                    if vec:
+                        env.observe()
+                    _ask(partner, env, int(partner_seed), int(history.draws[d]), hyp[d, k], self._scratch)
+            res = belief_select_depth(self.cfg, r, b["cand_rows"], b["cand_w"], hyp, history.moves.contiguous(), chain, R,
+                                      out=None if out is None else tuple(out) + _bufs(dev, None, ((D, m), torch.int32), ((m,), torch.int32),
+                                                                                      ((m,), torch.uint8)))
+        if out is not None:
+            return res
+        return res[0], res[1].long() & 0xFFFFFFFF, res[2], res[3], res[4]
+
 
 class SearchResult:
     """value [m, A] f32 (NaN: illegal at the root, or no live replica), wsum [m, A] int64, n_live [m, A] int32, best [m] int32
@@ -287,14 +461,16 @@ class SearchResult:
     the weighted mean over the replicas of score[slot] - score[baseline], `se` [m, C] f64 its standard error (inf with fewer
     than two live replicas; both 0 in the baseline's slot, NaN where there is no candidate, no baseline or no live replica) and
     `n_pair` [m] int32 the live replicas (hb_search_compare). None when not computed. With `history` (the belief conditioned on
-    the partner's last move): `n_surv` [m] int32 and `fallback` [m] uint8 of hb_belief_select; None without."""
+    the partner's last move): `n_surv` [m] int32 and `fallback` [m] uint8 of hb_belief_select; None without. With a
+    `PartnerHistory` (its last `depth` moves): `n_surv` [depth, m], `fallback` and `depth_used` [m] int32 of
+    hb_belief_select_depth; `depth_used` is None when not computed."""
 
     def __init__(self, value, wsum, n_live, best, rollouts, turns, dead=0, replicas=0, diff=None, se=None, n_pair=None, cand=None,
-                 best_uid=None, n_surv=None, fallback=None):
+                 best_uid=None, n_surv=None, fallback=None, depth_used=None):
         self.value, self.wsum, self.n_live, self.best = value, wsum, n_live, best
         self.rollouts, self.turns, self.dead, self.replicas = int(rollouts), int(turns), int(dead), int(replicas)
         self.diff, self.se, self.n_pair, self.cand, self.best_uid = diff, se, n_pair, cand, best_uid
-        self.n_surv, self.fallback = n_surv, fallback
+        self.n_surv, self.fallback, self.depth_used = n_surv, fallback, depth_used
 
     def __repr__(self):
         return f"SearchResult(roots={self.value.shape[0]}, rollouts={self.rollouts}, turns={self.turns})"
@@ -340,7 +516,9 @@ class RolloutSearch:
     history = (prev_rows, partner_seed, partner_draw, first_game_id[, valid]) to run / run_candidates / confirm: the replicas
     come from `ConditionedDeterminizer` (the belief conditioned on the last move, made from prev_rows by the seat before the
     roots' current player with those Philox keys) with `oversample` candidates per replica; everything after the
-    determinization is the same."""
+    determinization is the same. history may also be a `PartnerHistory` of the roots (the partner's last `depth` moves, with its
+    partner_seed and first_game_id): the replicas then come from `ConditionedDeterminizer.sample_history` and the result carries
+    `depth_used`."""
 
     def __init__(self, game="Hanabi-Full", players=2, replicas=32, seed=1, device=None, config=None, check_every=8, first_game_id=0,
                  oversample=8):
@@ -425,11 +603,17 @@ class RolloutSearch:
         if not cps:
             return self._nothing(m, Cn, dev, compared=base_slot is not None)
         cp, env = int(cps[0]), b["env"]
-        n_surv = fallback = None
+        n_surv = fallback = depth_used = None
         with torch.cuda.device(dev):
             if history is None:
                 self.det.sample(r, seat=cp, replicas=R, seed=self.seed, draw=draw, first_row_id=first_row_id,
                                 out=(b["det_rows"], b["weights"]))
+            elif isinstance(history, PartnerHistory):
+                if self.cdet is None:
+                    self.cdet = ConditionedDeterminizer(config=self.cfg)
+                _, _, n_surv, depth_used, fallback = self.cdet.sample_history(
+                    r, history, blueprint[(cp - 1) % self.players], cp, R, self.oversample, self.seed, draw, history.partner_seed,
+                    history.first_game_id, first_row_id=first_row_id, out=(b["det_rows"], b["weights"]))
             else:
                 prev, p_seed, p_draw, gid, valid = history
                 if self.cdet is None:
@@ -459,7 +643,7 @@ class RolloutSearch:
             value, wsum, n_live, best = search_reduce(scores, weights, slots)
             rollouts, dead, roots = counts.tolist()
             res = SearchResult(value, wsum, n_live, best, rollouts, turns, dead=dead, replicas=roots * R, n_surv=n_surv,
-                               fallback=fallback)
+                               fallback=fallback, depth_used=depth_used)
             if base_slot is not None:
                 res.diff, res.se, res.n_pair = search_compare(scores, weights, cand, base_slot)
         return res
@@ -475,7 +659,7 @@ class RolloutSearch:
         r = roots[0]
         dev = r.device
         m, A = r.shape[0], self.num_actions
-        if history is not None:
+        if history is not None and not isinstance(history, PartnerHistory):
             history = _history(history, m, self.det.state_words, dev)
         lg = torch.as_tensor(legal).to(device=dev, dtype=torch.int8).contiguous()
         if lg.shape != (m, A):
@@ -505,7 +689,7 @@ class RolloutSearch:
         roots = self._roots(rows, blueprint, None)
         dev = roots[0].device
         m = roots[0].shape[0]
-        if history is not None:
+        if history is not None and not isinstance(history, PartnerHistory):
             history = _history(history, m, self.det.state_words, dev)
         R = self.replicas if replicas is None else int(replicas)
         if R < 1:
@@ -588,16 +772,26 @@ class SearchPlayer:
     running now, and word 2 of its row names the partner as the last mover; every other root (a seat's first move of a game
     among them) is searched unconditioned.
 
+    depth=L (1..8, default 1: the rule above, unchanged; L > 1 needs condition=True): the belief is conditioned on the partner's
+    last L moves (ConditionedDeterminizer.sample_history). The player keeps a `PartnerHistory`: on each call it takes the move it
+    remembered playing at draw - 2 out of the stored alive masks (own_move), rebuilds S_prev as above and pushes it with
+    draw - 1 and the validity rule above; where the remembered call is not on the same env at draw - 2 the stack is cleared
+    first. A root whose deepest filter leaves no survivor takes the deepest that does: `last_result.depth_used` says which, and
+    that is a fallback, not the exact posterior given L moves. depth_stats() gives the sums per depth.
+
     Counters: `moves` (moves made in live games), `deviations` (those that left the blueprint), `dead_replicas` /
     `replicas_drawn` (of the first stage), `confirmed` (challengers that went to the second stage), `rejected` (of those, the
     ones not played), `rollouts` (games played, both stages); with condition=True, of the first stage: `conditioned` (live roots
     searched with the filter), `unconditioned` (live roots without), `survivors` / `candidates` (sums over the conditioned
-    roots), `fallbacks` (conditioned roots without a survivor)."""
+    roots), `fallbacks` (conditioned roots without a survivor), `depth_used` (sum over the conditioned roots of the number of
+    partner moves their replicas reproduce: 1 per root that did not fall back at depth 1; with depth > 1 `survivors` counts the
+    candidates that pass the filter of the depth used)."""
 
-    COUNTERS = ("moves", "deviations", "confirmed", "rejected", "conditioned", "unconditioned", "survivors", "candidates", "fallbacks")
+    COUNTERS = ("moves", "deviations", "confirmed", "rejected", "conditioned", "unconditioned", "survivors", "candidates", "fallbacks",
+                "depth_used")
 
     def __init__(self, blueprint, seat, replicas=32, threshold=0.0, seed=1, check_every=8, z=None, confirm_replicas=0,
-                 condition=False, oversample=8):
+                 condition=False, oversample=8, depth=1):
         self.blueprint = list(blueprint)
         self.seat = int(seat)
         if not 0 <= self.seat < len(self.blueprint):
@@ -618,6 +812,12 @@ class SearchPlayer:
             raise ValueError(f"oversample must be >= 1, got {oversample}")
         if self.condition and len(self.blueprint) != 2:
             raise ValueError(f"condition=True is built for 2 players, got {len(self.blueprint)}")
+        self.depth = int(depth)
+        if not 1 <= self.depth <= MAX_DEPTH:
+            raise ValueError(f"depth must be in 1..{MAX_DEPTH}, got {depth}")
+        if self.depth > 1 and not self.condition:
+            raise ValueError(f"depth={depth} needs condition=True")
+        self._history = None   # depth > 1: the PartnerHistory of the env of the last call
         self._search = None
         self.last_result = None   # the SearchResult of the last call's first stage
         self._memory = None    # condition: (env, draw, rows, moves played) of the last call
@@ -630,6 +830,15 @@ class SearchPlayer:
     def reset_stats(self):
         self._stats = None   # [len(COUNTERS)] int64 on the device, built by the first eval_moves: read through the properties
         self.dead_replicas = self.replicas_drawn = self.searches = self.rollouts = 0
+        self._by_depth = None   # depth > 1: [4, depth] int64 on the device, see depth_stats()
+
+    def depth_stats(self):
+        """depth > 1: sums over the first stage's conditioned roots since reset_stats(), one figure per D = 1 .. depth:
+        `reached` (roots with at least D usable partner moves), `survivors` (over those roots, the candidates that reproduce
+        the last D moves), `used` (roots whose replicas reproduce exactly D moves) and `shallow` (roots with exactly D usable
+        moves that use fewer: the deepest filter left no survivor; roots without any survivor among them)."""
+        t = torch.zeros((4, self.depth), dtype=torch.int64) if self._by_depth is None else self._by_depth.cpu()
+        return dict(zip(("reached", "survivors", "used", "shallow"), t.tolist()))
 
     def _previous(self, env, rows, draw):
         """history for this call: the remembered rows stepped with the remembered moves, and which roots that is usable for."""
@@ -649,6 +858,22 @@ class SearchPlayer:
         partner_moved_last = ((w2 & 1) != 0) & (((w2 >> 1) & 7) == partner)
         valid = running(then_rows) & running(rows) & partner_moved_last & running(prev) & (current_player(prev) == partner)
         return prev, valid.to(torch.uint8)
+
+    def _stack(self, env, rows, seed, draw, prev, valid):
+        """depth > 1: the PartnerHistory for this call. The move remembered from draw - 2 leaves the stored alive masks, then
+        (prev, valid) of _previous goes on top; a remembered call that is not this env's at draw - 2 empties the stack first."""
+        m, dev = rows.shape[0], rows.device
+        mem, h = self._memory, self._history
+        same = mem is not None and mem[0]() is env and mem[1] == int(draw) - 2 and mem[2].shape == rows.shape
+        if h is None or h.m != m or h.alive.device != dev or h.state_words != rows.shape[1]:
+            h = self._history = PartnerHistory(eval_config(None, None, env.cfg), m, self.depth, dev)
+        h.partner_seed, h.first_game_id = int(seed), env.first_game_id
+        if not same:   # (nothing to push either: _previous found no usable previous state for any root)
+            h.clear()
+            return h
+        h.own_move(mem[3])
+        h.push(prev, last_move_uid(env.cfg, rows), int(draw) - 1, valid, seat=self.seat)
+        return h
 
     def _significant(self, diff, se, z):
         """diff > z * se, never with a standard error that is not finite (0 * inf must not pass) or a NaN."""
@@ -676,7 +901,10 @@ class SearchPlayer:
         history = None
         if self.condition:
             prev, valid = self._previous(env, rows, draw)
-            history = (prev, int(seed), int(draw) - 1, env.first_game_id, valid)
+            if self.depth == 1:
+                history = (prev, int(seed), int(draw) - 1, env.first_game_id, valid)
+            else:
+                history = self._stack(env, rows, seed, draw, prev, valid)
         res = self._search.run(rows, env.legal, self.blueprint, draw, seat=self.seat,
                                baseline=actions_out if self.z is not None else None, history=history)
         self.last_result = res
@@ -705,9 +933,19 @@ class SearchPlayer:
             self._memory = (weakref.ref(env), int(draw), rows, actions_out.clone())
             if res.fallback is not None:   # (None: no root was running)
                 filtered = live & (res.fallback != 2)
+                if self.depth == 1:
+                    n_surv, used = res.n_surv, (res.fallback == 0).long()
+                else:   # the candidates that pass the filter of the depth used, root by root
+                    used = res.depth_used.long()
+                    n_surv = torch.where(used > 0, res.n_surv.gather(0, (used - 1).clamp(min=0).view(1, -1)).view(-1), 0)
+                    D = torch.arange(1, self.depth + 1, device=rows.device).view(-1, 1)
+                    have = ((history.valid != 0) & live.view(1, -1)).long().cumprod(0).sum(0).view(1, -1)   # L_i
+                    by_depth = torch.stack([(have >= D).sum(1), (res.n_surv * (have >= D)).sum(1), ((used.view(1, -1) == D) & filtered).sum(1),
+                                            ((have == D) & (used.view(1, -1) < D)).sum(1)])
+                    self._by_depth = by_depth if self._by_depth is None else self._by_depth + by_depth
                 counts.update(conditioned=filtered.sum(), unconditioned=(live & (res.fallback == 2)).sum(),
-                              survivors=(res.n_surv * filtered).sum(), candidates=filtered.sum() * (self.replicas * self.oversample),
-                              fallbacks=(filtered & (res.fallback == 1)).sum())
+                              survivors=(n_surv * filtered).sum(), candidates=filtered.sum() * (self.replicas * self.oversample),
+                              fallbacks=(filtered & (res.fallback == 1)).sum(), depth_used=(used * filtered).sum())
         counts.update(moves=live.sum(), deviations=deviate.sum())
         if self._stats is None:
             self._stats = torch.zeros(len(self.COUNTERS), dtype=torch.int64, device=rows.device)

@@ -425,7 +425,8 @@ class SelfPlaySession:
         the number of env steps taken). As evaluate(): updates in flight are completed first, and the session, its env and its
         agents are left exactly as they were. The RolloutSearch (its env and buffers) is kept for the next call. history =
         (prev_rows, partner_seed, partner_draw, first_game_id[, valid]): the belief is conditioned on the last move
-        (RolloutSearch's docstring), with `oversample` candidates per replica."""
+        (RolloutSearch's docstring), with `oversample` candidates per replica; or a `PartnerHistory` of the env's games: on the
+        partner's last `depth` moves."""
         if blueprint is None and self.pool is not None:
             raise ValueError("a session with a partner pool has no single team: pass the blueprint (one agent per seat)")
         if getattr(self.env, "color_shuffled", False):

@@ -870,7 +870,34 @@ int hb_train_tally(const hb_config* cfg, int64_t n_games, int32_t seat, const in
  *   hyp and actual are not read for it. Otherwise fallback = 0.
  * One wavefront per root, candidates 64 at a time: a ballot of the predicate, a prefix popcount and a running base give each
  * survivor its rank; no atomics, no LDS, a pure function of the inputs. n_cand >= replicas >= 1, m * n_cand * SW < 2^31.
- * All six check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                      */
+ * hb_belief_splice_alive: hb_belief_splice for an OLDER previous state, one the observer `seat` has played or discarded cards
+ * since. alive_dev [m] u8 (NULL: every slot alive): bit s set = the card in slot s of the observer's hand in prev row i is still
+ * in its hand now. Hands are ordered by age (cards slide left on removal, a drawn card goes to the end), so the cards still held
+ * are a prefix of the current hand in the same order, and the others were played or discarded, hence public. Row k * m + i of
+ * out_rows_dev [n_cand * m, SW] = prev row i with ONLY word 10 + seat rebuilt: walk the slots s = 0 .. 4 of the previous hand
+ * that hold a card (field != 31), j = 0; if bit s is alive and slot j of candidate (i, k)'s hand word holds a card, slot s takes
+ * that card and j += 1; in every other case (a dead slot; a candidate that has run out of cards, which must not happen but then
+ * still leaves a legal state) slot s keeps the previous row's own card. Empty slots stay empty, their alive bits are ignored,
+ * bits 25 .. 31 stay the previous row's. With every slot alive and equal hand sizes: hb_belief_splice's output, byte for byte.
+ * One wavefront per output row, lane j < SW moves word j, the lane of the hand word does the walk in registers.
+ * hb_belief_select_depth: hb_belief_select over the last mover's last `depth` moves, 1 <= depth <= 8, entry 0 the most recent.
+ * hyp_moves_dev [depth][n_cand * m] int32 (each slab candidate-major as above: the move under candidate (i, k) spliced into
+ * entry d's previous state), actual_dev [depth][m] int32, valid_dev [depth][m] u8 or NULL (all valid); the other inputs as above.
+ * Per root i: L_i = the number of leading entries d = 0, 1, .. with valid[d][i] != 0 (an invalid entry cuts the chain: nothing
+ * older is used); L_i = 0 for a root that is not running. pass_k = the number of leading entries d < L_i with
+ * hyp[d][k, i] == actual[d][i]; 0 if weight[i, k] == 0.
+ *   n_surv_dev [depth][m] int32: n_surv[D - 1][i] = candidates with pass_k >= D, for D = 1 .. L_i; 0 for D > L_i;
+ *   depth_used_dev [m] int32 = the largest D <= L_i with n_surv[D - 1][i] >= 1, 0 if there is none;
+ *   depth_used = D > 0: the candidates with pass_k >= D in ascending k fill replicas 0 .. min(n_surv[D - 1], replicas) - 1, whole
+ *   row and weight; the remaining replicas are dead (weight 0, a copy of src row i); fallback = 0. D < L_i is a FALLBACK to a
+ *   shallower filter (the deepest had no survivor), not the exact posterior given L_i moves: depth_used says which roots;
+ *   depth_used = 0 < L_i: fallback = 1, the outputs are candidates 0 .. replicas - 1 with their own weights;
+ *   L_i = 0: the same outputs, fallback = 2; hyp and actual are not read for the root.
+ * With depth = 1, out_rows, out_weight, n_surv[0] and fallback are hb_belief_select's, byte for byte. One wavefront per root,
+ * candidates 64 at a time: the first sweep accumulates popc(ballot(pass_k >= D)) for each D, the second places the survivors by
+ * running base plus prefix popcount and stops once `replicas` are placed; no atomics, no LDS, a pure function of the inputs.
+ * n_cand >= replicas >= 1, m * n_cand * SW < 2^31.
+ * All eight check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                    */
 int hb_belief_determinize(const hb_config* cfg, const uint32_t* src_rows_dev, int64_t m, int32_t seat, int32_t replicas, uint64_t seed,
                           uint64_t draw, int64_t first_row_id, uint32_t* out_rows_dev, uint32_t* weight_dev, void* stream);
 int hb_search_reduce(const int8_t* score_dev, const uint32_t* weight_dev, const int8_t* legal_dev, int64_t m, int32_t n_actions,
@@ -886,6 +913,12 @@ int hb_belief_select(const hb_config* cfg, const uint32_t* src_rows_dev, const u
                      const int32_t* hyp_moves_dev, const int32_t* actual_dev, const uint8_t* valid_dev, int64_t m, int32_t n_cand,
                      int32_t replicas, uint32_t* out_rows_dev, uint32_t* out_weight_dev, int32_t* n_surv_dev, uint8_t* fallback_dev,
                      void* stream);
+int hb_belief_splice_alive(const hb_config* cfg, const uint32_t* prev_rows_dev, const uint8_t* alive_dev, const uint32_t* det_rows_dev,
+                           int64_t m, int32_t seat, int32_t n_cand, uint32_t* out_rows_dev, void* stream);
+int hb_belief_select_depth(const hb_config* cfg, const uint32_t* src_rows_dev, const uint32_t* det_rows_dev, const uint32_t* weight_dev,
+                           const int32_t* hyp_moves_dev, const int32_t* actual_dev, const uint8_t* valid_dev, int64_t m, int32_t n_cand,
+                           int32_t replicas, int32_t depth, uint32_t* out_rows_dev, uint32_t* out_weight_dev, int32_t* n_surv_dev,
+                           int32_t* depth_used_dev, uint8_t* fallback_dev, void* stream);
 
 /* ---- One host call per step: hb_chain_run (csrc/chain.hip, round 3) ------------------------------------------------------
  * The session that drives DQNAgent (rlax_rainbow.py:277-339: explore / add_experience / update once per env step) issues ~25
