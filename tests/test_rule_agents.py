@@ -4,7 +4,10 @@ The reference's rules run on `hanabi_learning_environment` observation objects, 
 reference has no tests for them: parity against the running reference is UNPINNED. What pins the behaviour:
   * hand-worked situations below (CPU oracle, explicit decks), derived from ruleset.py by reading;
   * bit-exact agreement of the HIP kernel with the independent C restatement (oracle/rule_oracle.c) over long
-    self-play of all four predefined rule lists, 2-5 players, three game sizes;
+    self-play of all four predefined rule lists, 2-5 players, three game sizes. The lists are walked in priority order,
+    so a rule only sees the states the rules before it declined, and only moves are compared; of the sixteen kinds,
+    hail_mary is not among those asserted to have fired (these games rarely reach an empty deck), tell_most_information
+    never fires. tests/test_deep_play_gpu.py holds every kind alone to the oracle on deep games, hail_mary included;
   * self-play scores of the four agents in the range the literature reports for them.
 """
 import numpy as np
@@ -120,7 +123,7 @@ def test_hail_mary_and_probabilities_small_game():
 @pytest.mark.parametrize("game,players", [("Hanabi-Full", 2), ("Hanabi-Full", 3), ("Hanabi-Full", 5), ("Hanabi-Small", 2),
                                           ("Hanabi-Small", 4), ("Hanabi-Very-Small", 2)])
 def test_hip_rule_agents_match_oracle(game, players):
-    """All rule kinds, walked by the HIP kernel and by rule_oracle.c on identical games: same move and same firing
+    """The rule lists, walked by the HIP kernel and by rule_oracle.c on identical games: same move and same firing
     rule for every game at every step, through several episodes (auto-reset)."""
     import hanabi_hip
     from hanabi_agents.rule_based import RulebasedAgent, Ruleset, predefined_rules as PR
@@ -155,7 +158,7 @@ def test_hip_rule_agents_match_oracle(game, players):
     assert np.array_equal(env.export_state().cpu().numpy().astype(np.uint32), orc.export_state())
     assert sum(a.totalCalls for a in agents) == n * steps
     if game == "Hanabi-Full" and players == 2:
-        # every kind except tell_most_information (never fires) and legal_random-as-a-rule was exercised
+        # every kind except hail_mary (12), tell_most_information (never fires) and legal_random-as-a-rule was exercised
         assert fired_any[[1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 14]].all(), fired_any
 
 
