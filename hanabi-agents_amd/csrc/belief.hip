@@ -18,16 +18,15 @@
 // shared replicas, and that difference's standard error; one wavefront per root like hb_search_reduce. Neither uses LDS, a
 // barrier or an atomic.
 //
-// hb_belief_splice / hb_belief_select: the belief conditioned on the partner's last move. Splice: the previous state's rows with
-// the observer's hand word taken from each candidate, candidate-major (one wavefront per output row, a plain coalesced copy).
-// Select: per root the first `replicas` candidates whose hypothetical partner move equals the real one, ranked by ballot and
-// prefix popcount (one wavefront per root, rows copied with lane j < SW holding word j). No LDS, barrier or atomic either.
-//
-// hb_belief_splice_alive / hb_belief_select_depth: the same belief conditioned on the partner's last `depth` moves. Splice-alive:
-// the splice for an OLDER previous state, in which the observer still held cards it has played or discarded since: the cards of
-// that hand it still holds (the `alive` slots) are a prefix of the candidate's hand in the same order, the others are public and
-// stay the previous row's (the lane of the hand word walks the 5 slots in registers). Select-depth: the selection over `depth`
-// predicates, a candidate's pass count = its leading matches; survivors of the deepest level that has any.
+// hb_belief_splice_alive / hb_belief_select_depth: the belief conditioned on the partner's last `depth` moves. Splice-alive: an
+// earlier state's rows with the observer's hand rebuilt from each candidate, candidate-major (one wavefront per output row, a
+// coalesced copy): the cards of that hand the observer still holds (the `alive` slots) are a prefix of the candidate's hand in
+// the same order, the others are public and stay the previous row's (the lane of the hand word walks the 5 slots in registers).
+// Select-depth: per root the first `replicas` candidates whose hypothetical partner moves reproduce the most leading real ones
+// (a candidate's pass count = its leading matches; survivors of the deepest level that has any), ranked by ballot and prefix
+// popcount (one wavefront per root, rows copied with lane j < SW holding word j). No LDS, barrier or atomic either.
+// hb_belief_splice = splice-alive with alive NULL (the state the partner just moved from: every slot alive);
+// hb_belief_select = select-depth with depth 1: the same two kernels.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -309,94 +308,6 @@ __global__ void __launch_bounds__(256) search_compare_kernel(const int8_t* __res
   }
 }
 
-struct SpliceArgs {
-  const uint32_t* prev;
-  const uint32_t* det;
-  uint32_t* out;
-  long long m, n_out;   // n_out = K * m
-  int K, SW, hand_word;
-};
-
-// One wavefront per output row o = k * m + i: the previous state's row i with the observer's hand word taken from candidate
-// (i, k). Lane j < SW moves word j; the lane of the hand word reads the candidate's instead.
-__global__ void __launch_bounds__(256) belief_splice_kernel(SpliceArgs a) {
-  const int lane = threadIdx.x & 63;
-  const long long o = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (o >= a.n_out || lane >= a.SW) return;
-  const long long k = o / a.m, i = o - k * a.m;
-  const uint32_t* src = lane == a.hand_word ? a.det + (i * a.K + k) * a.SW : a.prev + i * a.SW;
-  a.out[o * a.SW + lane] = src[lane];
-}
-
-struct SelectArgs {
-  const uint32_t* src;
-  const uint32_t* det;
-  const uint32_t* weight;
-  const int32_t* hyp;
-  const int32_t* actual;
-  const uint8_t* valid;   // may be null: every root valid
-  uint32_t* out;
-  uint32_t* out_weight;
-  int32_t* n_surv;
-  uint8_t* fallback;
-  long long m;
-  int K, R, SW;
-};
-
-// One wavefront per root. Pass 1 counts the survivors (ballots over 64 candidates at a time); pass 2 copies the first R of them
-// in candidate order, each survivor's rank = running base + prefix popcount of its chunk's ballot. Everything that decides a
-// branch is wave-uniform.
-__global__ void __launch_bounds__(256) belief_select_kernel(SelectArgs a) {
-  const int lane = threadIdx.x & 63;
-  const long long i = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
-  if (i >= a.m) return;
-  const uint32_t* det = a.det + i * a.K * a.SW;
-  const uint32_t* w = a.weight + i * a.K;
-  uint32_t* out = a.out + i * a.R * a.SW;
-  uint32_t* ow = a.out_weight + i * a.R;
-  const bool running = ((a.src[i * a.SW] >> 19) & 3u) == 0;
-  const bool usable = running && (!a.valid || a.valid[i] != 0);
-  const int32_t actual = a.actual[i];
-  int total = 0;
-  if (usable) {
-    for (int k0 = 0; k0 < a.K; k0 += 64) {
-      const int k = k0 + lane;
-      const bool s = k < a.K && w[k] != 0u && a.hyp[k * a.m + i] == actual;
-      total += __popcll(__ballot(s));
-    }
-  }
-  if (lane == 0) {
-    a.n_surv[i] = total;
-    a.fallback[i] = !usable ? 2 : total == 0 ? 1 : 0;
-  }
-  if (total == 0) {   // the unconditioned belief: candidates 0 .. R - 1 as they are
-    for (int r = 0; r < a.R; ++r)
-      if (lane < a.SW) out[r * a.SW + lane] = det[r * a.SW + lane];
-    for (int r = lane; r < a.R; r += 64) ow[r] = w[r];
-    return;
-  }
-  int base = 0;
-  for (int k0 = 0; k0 < a.K && base < a.R; k0 += 64) {
-    const int k = k0 + lane;
-    const uint32_t wk = k < a.K ? w[k] : 0u;
-    const bool s = wk != 0u && a.hyp[k * a.m + i] == actual;   // (k >= K: wk = 0, nothing is read)
-    const unsigned long long mask = __ballot(s);
-    const int rank = base + __popcll(mask & ((1ull << lane) - 1ull));
-    if (s && rank < a.R) ow[rank] = wk;
-    int r = base;
-    for (unsigned long long todo = mask; todo && r < a.R; todo &= todo - 1, ++r) {
-      const int kk = k0 + __ffsll(todo) - 1;
-      if (lane < a.SW) out[r * a.SW + lane] = det[kk * a.SW + lane];
-    }
-    base += __popcll(mask);
-  }
-  const uint32_t sj = lane < a.SW ? a.src[i * a.SW + lane] : 0u;
-  for (int r = total; r < a.R; ++r) {   // fewer survivors than replicas: dead copies of the root
-    if (lane < a.SW) out[r * a.SW + lane] = sj;
-    if (lane == 0) ow[r] = 0u;
-  }
-}
-
 struct SpliceAliveArgs {
   const uint32_t* prev;
   const uint8_t* alive;   // may be null: every slot alive
@@ -443,7 +354,7 @@ struct SelectDepthArgs {
   uint32_t* out;
   uint32_t* out_weight;
   int32_t* n_surv;         // [depth][m]
-  int32_t* depth_used;
+  int32_t* depth_used;     // may be null: not written
   uint8_t* fallback;
   long long m;
   int K, R, SW, depth;
@@ -451,12 +362,12 @@ struct SelectDepthArgs {
 
 constexpr int MAX_DEPTH = 8;
 
-// One wavefront per root, belief_select_kernel over `depth` predicates. L = the leading valid entries of the root (0 when it is
-// not running). Sweep 1: every lane's candidate stays `on` while its moves match, from entry 0 (never, for a weight of 0);
-// cnt[D - 1] = candidates with at least D leading matches, by ballot. used = the deepest level with a survivor (cnt never grows
-// with D). Sweep 2 places the candidates with at least `used` leading matches exactly as belief_select_kernel places its
-// survivors. The loops over the levels are unrolled to MAX_DEPTH with wave-uniform guards, so that act[] and cnt[] stay in
-// registers.
+// One wavefront per root. L = the leading valid entries of the root (0 when it is not running). Sweep 1: every lane's candidate
+// stays `on` while its moves match, from entry 0 (never, for a weight of 0); cnt[D - 1] = candidates with at least D leading
+// matches, by ballot over 64 candidates at a time. used = the deepest level with a survivor (cnt never grows with D). Sweep 2
+// copies the first R candidates with at least `used` leading matches in candidate order, each one's rank = running base + prefix
+// popcount of its chunk's ballot. Everything that decides a branch is wave-uniform. The loops over the levels are unrolled to
+// MAX_DEPTH with wave-uniform guards, so that act[] and cnt[] stay in registers.
 __global__ void __launch_bounds__(256) belief_select_depth_kernel(SelectDepthArgs a) {
   const int lane = threadIdx.x & 63;
   const long long i = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
@@ -500,7 +411,7 @@ __global__ void __launch_bounds__(256) belief_select_depth_kernel(SelectDepthArg
     total = d + 1 == used ? cnt[d] : total;
   }
   if (lane == 0) {
-    a.depth_used[i] = used;
+    if (a.depth_used) a.depth_used[i] = used;
     a.fallback[i] = L == 0 ? 2 : used == 0 ? 1 : 0;
   }
   if (used == 0) {   // the unconditioned belief: candidates 0 .. R - 1 as they are
@@ -541,6 +452,23 @@ int have_device() {
     return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
   }();
   return ndev > 0 ? HB_OK : hb::fail(HB_ERR_NO_DEVICE, "no HIP device available");
+}
+
+// The launch hb_belief_select (depth 1, no depth_used) and hb_belief_select_depth share; arguments checked by the caller.
+int launch_select(const hb_config* cfg, const uint32_t* src, const uint32_t* det, const uint32_t* weight, const int32_t* hyp,
+                  const int32_t* actual, const uint8_t* valid, int64_t m, int n_cand, int replicas, int depth, uint32_t* out,
+                  uint32_t* out_weight, int32_t* n_surv, int32_t* depth_used, uint8_t* fallback, void* stream) {
+  if (m == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  SelectDepthArgs a{};
+  a.src = src; a.det = det; a.weight = weight; a.hyp = hyp; a.actual = actual; a.valid = valid;
+  a.out = out; a.out_weight = out_weight; a.n_surv = n_surv; a.depth_used = depth_used; a.fallback = fallback;
+  a.m = m;
+  a.K = n_cand; a.R = replicas; a.SW = hb_state_words(cfg); a.depth = depth;
+  const unsigned blocks = static_cast<unsigned>((m + 3) / 4);   // four wavefronts = four roots per workgroup
+  hipLaunchKernelGGL(belief_select_depth_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
 }
 
 }  // namespace
@@ -639,29 +567,7 @@ extern "C" int hb_search_compare(const int8_t* score_dev, const uint32_t* weight
 
 extern "C" int hb_belief_splice(const hb_config* cfg, const uint32_t* prev_rows_dev, const uint32_t* det_rows_dev, int64_t m, int32_t seat,
                                 int32_t n_cand, uint32_t* out_rows_dev, void* stream) {
-  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
-  if (int rc = hb_config_validate(cfg)) return rc;
-  if (m < 0) return hb::fail(HB_ERR_INVALID, "m must be >= 0");
-  if (n_cand < 1) return hb::fail(HB_ERR_INVALID, "n_cand must be >= 1, got %d", n_cand);
-  if (seat < 0 || seat >= cfg->players)
-    return hb::fail(HB_ERR_INVALID, "seat %d out of range 0..%d (the observer is not the previous state's current player)", seat,
-                    cfg->players - 1);
-  if (!prev_rows_dev || !det_rows_dev || !out_rows_dev) return hb::fail(HB_ERR_INVALID, "null argument");
-  const int SW = hb_state_words(cfg);
-  if (m > ((static_cast<int64_t>(1) << 31) - 1) / (static_cast<int64_t>(n_cand) * SW))
-    return hb::fail(HB_ERR_INVALID, "m * n_cand * state words must stay below 2^31: split the roots");
-  if (m == 0) return HB_OK;
-  if (int rc = have_device()) return rc;
-  SpliceArgs a{};
-  a.prev = prev_rows_dev; a.det = det_rows_dev; a.out = out_rows_dev;
-  a.m = m;
-  a.n_out = m * n_cand;
-  a.K = n_cand; a.SW = SW;
-  a.hand_word = 10 + seat;
-  const unsigned blocks = static_cast<unsigned>((a.n_out + 3) / 4);   // four wavefronts = four output rows per workgroup
-  hipLaunchKernelGGL(belief_splice_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  HB_HIP(hipGetLastError());
-  return HB_OK;
+  return hb_belief_splice_alive(cfg, prev_rows_dev, /*alive*/ nullptr, det_rows_dev, m, seat, n_cand, out_rows_dev, stream);
 }
 
 extern "C" int hb_belief_select(const hb_config* cfg, const uint32_t* src_rows_dev, const uint32_t* det_rows_dev, const uint32_t* weight_dev,
@@ -679,17 +585,8 @@ extern "C" int hb_belief_select(const hb_config* cfg, const uint32_t* src_rows_d
   const int SW = hb_state_words(cfg);
   if (m > ((static_cast<int64_t>(1) << 31) - 1) / (static_cast<int64_t>(n_cand) * SW))
     return hb::fail(HB_ERR_INVALID, "m * n_cand * state words must stay below 2^31: split the roots");
-  if (m == 0) return HB_OK;
-  if (int rc = have_device()) return rc;
-  SelectArgs a{};
-  a.src = src_rows_dev; a.det = det_rows_dev; a.weight = weight_dev; a.hyp = hyp_moves_dev; a.actual = actual_dev; a.valid = valid_dev;
-  a.out = out_rows_dev; a.out_weight = out_weight_dev; a.n_surv = n_surv_dev; a.fallback = fallback_dev;
-  a.m = m;
-  a.K = n_cand; a.R = replicas; a.SW = SW;
-  const unsigned blocks = static_cast<unsigned>((m + 3) / 4);   // four wavefronts = four roots per workgroup
-  hipLaunchKernelGGL(belief_select_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  HB_HIP(hipGetLastError());
-  return HB_OK;
+  return launch_select(cfg, src_rows_dev, det_rows_dev, weight_dev, hyp_moves_dev, actual_dev, valid_dev, m, n_cand, replicas, /*depth*/ 1,
+                       out_rows_dev, out_weight_dev, n_surv_dev, /*depth_used*/ nullptr, fallback_dev, stream);
 }
 
 extern "C" int hb_belief_splice_alive(const hb_config* cfg, const uint32_t* prev_rows_dev, const uint8_t* alive_dev,
@@ -737,15 +634,6 @@ extern "C" int hb_belief_select_depth(const hb_config* cfg, const uint32_t* src_
   const int SW = hb_state_words(cfg);
   if (m > ((static_cast<int64_t>(1) << 31) - 1) / (static_cast<int64_t>(n_cand) * SW))
     return hb::fail(HB_ERR_INVALID, "m * n_cand * state words must stay below 2^31: split the roots");
-  if (m == 0) return HB_OK;
-  if (int rc = have_device()) return rc;
-  SelectDepthArgs a{};
-  a.src = src_rows_dev; a.det = det_rows_dev; a.weight = weight_dev; a.hyp = hyp_moves_dev; a.actual = actual_dev; a.valid = valid_dev;
-  a.out = out_rows_dev; a.out_weight = out_weight_dev; a.n_surv = n_surv_dev; a.depth_used = depth_used_dev; a.fallback = fallback_dev;
-  a.m = m;
-  a.K = n_cand; a.R = replicas; a.SW = SW; a.depth = depth;
-  const unsigned blocks = static_cast<unsigned>((m + 3) / 4);   // four wavefronts = four roots per workgroup
-  hipLaunchKernelGGL(belief_select_depth_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  HB_HIP(hipGetLastError());
-  return HB_OK;
+  return launch_select(cfg, src_rows_dev, det_rows_dev, weight_dev, hyp_moves_dev, actual_dev, valid_dev, m, n_cand, replicas, depth,
+                       out_rows_dev, out_weight_dev, n_surv_dev, depth_used_dev, fallback_dev, stream);
 }

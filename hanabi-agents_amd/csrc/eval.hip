@@ -8,7 +8,9 @@
 // atomics on one address cost ~12 ns each (env_kernel.hpp, the episode statistics). Measured: one atomic per wave and
 // counter cost 22-25 us per turn at 32 768 games (512 waves on the same few addresses) against 7 us at 4 096.
 //
-// The partner-response counts (hb_eval_response_tally, issued between the env step and the tally) are at the end of the file.
+// hb_eval_tally_grouped runs the same kernel over blocks of games, one grid row and one row of counters per block; hb_eval_tally
+// is that launch with one grid row. The partner-response counts (hb_eval_response_tally, issued between the env step and the
+// tally; grouped in the same way) are at the end of the file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,73 +40,64 @@ __device__ __forceinline__ void wave_add(unsigned int* c, unsigned long long mas
   if (mask && lane == 0) atomicAdd(c, static_cast<unsigned int>(__popcll(mask)));
 }
 
-// Grid-stride over the games (the loop bound is uniform across the workgroup, so every lane takes part in every ballot).
-// Each wave adds its ballot counts into the workgroup's LDS copy of the counters; the workgroup then issues one global atomic
-// per nonzero counter.
-// A macro over the arguments `a` of the enclosing kernel, so that eval_tally_kernel expands to exactly the code it was written as
-// (its code object is unchanged) and the grouped kernel shares it.
-#define HB_TALLY_BODY                                                                                                                             \
-  __shared__ unsigned int lc[kMaxCounters];                                                                                                       \
-  const int lane = threadIdx.x & 63;                                                                                                              \
-  const int B = a.bins, nc = 2 + B + 5 * a.P;                                                                                                     \
-  for (int i = threadIdx.x; i < nc; i += 256) lc[i] = 0;                                                                                          \
-  __syncthreads();                                                                                                                                \
-  for (long long base = static_cast<long long>(blockIdx.x) * 256; base < a.n; base += static_cast<long long>(gridDim.x) * 256) {                  \
-    const long long g = base + threadIdx.x;                                                                                                       \
-    int kind = -1, bin = 0;                                                                                                                       \
-    bool ended = false, misplay = false, bomb = false;                                                                                            \
-    if (g < a.n) {                                                                                                                                \
-      const uint8_t st = a.done[g];                                                                                                               \
-      if (!(st & 0x80u)) {   /* a game counts only while it is live: finished games' env outputs are never read */                                \
-        const int u = a.actions[g];                                                                                                               \
-        if (u >= 0 && u < a.A) kind = u < a.H ? 0 : u < 2 * a.H ? 1 : u < 2 * a.H + (a.P - 1) * a.C ? 2 : 3;   /* App. A.2 order */               \
-        misplay = kind == 1 && a.reward[g] <= 0.f;   /* a successful play always scores +1; a misplay 0, or -score at a bomb-out */               \
-        const int lost = (st & 0x7f) + (misplay ? 1 : 0);                                                                                         \
-        ended = a.terminal[g] != 0;                                                                                                               \
-        if (ended) {                                                                                                                              \
-          const int sc = a.score[g];   /* 0 after a bomb-out (hb_env_step) */                                                                     \
-          bin = sc < 0 ? 0 : sc > B - 1 ? B - 1 : sc;                                                                                             \
-          bomb = lost >= a.max_life;                                                                                                              \
-          a.final_score[g] = static_cast<int8_t>(sc);                                                                                             \
-          a.length[g] = static_cast<int16_t>(a.turn + 1);                                                                                         \
-          a.done[g] = static_cast<uint8_t>(0x80 | lost);                                                                                          \
-        } else if (misplay) {                                                                                                                     \
-          a.done[g] = static_cast<uint8_t>(lost);                                                                                                 \
-        }                                                                                                                                         \
-      }                                                                                                                                           \
-    }                                                                                                                                             \
-    unsigned long long m = __ballot(ended);                                                                                                       \
-    if (m) {                                                                                                                                      \
-      wave_add(lc, m, lane);   /* (slot 0 counts the games that ended: subtracted from the live count below) */                                   \
-      wave_add(lc + 1 + B, __ballot(bomb), lane);                                                                                                 \
-      while (m) {   /* histogram: one ballot per score that occurs in this wave (wave-uniform loop) */                                            \
-        const int b = __shfl(bin, __ffsll(static_cast<unsigned long long>(m)) - 1);                                                               \
-        const unsigned long long mb = __ballot(ended && bin == b);                                                                                \
-        wave_add(lc + 1 + b, mb, lane);                                                                                                           \
-        m &= ~mb;                                                                                                                                 \
-      }                                                                                                                                           \
-    }                                                                                                                                             \
-    _Pragma("unroll") for (int k = 0; k < 4; ++k) wave_add(lc + 2 + B + 4 * a.seat + k, __ballot(kind == k), lane);                                                 \
-    wave_add(lc + 2 + B + 4 * a.P + a.seat, __ballot(misplay), lane);                                                                             \
-  }                                                                                                                                               \
-  __syncthreads();                                                                                                                                \
-  for (int i = threadIdx.x; i < nc; i += 256) {                                                                                                   \
-    const unsigned int v = lc[i];                                                                                                                 \
-    if (v) atomicAdd(a.counters + i, i == 0 ? static_cast<unsigned long long>(-static_cast<long long>(v)) : static_cast<unsigned long long>(v));  \
-  }
-
-__global__ void __launch_bounds__(256) eval_tally_kernel(TallyArgs a) {
-  HB_TALLY_BODY
-}
-
-// hb_eval_tally_grouped: blockIdx.y selects a block of a0.n games and its own row of counters
+// blockIdx.y selects a block of a0.n games and its own row of counters (hb_eval_tally: the one block). Grid-stride over the
+// block's games (the loop bound is uniform across the workgroup, so every lane takes part in every ballot). Each wave adds its
+// ballot counts into the workgroup's LDS copy of the counters; the workgroup then issues one global atomic per nonzero counter.
 __global__ void __launch_bounds__(256) eval_tally_grouped_kernel(TallyArgs a0) {
   const long long off = static_cast<long long>(blockIdx.y) * a0.n;
   TallyArgs a = a0;
   a.actions += off; a.reward += off; a.terminal += off; a.score += off;
   a.done += off; a.final_score += off; a.length += off;
   a.counters += static_cast<long long>(blockIdx.y) * (2 + a0.bins + 5 * a0.P);
-  HB_TALLY_BODY
+  __shared__ unsigned int lc[kMaxCounters];
+  const int lane = threadIdx.x & 63;
+  const int B = a.bins, nc = 2 + B + 5 * a.P;
+  for (int i = threadIdx.x; i < nc; i += 256) lc[i] = 0;
+  __syncthreads();
+  for (long long base = static_cast<long long>(blockIdx.x) * 256; base < a.n; base += static_cast<long long>(gridDim.x) * 256) {
+    const long long g = base + threadIdx.x;
+    int kind = -1, bin = 0;
+    bool ended = false, misplay = false, bomb = false;
+    if (g < a.n) {
+      const uint8_t st = a.done[g];
+      if (!(st & 0x80u)) {   // a game counts only while it is live: finished games' env outputs are never read
+        const int u = a.actions[g];
+        if (u >= 0 && u < a.A) kind = u < a.H ? 0 : u < 2 * a.H ? 1 : u < 2 * a.H + (a.P - 1) * a.C ? 2 : 3;   // App. A.2 order
+        misplay = kind == 1 && a.reward[g] <= 0.f;   // a successful play always scores +1; a misplay 0, or -score at a bomb-out
+        const int lost = (st & 0x7f) + (misplay ? 1 : 0);
+        ended = a.terminal[g] != 0;
+        if (ended) {
+          const int sc = a.score[g];   // 0 after a bomb-out (hb_env_step)
+          bin = sc < 0 ? 0 : sc > B - 1 ? B - 1 : sc;
+          bomb = lost >= a.max_life;
+          a.final_score[g] = static_cast<int8_t>(sc);
+          a.length[g] = static_cast<int16_t>(a.turn + 1);
+          a.done[g] = static_cast<uint8_t>(0x80 | lost);
+        } else if (misplay) {
+          a.done[g] = static_cast<uint8_t>(lost);
+        }
+      }
+    }
+    unsigned long long m = __ballot(ended);
+    if (m) {
+      wave_add(lc, m, lane);   // (slot 0 counts the games that ended: subtracted from the live count below)
+      wave_add(lc + 1 + B, __ballot(bomb), lane);
+      while (m) {   // histogram: one ballot per score that occurs in this wave (wave-uniform loop)
+        const int b = __shfl(bin, __ffsll(static_cast<unsigned long long>(m)) - 1);
+        const unsigned long long mb = __ballot(ended && bin == b);
+        wave_add(lc + 1 + b, mb, lane);
+        m &= ~mb;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) wave_add(lc + 2 + B + 4 * a.seat + k, __ballot(kind == k), lane);
+    wave_add(lc + 2 + B + 4 * a.P + a.seat, __ballot(misplay), lane);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nc; i += 256) {
+    const unsigned int v = lc[i];
+    if (v) atomicAdd(a.counters + i, i == 0 ? static_cast<unsigned long long>(-static_cast<long long>(v)) : static_cast<unsigned long long>(v));
+  }
 }
 
 }  // namespace
@@ -155,6 +148,14 @@ TallyArgs tally_args(const hb_config* cfg, int64_t n_games, int32_t seat, int32_
   return a;
 }
 
+// n_blocks grid rows of at most kMaxBlocks workgroups each over the a.n games of a block
+int launch_tally(const TallyArgs& a, int64_t n_blocks, void* stream) {
+  const dim3 grid(static_cast<unsigned>(std::min<int64_t>((a.n + 255) / 256, kMaxBlocks)), static_cast<unsigned>(n_blocks));
+  hipLaunchKernelGGL(eval_tally_grouped_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
 }  // namespace
 
 extern "C" int hb_eval_tally(const hb_config* cfg, int64_t n_games, int32_t seat, int32_t turn, const int32_t* actions_dev,
@@ -165,12 +166,8 @@ extern "C" int hb_eval_tally(const hb_config* cfg, int64_t n_games, int32_t seat
     return rc;
   if (n_games == 0) return HB_OK;
   if (int rc = have_device()) return rc;
-  const TallyArgs a = tally_args(cfg, n_games, seat, turn, actions_dev, reward_dev, terminal_dev, score_dev, done_dev, final_score_dev,
-                                 length_dev, counters_dev);
-  const unsigned blocks = static_cast<unsigned>(std::min<int64_t>((n_games + 255) / 256, kMaxBlocks));
-  hipLaunchKernelGGL(eval_tally_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  HB_HIP(hipGetLastError());
-  return HB_OK;
+  return launch_tally(tally_args(cfg, n_games, seat, turn, actions_dev, reward_dev, terminal_dev, score_dev, done_dev, final_score_dev,
+                                 length_dev, counters_dev), 1, stream);
 }
 
 extern "C" int hb_eval_tally_grouped(const hb_config* cfg, int64_t n_blocks, int64_t block_games, int32_t seat, int32_t turn,
@@ -183,12 +180,8 @@ extern "C" int hb_eval_tally_grouped(const hb_config* cfg, int64_t n_blocks, int
   if (n_blocks < 0 || n_blocks > 65535) return hb::fail(HB_ERR_INVALID, "n_blocks must be 0..65535 (one grid row per block)");
   if (n_blocks == 0 || block_games == 0) return HB_OK;
   if (int rc = have_device()) return rc;
-  const TallyArgs a = tally_args(cfg, block_games, seat, turn, actions_dev, reward_dev, terminal_dev, score_dev, done_dev, final_score_dev,
-                                 length_dev, counters_dev);
-  const dim3 grid(static_cast<unsigned>(std::min<int64_t>((block_games + 255) / 256, kMaxBlocks)), static_cast<unsigned>(n_blocks));
-  hipLaunchKernelGGL(eval_tally_grouped_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  HB_HIP(hipGetLastError());
-  return HB_OK;
+  return launch_tally(tally_args(cfg, block_games, seat, turn, actions_dev, reward_dev, terminal_dev, score_dev, done_dev,
+                                 final_score_dev, length_dev, counters_dev), n_blocks, stream);
 }
 
 // ---- partner-response counts (hb_eval_response_tally) -------------------------------------------------------------------------
@@ -212,7 +205,12 @@ struct RespArgs {
   unsigned long long* resp;
 };
 
-__device__ __forceinline__ void response_body(const RespArgs& a) {
+// blockIdx.y selects a block of a0.n games and its own [P][A + 1][A] counts (hb_eval_response_tally: the one block)
+__global__ void __launch_bounds__(256) eval_response_grouped_kernel(RespArgs a0) {
+  const long long off = static_cast<long long>(blockIdx.y) * a0.n;
+  RespArgs a = a0;
+  a.actions += off; a.done += off; a.prev += off;
+  a.resp += static_cast<long long>(blockIdx.y) * a0.P * ((a0.A + 1) * a0.A);
   __shared__ unsigned int hist[kMaxRespBins];
   const int bins = (a.A + 1) * a.A;   // <= kMaxRespBins (checked on the host)
   for (int i = threadIdx.x; i < bins; i += 256) hist[i] = 0;
@@ -231,17 +229,6 @@ __device__ __forceinline__ void response_body(const RespArgs& a) {
     const unsigned int v = hist[i];
     if (v) atomicAdd(out + i, static_cast<unsigned long long>(v));
   }
-}
-
-__global__ void __launch_bounds__(256) eval_response_kernel(RespArgs a) { response_body(a); }
-
-// hb_eval_response_tally_grouped: blockIdx.y selects a block of a0.n games and its own [P][A + 1][A] counts
-__global__ void __launch_bounds__(256) eval_response_grouped_kernel(RespArgs a0) {
-  const long long off = static_cast<long long>(blockIdx.y) * a0.n;
-  RespArgs a = a0;
-  a.actions += off; a.done += off; a.prev += off;
-  a.resp += static_cast<long long>(blockIdx.y) * a0.P * ((a0.A + 1) * a0.A);
-  response_body(a);
 }
 
 int check_response(const hb_config* cfg, int64_t n_games, int32_t seat, const int32_t* actions_dev, const uint8_t* done_dev,
@@ -268,6 +255,14 @@ RespArgs response_args(const hb_config* cfg, int64_t n_games, int32_t seat, cons
   return a;
 }
 
+// n_blocks grid rows of at most kMaxBlocks workgroups each over the a.n games of a block
+int launch_response(const RespArgs& a, int64_t n_blocks, void* stream) {
+  const dim3 grid(static_cast<unsigned>(std::min<int64_t>((a.n + 255) / 256, kMaxBlocks)), static_cast<unsigned>(n_blocks));
+  hipLaunchKernelGGL(eval_response_grouped_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
 }  // namespace
 
 extern "C" int hb_eval_response_bins(const hb_config* cfg) {
@@ -282,11 +277,7 @@ extern "C" int hb_eval_response_tally(const hb_config* cfg, int64_t n_games, int
   if (int rc = check_response(cfg, n_games, seat, actions_dev, done_dev, prev_dev, resp_dev)) return rc;
   if (n_games == 0) return HB_OK;
   if (int rc = have_device()) return rc;
-  const RespArgs a = response_args(cfg, n_games, seat, actions_dev, done_dev, prev_dev, resp_dev);
-  const unsigned blocks = static_cast<unsigned>(std::min<int64_t>((n_games + 255) / 256, kMaxBlocks));
-  hipLaunchKernelGGL(eval_response_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  HB_HIP(hipGetLastError());
-  return HB_OK;
+  return launch_response(response_args(cfg, n_games, seat, actions_dev, done_dev, prev_dev, resp_dev), 1, stream);
 }
 
 extern "C" int hb_eval_response_tally_grouped(const hb_config* cfg, int64_t n_blocks, int64_t block_games, int32_t seat,
@@ -298,9 +289,5 @@ extern "C" int hb_eval_response_tally_grouped(const hb_config* cfg, int64_t n_bl
     return hb::fail(HB_ERR_INVALID, "n_blocks * block_games must be < 2^31");
   if (n_blocks == 0 || block_games == 0) return HB_OK;
   if (int rc = have_device()) return rc;
-  const RespArgs a = response_args(cfg, block_games, seat, actions_dev, done_dev, prev_dev, resp_dev);
-  const dim3 grid(static_cast<unsigned>(std::min<int64_t>((block_games + 255) / 256, kMaxBlocks)), static_cast<unsigned>(n_blocks));
-  hipLaunchKernelGGL(eval_response_grouped_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  HB_HIP(hipGetLastError());
-  return HB_OK;
+  return launch_response(response_args(cfg, block_games, seat, actions_dev, done_dev, prev_dev, resp_dev), n_blocks, stream);
 }

@@ -141,8 +141,9 @@ def search_compare(scores, weights, cand, base_slot):
 
 
 def belief_splice(cfg, prev_rows, det_rows, seat, n_cand, out=None):
-    """hb_belief_splice: prev_rows [m, SW] int32, det_rows [m * K, SW] int32 (candidate (i, k) = row i * K + k) ->
-    rows [K, m, SW] int32, candidate-major: slab k = prev_rows with word 10 + seat of every row taken from candidate (i, k)."""
+    """hb_belief_splice (belief_splice_alive with every slot alive): prev_rows [m, SW] int32, det_rows [m * K, SW] int32
+    (candidate (i, k) = row i * K + k) -> rows [K, m, SW] int32, candidate-major: slab k = prev_rows with word 10 + seat of every
+    row taken from candidate (i, k)."""
     m, SW = prev_rows.shape
     Kn, dev = int(n_cand), prev_rows.device
     _bufs(dev, (prev_rows, det_rows), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32))
@@ -154,9 +155,9 @@ def belief_splice(cfg, prev_rows, det_rows, seat, n_cand, out=None):
 
 
 def belief_select(cfg, src_rows, det_rows, weights, hyp_moves, actual, valid, replicas, out=None):
-    """hb_belief_select: src_rows [m, SW] int32, det_rows [m * K, SW] int32, weights [m * K] (u32 bits in int32), hyp_moves [K, m]
-    int32, actual [m] int32, valid [m] uint8 or None -> (rows [m * R, SW] int32, weights [m * R] int32, n_surv [m] int32,
-    fallback [m] uint8). `out`: an optional tuple of these four buffers to write into."""
+    """hb_belief_select (belief_select_depth at depth 1): src_rows [m, SW] int32, det_rows [m * K, SW] int32, weights [m * K]
+    (u32 bits in int32), hyp_moves [K, m] int32, actual [m] int32, valid [m] uint8 or None -> (rows [m * R, SW] int32, weights
+    [m * R] int32, n_surv [m] int32, fallback [m] uint8). `out`: an optional tuple of these four buffers to write into."""
     m, SW = src_rows.shape
     Kn, R, dev = hyp_moves.shape[0], int(replicas), src_rows.device
     _bufs(dev, (src_rows, det_rows, weights, hyp_moves, actual), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32),
@@ -173,8 +174,10 @@ def belief_select(cfg, src_rows, det_rows, weights, hyp_moves, actual, valid, re
 
 
 def belief_splice_alive(cfg, prev_rows, alive, det_rows, seat, n_cand, out=None):
-    """hb_belief_splice_alive: belief_splice for an older previous state; alive [m] uint8 (or None: every slot alive) marks the
-    slots of `seat`'s hand in prev_rows whose card is still in its hand now. -> rows [K, m, SW] int32, candidate-major."""
+    """hb_belief_splice_alive: prev_rows [m, SW] int32 states the partner moved from, det_rows [m * K, SW] int32 (candidate (i, k)
+    = row i * K + k); alive [m] uint8 (or None: every slot alive) marks the slots of `seat`'s hand in prev_rows whose card is
+    still in its hand now. -> rows [K, m, SW] int32, candidate-major: slab k = prev_rows with the alive slots of word 10 + seat
+    taken from candidate (i, k)'s hand, in order."""
     m, SW = prev_rows.shape
     Kn, dev = int(n_cand), prev_rows.device
     _bufs(dev, (prev_rows, det_rows), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32))
@@ -363,7 +366,9 @@ class ConditionedDeterminizer:
         """rows [m, SW] the current states (seat `seat` to act), prev_rows [m, SW] the states the partner moved from, partner:
         the agent that moved (its eval_moves is called with partner_seed / partner_draw on games first_game_id + i: what it was
         called with in the real game), valid [m] (0: no usable previous state; the root keeps the unconditioned belief). K =
-        replicas * oversample candidates per root are drawn with (seed, draw) and row ids first_row_id + i * K + k.
+        replicas * oversample candidates per root are drawn with (seed, draw) and row ids first_row_id + i * K + k. A prev_rows
+        that is not the state the partner moved from (another deal, a hand of another size for `seat`) gives some legal
+        hypothetical state, not a specified one.
         -> (rows_out [m * replicas, SW] int32, weights [m * replicas] int64, n_surv [m] int32, fallback [m] uint8). `out`: an
         optional (rows_out, weights_u32) pair to write into (the weights then come back as the int32 buffer)."""
         r = _rows(rows, self.state_words)

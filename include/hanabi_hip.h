@@ -849,54 +849,47 @@ int hb_train_tally(const hb_config* cfg, int64_t n_games, int32_t seat, const in
  *   n_pair_dev [m] int32 = n = replicas with w_r > 0.
  * c == base: diff = se = 0. cand[i, c] < 0, no baseline (or cand[i, base] < 0), or sum w = 0: both NaN.
  * 1 <= n_cand <= 64, 1 <= replicas <= 2^20, m * n_cand * replicas < 2^31.
- * hb_belief_splice: "what the partner would have seen". prev_rows_dev [m, hb_state_words()] the states the last mover moved from,
- * det_rows_dev [m * n_cand, SW] hb_belief_determinize's candidates for the observer `seat` (candidate (i, k) = row i * n_cand + k).
+ * hb_belief_splice_alive: "what the partner would have seen". prev_rows_dev [m, hb_state_words()] states the last mover moved
+ * from, now or earlier, det_rows_dev [m * n_cand, SW] hb_belief_determinize's candidates for the observer `seat` (candidate (i, k)
+ * = row i * n_cand + k). alive_dev [m] u8 (NULL: every slot alive): bit s set = the card in slot s of the observer's hand in prev
+ * row i is still in its hand now. Hands are ordered by age (cards slide left on removal, a drawn card goes to the end), so the
+ * cards still held are a prefix of the current hand in the same order, and the others were played or discarded, hence public.
  * out_rows_dev [n_cand * m, SW], candidate-major: row k * m + i = prev row i with ONLY word 10 + seat (the observer's hand word)
- * replaced by that word of candidate (i, k); knowledge, deck bytes and everything else stay the previous state's (another seat's
- * observation and legal mask read the observer's cards, the public state and the deck size, never the deck's order). Slab k is m
- * contiguous rows in the roots' order: it imports into an m-game env whose game ids are the real games'. seat in 0 .. players - 1
- * (no -1: the observer is not the previous state's current player). A pure copy: finished rows are spliced like any other.
- * hb_belief_select: keep the first `replicas` candidates under which the last mover's policy plays the move it played.
- * src_rows_dev [m, SW] the current states, det_rows_dev [m * n_cand, SW] / weight_dev [m * n_cand] u32 the candidates,
- * hyp_moves_dev [n_cand * m] int32 (candidate-major: [k * m + i] = the move under candidate (i, k)), actual_dev [m] int32 the
- * move made, valid_dev [m] u8 or NULL (all valid). Candidate (i, k) SURVIVES iff weight[i, k] != 0 and hyp[k, i] == actual[i].
- * Per root, candidates in ascending k:
- *   n_surv_dev [m] int32 = survivors among all n_cand; the j-th survivor (j < replicas) becomes output replica i * replicas + j:
- *   its determinized row copied whole into out_rows_dev [m * replicas, SW], its weight into out_weight_dev [m * replicas] u32;
- *   0 < n_surv < replicas: replicas j >= n_surv get weight 0 and an unchanged copy of src row i (the dead-replica convention);
- *   n_surv == 0: fallback_dev [m] u8 = 1 and the outputs are candidates 0 .. replicas - 1 with their own weights (the
- *   unconditioned belief: a policy the partner does not follow must not leave the searcher without one);
- *   a root that is not running (status bits of src word 0) or has valid[i] == 0: the same outputs, fallback = 2, n_surv = 0,
- *   hyp and actual are not read for it. Otherwise fallback = 0.
- * One wavefront per root, candidates 64 at a time: a ballot of the predicate, a prefix popcount and a running base give each
- * survivor its rank; no atomics, no LDS, a pure function of the inputs. n_cand >= replicas >= 1, m * n_cand * SW < 2^31.
- * hb_belief_splice_alive: hb_belief_splice for an OLDER previous state, one the observer `seat` has played or discarded cards
- * since. alive_dev [m] u8 (NULL: every slot alive): bit s set = the card in slot s of the observer's hand in prev row i is still
- * in its hand now. Hands are ordered by age (cards slide left on removal, a drawn card goes to the end), so the cards still held
- * are a prefix of the current hand in the same order, and the others were played or discarded, hence public. Row k * m + i of
- * out_rows_dev [n_cand * m, SW] = prev row i with ONLY word 10 + seat rebuilt: walk the slots s = 0 .. 4 of the previous hand
- * that hold a card (field != 31), j = 0; if bit s is alive and slot j of candidate (i, k)'s hand word holds a card, slot s takes
- * that card and j += 1; in every other case (a dead slot; a candidate that has run out of cards, which must not happen but then
- * still leaves a legal state) slot s keeps the previous row's own card. Empty slots stay empty, their alive bits are ignored,
- * bits 25 .. 31 stay the previous row's. With every slot alive and equal hand sizes: hb_belief_splice's output, byte for byte.
- * One wavefront per output row, lane j < SW moves word j, the lane of the hand word does the walk in registers.
- * hb_belief_select_depth: hb_belief_select over the last mover's last `depth` moves, 1 <= depth <= 8, entry 0 the most recent.
- * hyp_moves_dev [depth][n_cand * m] int32 (each slab candidate-major as above: the move under candidate (i, k) spliced into
- * entry d's previous state), actual_dev [depth][m] int32, valid_dev [depth][m] u8 or NULL (all valid); the other inputs as above.
+ * rebuilt: walk the slots s = 0 .. 4 of the previous hand that hold a card (field != 31), j = 0; if bit s is alive and slot j of
+ * candidate (i, k)'s hand word holds a card, slot s takes that card and j += 1; in every other case (a dead slot; a candidate that
+ * has run out of cards, which must not happen but then still leaves a legal state) slot s keeps the previous row's own card.
+ * Empty slots stay empty, their alive bits are ignored, bits 25 .. 31 stay the previous row's. Knowledge, deck bytes and
+ * everything else stay the previous state's (another seat's observation and legal mask read the observer's cards, the public
+ * state and the deck size, never the deck's order). Slab k is m contiguous rows in the roots' order: it imports into an m-game env
+ * whose game ids are the real games'. seat in 0 .. players - 1 (no -1: the observer is not the previous state's current player).
+ * Finished rows are spliced like any other. One wavefront per output row, lane j < SW moves word j, the lane of the hand word
+ * does the walk in registers.
+ * hb_belief_splice = hb_belief_splice_alive with alive NULL: prev_rows_dev are the states the last mover JUST moved from, in
+ * which the observer holds the cards it holds now, so word 10 + seat of row k * m + i is that word of candidate (i, k).
+ * hb_belief_select_depth: keep the first `replicas` candidates under which the last mover's policy plays the most of its last
+ * `depth` moves, 1 <= depth <= 8, entry 0 the most recent. src_rows_dev [m, SW] the current states, det_rows_dev [m * n_cand, SW]
+ * / weight_dev [m * n_cand] u32 the candidates, hyp_moves_dev [depth][n_cand * m] int32 (each slab candidate-major: [k * m + i] =
+ * the move under candidate (i, k) spliced into entry d's previous state), actual_dev [depth][m] int32 the moves made, valid_dev
+ * [depth][m] u8 or NULL (all valid).
  * Per root i: L_i = the number of leading entries d = 0, 1, .. with valid[d][i] != 0 (an invalid entry cuts the chain: nothing
- * older is used); L_i = 0 for a root that is not running. pass_k = the number of leading entries d < L_i with
- * hyp[d][k, i] == actual[d][i]; 0 if weight[i, k] == 0.
+ * older is used); L_i = 0 for a root that is not running (status bits of src word 0). pass_k = the number of leading entries
+ * d < L_i with hyp[d][k, i] == actual[d][i]; 0 if weight[i, k] == 0.
  *   n_surv_dev [depth][m] int32: n_surv[D - 1][i] = candidates with pass_k >= D, for D = 1 .. L_i; 0 for D > L_i;
  *   depth_used_dev [m] int32 = the largest D <= L_i with n_surv[D - 1][i] >= 1, 0 if there is none;
- *   depth_used = D > 0: the candidates with pass_k >= D in ascending k fill replicas 0 .. min(n_surv[D - 1], replicas) - 1, whole
- *   row and weight; the remaining replicas are dead (weight 0, a copy of src row i); fallback = 0. D < L_i is a FALLBACK to a
- *   shallower filter (the deepest had no survivor), not the exact posterior given L_i moves: depth_used says which roots;
- *   depth_used = 0 < L_i: fallback = 1, the outputs are candidates 0 .. replicas - 1 with their own weights;
+ *   depth_used = D > 0: the candidates with pass_k >= D in ascending k fill replicas 0 .. min(n_surv[D - 1], replicas) - 1 (the
+ *   j-th becomes output replica i * replicas + j: its determinized row copied whole into out_rows_dev [m * replicas, SW], its
+ *   weight into out_weight_dev [m * replicas] u32); the remaining replicas are dead (weight 0, an unchanged copy of src row i);
+ *   fallback_dev [m] u8 = 0. D < L_i is a FALLBACK to a shallower filter (the deepest had no survivor), not the exact posterior
+ *   given L_i moves: depth_used says which roots;
+ *   depth_used = 0 < L_i: fallback = 1, the outputs are candidates 0 .. replicas - 1 with their own weights (the unconditioned
+ *   belief: a policy the partner does not follow must not leave the searcher without one);
  *   L_i = 0: the same outputs, fallback = 2; hyp and actual are not read for the root.
- * With depth = 1, out_rows, out_weight, n_surv[0] and fallback are hb_belief_select's, byte for byte. One wavefront per root,
- * candidates 64 at a time: the first sweep accumulates popc(ballot(pass_k >= D)) for each D, the second places the survivors by
- * running base plus prefix popcount and stops once `replicas` are placed; no atomics, no LDS, a pure function of the inputs.
- * n_cand >= replicas >= 1, m * n_cand * SW < 2^31.
+ * One wavefront per root, candidates 64 at a time: the first sweep accumulates popc(ballot(pass_k >= D)) for each D, the second
+ * places the survivors by running base plus prefix popcount and stops once `replicas` are placed; no atomics, no LDS, a pure
+ * function of the inputs. n_cand >= replicas >= 1, m * n_cand * SW < 2^31.
+ * hb_belief_select = hb_belief_select_depth with depth 1 and no depth_used output: hyp_moves_dev [n_cand * m], actual_dev [m],
+ * valid_dev [m] and n_surv_dev [m] are the [1][..] layouts above. Candidate (i, k) survives iff weight[i, k] != 0 and
+ * hyp[k, i] == actual[i]; fallback = 2 for a root that is not running or has valid[i] == 0, 1 for one without a survivor.
  * All eight check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                    */
 int hb_belief_determinize(const hb_config* cfg, const uint32_t* src_rows_dev, int64_t m, int32_t seat, int32_t replicas, uint64_t seed,
                           uint64_t draw, int64_t first_row_id, uint32_t* out_rows_dev, uint32_t* weight_dev, void* stream);

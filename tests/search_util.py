@@ -33,3 +33,24 @@ def _team(name, env_like):
     if name == "iggi_flawed":
         return [RulebasedAgent(PR.iggi_rules, seed=13), RulebasedAgent(PR.flawed_rules, seed=14)]
     return [_dqn(env_like, seed=5), RulebasedAgent(PR.piers_rules, seed=15)]
+
+
+def _conditioned_games():
+    """The two recorded runs of tests/golden/search_belief_lastmove.json (written by tests/golden/gen_search_belief_golden.py,
+    replayed by test_search_belief_gpu.py): Full, 2 players, 16 games of [Piers, Piers] with SearchPlayer(condition=True) in
+    (a) seat 0, (b) both seats with a confirming stage. Everything is Philox draws and integer sums -> plain ints."""
+    from hanabi_agents.rule_based import RulebasedAgent, predefined_rules as PR
+    from hanabi_hip import Evaluator, SearchPlayer
+
+    team = [RulebasedAgent(PR.piers_rules, seed=30), RulebasedAgent(PR.piers_rules, seed=31)]
+    ev = Evaluator("Hanabi-Full", 2, n_games=16, seed=7, record_actions=True)
+    kw = dict(replicas=3, seed=2, z=1.0, condition=True, oversample=4)
+    one = SearchPlayer(team, 0, **kw)
+    both = [SearchPlayer(team, s, confirm_replicas=4, **kw) for s in (0, 1)]
+    out = {}
+    for name, agents, players in (("seat0", [one, team[1]], [one]), ("both", both, both)):
+        res = ev.run(agents)
+        out[name] = dict(scores=res.scores.tolist(), lengths=res.lengths.tolist(), actions=res.actions.tolist(), players=[
+            {k: int(getattr(p, k)) for k in SearchPlayer.COUNTERS + ("rollouts", "dead_replicas", "replicas_drawn", "searches")}
+            for p in players])
+    return out

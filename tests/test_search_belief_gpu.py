@@ -1,10 +1,14 @@
 """The search belief conditioned on the partner's last move, on the GPU (hanabi_hip.search, csrc/belief.hip): hb_belief_splice
 and hb_belief_select against the numpy restatement of tests/test_search_belief_cpu.py byte for byte,
-ConditionedDeterminizer.sample against a rerun by hand, the reconstruction of the state the partner moved from, and the
-guarantees of SearchPlayer(condition=True) and session.search(history=)."""
+ConditionedDeterminizer.sample against a rerun by hand, the reconstruction of the state the partner moved from, the
+guarantees of SearchPlayer(condition=True) and session.search(history=), and the games SearchPlayer(condition=True) plays
+against a recording (tests/golden/search_belief_lastmove.json)."""
+import json
+import os
+
 import numpy as np
 import pytest
-from search_util import _dqn, _u32
+from search_util import _conditioned_games, _dqn, _u32
 
 pytestmark = pytest.mark.gpu
 
@@ -314,6 +318,24 @@ def test_search_player_conditioned():
     with pytest.raises(ValueError, match="2 players"):
         three = [RulebasedAgent(PR.piers_rules, seed=s) for s in range(3)]
         SearchPlayer(three, 0, condition=True)
+
+
+def test_search_player_conditioned_reproduces_the_recorded_games():
+    """Scores, lengths, every action and every counter of the two runs of search_util._conditioned_games equal the file
+    tests/golden/gen_search_belief_golden.py wrote: Philox draws and integer sums only, so the games are the same games."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "search_belief_lastmove.json")) as f:
+        want = json.load(f)
+    got = _conditioned_games()
+    assert sorted(got) == sorted(want) == ["both", "seat0"]
+    for name, run in want.items():
+        assert len(got[name]["players"]) == len(run["players"]) == (1 if name == "seat0" else 2)
+        for field in ("scores", "lengths", "actions"):
+            assert got[name][field] == run[field], (name, field)
+        for s, (p, q) in enumerate(zip(got[name]["players"], run["players"])):
+            assert sorted(p) == sorted(q)
+            for k in q:
+                assert p[k] == q[k], (name, s, k)
+            assert q["conditioned"] > 0 and q["survivors"] < q["candidates"]   # (the filter bites in what was recorded)
 
 
 def test_search_player_conditions_on_a_dqn_partner():

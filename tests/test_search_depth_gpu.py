@@ -1,6 +1,6 @@
 """The search belief conditioned on the partner's last L moves, on the GPU (hanabi_hip.search, csrc/belief.hip):
 hb_belief_splice_alive and hb_belief_select_depth against the numpy restatements of tests/test_search_depth_cpu.py byte for byte
-and against the depth-1 kernels, ConditionedDeterminizer.sample_history against a rerun by hand, and the guarantees of
+and against the depth-1 restatements of tests/test_search_belief_cpu.py, ConditionedDeterminizer.sample_history against a rerun by hand, and the guarantees of
 SearchPlayer(condition=True, depth=L) and session.search(history=PartnerHistory)."""
 import numpy as np
 import pytest
@@ -36,9 +36,10 @@ def _rows_and_candidates(game, players, seat, turns, m, K):
 @pytest.mark.parametrize("K", [5, 70])
 def test_splice_alive_equals_the_restatement(game, players, seat, turns, m, K):
     import torch
+    from test_search_belief_cpu import splice_ref
     from test_search_depth_cpu import splice_alive_ref
 
-    from hanabi_hip import belief_splice, belief_splice_alive
+    from hanabi_hip import belief_splice_alive
 
     env, earlier, rows, det_rows, _ = _rows_and_candidates(game, players, seat, turns, m, K)
     assert env.state_words == (48 if players == 5 else 32)
@@ -53,10 +54,11 @@ def test_splice_alive_equals_the_restatement(game, players, seat, turns, m, K):
     want = splice_alive_ref(_u32(earlier), alive, _u32(det_rows), seat, K)
     assert np.array_equal(_u32(out).reshape(K * m, -1), want)
     assert (want[:m, 10 + seat] != _u32(earlier)[:, 10 + seat]).any() and (want[:m, 10 + seat] != _u32(det_rows)[::K, 10 + seat]).any()
-    # alive = NULL is every slot alive; on the candidates' own rows (equal hand sizes) that is hb_belief_splice byte for byte
+    # alive = NULL is every slot alive; on the candidates' own rows (equal hand sizes) that is the whole hand word taken over
     every = belief_splice_alive(env.cfg, earlier, None, det_rows, seat, K)
     assert np.array_equal(_u32(every).reshape(K * m, -1), splice_alive_ref(_u32(earlier), None, _u32(det_rows), seat, K))
-    assert torch.equal(belief_splice_alive(env.cfg, rows, None, det_rows, seat, K), belief_splice(env.cfg, rows, det_rows, seat, K))
+    own = belief_splice_alive(env.cfg, rows, None, det_rows, seat, K)
+    assert np.array_equal(_u32(own).reshape(K * m, -1), splice_ref(_u32(rows), _u32(det_rows), seat, K))
     buf = torch.empty_like(out)
     assert belief_splice_alive(env.cfg, earlier, torch.as_tensor(alive).cuda(), det_rows, seat, K, out=buf) is buf and torch.equal(buf, out)
 
@@ -107,10 +109,9 @@ def _branches(m, K, D, rng, w):
 @pytest.mark.parametrize("depth", [1, 2, 3, 8])
 def test_select_depth_equals_the_restatement(game, players, seat, turns, m, K, depth):
     """Every branch in one call, the survivors on both sides of the 64-candidate chunk boundaries, a finished root (7) and an
-    all-invalid root (4) among them; and, at depth 1, hb_belief_select byte for byte."""
+    all-invalid root (4) among them; and, at depth 1, the depth-1 restatement of hb_belief_select byte for byte."""
     import torch
-
-    from hanabi_hip import belief_select
+    from test_search_belief_cpu import select_ref
 
     R = 5
     env, _, rows, det_rows, w = _rows_and_candidates(game, players, seat, turns, m, K)
@@ -128,10 +129,10 @@ def test_select_depth_equals_the_restatement(game, players, seat, turns, m, K, d
     assert (depth == 1 or n_surv[last, 6] == 0) and (ow.reshape(m, R)[2, 2:] == 0).all() and (ow.reshape(m, R)[2, :2] != 0).all()
     _select_depth_both(env.cfg, rows, det_rows, w, hyp, actual, None, K, R)   # valid = NULL: every entry valid
     if depth == 1:
-        t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a).astype(dt)).cuda()
-        old = belief_select(env.cfg, rows, det_rows, w, t(hyp[0], np.int32), t(actual[0], np.int32), t(valid[0], np.uint8), R)
-        assert torch.equal(old[0], got[0]) and torch.equal(old[1], got[1]) and torch.equal(old[2], got[2][0])
-        assert torch.equal(old[3], got[4]) and torch.equal(got[3], (old[3] == 0).int())
+        one = select_ref(_u32(rows), _u32(det_rows), _u32(w), hyp[0], actual[0], valid[0], K, R)
+        assert np.array_equal(_u32(got[0]), one[0]) and np.array_equal(_u32(got[1]), one[1])
+        assert np.array_equal(got[2][0].cpu().numpy(), one[2]) and np.array_equal(got[4].cpu().numpy(), one[3])
+        assert np.array_equal(got[3].cpu().numpy(), (one[3] == 0).astype(np.int32))
 
 
 # ---- sample_history -------------------------------------------------------------------------------------------------------------------
