@@ -690,6 +690,54 @@ class DQNAgent:
                                         (st == 2).reshape(-1, 1))
         self.last_obs.copy_(obs8)  # the caller's buffer is rewritten in place by the next env step
 
+    def add_transitions_dense(self, obs_tm1, actions, rewards, terminals, obs_t, legal_t):
+        """Whole transitions out of a branch of P env steps (off-belief learning, hanabi_hip.obl):
+        obs_tm1 / obs_t [n, obs] in either observation form, actions [n], rewards and terminals [P, n] (one row per step of the
+        branch: the learner's move, then each partner's), legal_t [n, A]. With e = the first step whose terminal flag is set (P:
+        none), row g becomes (obs_tm1[g], actions[g], rewards[0][g] + ... + rewards[min(e, P - 1)][g], obs_t[g], legal_t[g],
+        e < P), the last observation and legal mask all zero when e < P: one hb_obl_insert launch on the GPU, the same rule in
+        torch elsewhere. New leaves enter at max priority as in add_experience_dense; last_obs is neither read nor written."""
+        buf = self.experience
+        rew, term = self._vec(rewards, torch.float32), self._vec(terminals, torch.int8)
+        if rew.dim() != 2 or term.shape != rew.shape or not 1 <= rew.shape[0] <= 5:
+            raise ValueError(f"rewards and terminals have shape [P, n] with P in 1..5, got {tuple(rew.shape)} and {tuple(term.shape)}")
+        n = rew.shape[1]
+        o0, o1 = self._obs_store(obs_tm1).contiguous(), self._obs_store(obs_t).contiguous()
+        legal = self._vec(legal_t, torch.int8).contiguous()
+        act = self._vec(actions, torch.int32).contiguous()
+        if o0.shape != (n, buf._obs_tm1_buf.shape[1]) or o1.shape != o0.shape or legal.shape != (n, self.n_actions) or act.shape != (n,):
+            raise ValueError("observations, actions and legal moves must hold one row per game of rewards / terminals")
+        if n > buf.capacity:
+            raise ValueError(f"{n} transitions do not fit a ring of {buf.capacity}")
+        self._dense_call = None
+        if n == 0:
+            return
+        if self.device.type == "cuda":
+            from hanabi_hip import _capi as K
+
+            start = buf.oldest_entry
+            if self.params.use_priority:  # new leaves enter at max priority (priority_buffer.py:29-32)
+                if self.split_update:
+                    self._queue_fill(start, n)   # (set on the stream the updates run on: add_experience_dense)
+                else:
+                    buf.sum_tree.fill_range_dev(start, n, buf._max_priority)
+            K.check(K.lib().hb_obl_insert(K.dptr(o0), K.dptr(act), K.dptr(rew.contiguous()), K.dptr(term.contiguous()), K.dptr(o1),
+                                          K.dptr(legal), K.dptr(buf._obs_tm1_buf), K.dptr(buf._obs_t_buf), K.dptr(buf._act_tm1_buf),
+                                          K.dptr(buf._lms_t_buf), K.dptr(buf._rew_t_buf), K.dptr(buf._terminal_t_buf), n,
+                                          rew.shape[0], o0.shape[1] * o0.element_size(), self.n_actions, buf.capacity, start,
+                                          K.current_stream()))
+            buf._advance(n)
+            return
+        P = rew.shape[0]
+        ended = term != 0
+        e = torch.where(ended.any(0), ended.int().argmax(0), torch.full((n,), P, dtype=torch.int64, device=self.device))
+        total = rew[0].clone()
+        for k in range(1, P):   # ascending, in fp32
+            total = torch.where(e >= k, total + rew[k], total)
+        live = (e == P)[:, None]
+        buf.add_transitions(o0, act.to(torch.int64).reshape(-1, 1), total.reshape(-1, 1), torch.where(live, o1, torch.zeros_like(o1)),
+                            torch.where(live, legal, torch.zeros_like(legal)), (e < P).reshape(-1, 1))
+
     # ---- learning (rlax_rainbow.py:310-339) -----------------------------------------------------------------
     def _sample(self):
         indices, prios = self._sample_indices()

@@ -258,12 +258,7 @@ class SelfPlaySession:
         # [0]: the rich observation source for agents with requires_vectorized_observation() False (rule-based
         # partners read the env's state rows); [1]: the vectorised (obs, legal) pair the DQN agents use
         observations = (env, (env.net_obs, env.legal))   # packed env: the bit rows, which the agents take as they are
-        if self.t < env.players:
-            # only during the first round can a seat be without a pending move (step type FIRST)
-            agent.add_experience_first(observations, env.agent_step_type)
-            agent.add_experience(observations, self.last_actions[seat], env.agent_reward, env.agent_step_type)
-        else:
-            agent.add_experience_dense(observations, self.last_actions[seat], env.agent_reward, env.agent_step_type)
+        self._record(agent, seat, observations)
         early = main is not None
 
         def record_acted():
@@ -284,9 +279,10 @@ class SelfPlaySession:
             # the 100-byte q and legal rows the selection fused into the env step reads)
             actions = agent.act_for_step(observations, explore, actions_out=self._act_buf[seat])
         sel = None
-        if actions is None and self.fuse_select and hasattr(agent, "q_for_step"):
+        if actions is None and self.fuse_select and self._select_in_env and hasattr(agent, "q_for_step"):
             sel = agent.q_for_step(observations, explore)
         if actions is not None:
+            self._before_env_step(agent, seat, actions, observations)
             if early:
                 acted = record_acted()
             env.step(actions)
@@ -298,6 +294,7 @@ class SelfPlaySession:
             self.select_in_env_steps += 1
         else:
             actions = agent.explore(observations) if explore else agent.exploit(observations)
+            self._before_env_step(agent, seat, actions, observations)
             if early:
                 acted = record_acted()
             env.step(actions)
@@ -328,6 +325,22 @@ class SelfPlaySession:
                 K.set_stream(main)
             self._update_done[id(agent)] = done
         self.t += 1
+
+    # ---- what a step records, and when (hanabi_hip.obl.OffBeliefSession records other transitions at another point) ----------
+    _select_in_env = True   # False: the moves are always picked before the env step (never inside hb_env_step_select_packed)
+
+    def _record(self, agent, seat, observations):
+        """The seat's real transition, before it acts: its last observation and move paired with this observation."""
+        env = self.env
+        if self.t < env.players:
+            # only during the first round can a seat be without a pending move (step type FIRST)
+            agent.add_experience_first(observations, env.agent_step_type)
+            agent.add_experience(observations, self.last_actions[seat], env.agent_reward, env.agent_step_type)
+        else:
+            agent.add_experience_dense(observations, self.last_actions[seat], env.agent_reward, env.agent_step_type)
+
+    def _before_env_step(self, agent, seat, actions, observations):
+        """Called with the seat's moves once they are chosen, before `acted` is recorded and the env steps."""
 
     def _learner_stream_of(self, agent):
         """One learner stream with a single rank (measured best: 0.195 ms per step). Data-parallel: one per agent, so that

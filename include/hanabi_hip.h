@@ -400,6 +400,28 @@ int hb_replay_insert(int8_t* last_obs_dev, const int8_t* obs_dev, const int8_t* 
                      uint8_t* ring_term_dev, int64_t n, int32_t obs_len, int32_t n_actions, int64_t capacity,
                      int64_t start, void* stream);
 
+/* ---- off-belief insert (csrc/obl.hip; hanabi_hip/obl.py) -----------
+ * hb_replay_insert's counterpart for transitions that come whole out of a fictitious branch of
+ * n_steps = P env steps (the learner's move, then one per partner) instead of pairing last_obs
+ * with the next observation. Row g of the batch goes to ring slot (start + g) mod capacity.
+ *   obs_tm1 [n, row_bytes]   the observation the move was chosen on (plain bytes: int8 rows or
+ *                            bit-packed int32 rows alike, as in hb_replay_insert)
+ *   actions [n] int32, rewards [n_steps, n] f32, terminal [n_steps, n] int8 (step-major)
+ *   obs_t [n, row_bytes], legal_t [n, n_actions]   what the learner sees after the last step
+ * With e = the first step k with terminal[k][g] != 0, or n_steps when there is none:
+ *   ring_obs_tm1 <- obs_tm1[g], ring_act <- actions[g],
+ *   ring_rew  <- rewards[0][g] + ... + rewards[min(e, n_steps - 1)][g], added in this order in fp32
+ *                (what a finished game emits after its ending step is not used),
+ *   ring_term <- (e < n_steps),
+ *   ring_obs_t, ring_lms <- obs_t[g], legal_t[g] when e == n_steps, else all-zero rows (the ring
+ *                is a pure function of the inputs, whatever the env emits for a finished game).
+ * No buffer is read and written by the same call. n_steps 1..5, n <= capacity, 0 <= start <
+ * capacity; n == 0 is a no-op. The caller advances its ring pointer.                          */
+int hb_obl_insert(const int8_t* obs_tm1_dev, const int32_t* actions_dev, const float* rewards_dev, const int8_t* terminal_dev,
+                  const int8_t* obs_t_dev, const int8_t* legal_t_dev, int8_t* ring_obs_tm1_dev, int8_t* ring_obs_t_dev,
+                  int8_t* ring_act_dev, int8_t* ring_lms_dev, float* ring_rew_dev, uint8_t* ring_term_dev, int64_t n,
+                  int32_t n_steps, int32_t row_bytes, int32_t n_actions, int64_t capacity, int64_t start, void* stream);
+
 /* ---- fused learner pieces (hanabi_agents/rlax_dqn/rlax_rainbow.py:152-217) ---------------
  * dtype codes: 0 = f32, 1 = bf16, 2 = f16.
  *

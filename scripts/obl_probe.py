@@ -1,0 +1,189 @@
+"""Off-belief learning (hanabi_hip.obl) on one MI355X: what the fictitious branch costs and what a short
+run learns.
+
+  step      ms per step of OffBeliefSession against SelfPlaySession (its one-call step, and its ordinary path, which is the one
+            OffBeliefSession extends), 32 768 games of 2-player Hanabi-Full, bf16: each session warmed, then windows of STEPS
+            steps alternated, best of REPS (host clock around a window that ends in a device synchronise);
+  split     event-timed us per launch of the branch's parts at that size, back to back (a floor: in a step they sit between
+            other kernels): state export, determinize, import, scratch env step, the partner's greedy forward, hb_obl_insert, and
+            hb_replay_insert on the same rows for comparison;
+  kernel    registers / spills / LDS of obl_insert_kernel from the compiler's resource remarks (needs hipcc, no GPU);
+  learn     Hanabi-Small, 2 players: two runs (one agent per seat) each of off-belief and plain self-play for the same number of env steps,
+            then greedy self-play score, cross-play between the runs (seats swapped) and convention distance (CrossPlay(responses=True)).
+
+Usage: obl_probe.py [out.json] [--skip-learn] [--learn-steps N]   (default profiles/obl/obl_probe.json)"""
+import json
+import os
+import re
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "hanabi-agents_amd")]
+
+N, STEPS, REPS, WARM = 32768, 200, 3, 80
+
+
+def kernel_resources():
+    """{kernel: {sgprs, vgprs, spill, scratch, lds, occupancy}} of csrc/obl.hip for gfx950, from -Rpass-analysis."""
+    src = os.path.join(ROOT, "hanabi-agents_amd", "csrc", "obl.hip")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    try:
+        p = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-c", src, "-o", os.devnull,
+                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=300)
+    except (OSError, subprocess.TimeoutExpired) as e:
+        return {"error": str(e)}
+    out, cur = {}, None
+    keys = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch", "SGPRs Spill": "sgpr_spill",
+            "VGPRs Spill": "vgpr_spill", "LDS Size [bytes/block]": "lds", "Occupancy [waves/SIMD]": "occupancy"}
+    for line in p.stderr.splitlines():
+        m = re.search(r"remark: .*?Function Name: (\S+)", line)
+        if m:
+            cur = out.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark: .*?\s{2,}([A-Za-z \[\]/]+): (\d+)", line)
+        if m and cur is not None and m.group(1).strip() in keys:
+            cur[keys[m.group(1).strip()]] = int(m.group(2))
+    return out or {"error": p.stderr[-400:]}
+
+
+def main():
+    import argparse
+
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("out", nargs="?", default=os.path.join(ROOT, "profiles", "obl", "obl_probe.json"))
+    ap.add_argument("--skip-learn", action="store_true")
+    ap.add_argument("--learn-steps", type=int, default=4000)
+    opt = ap.parse_args()
+    path, learn_steps = opt.out, opt.learn_steps
+    out = {"kernel": kernel_resources()}
+    print(json.dumps(out["kernel"]), flush=True)
+
+    import torch
+
+    import hanabi_hip
+    from hanabi_agents.rlax_dqn import ActionSpec, DQNAgent, ObservationSpec, RlaxRainbowParams
+    from hanabi_hip import CrossPlay, OffBeliefSession, _capi as K
+    from hanabi_hip.search import Determinizer, _ask
+    from hanabi_hip.selfplay import SelfPlaySession
+
+    if not torch.cuda.is_available():
+        raise SystemExit("obl_probe.py measures on the GPU: none found")
+
+    def agents_for(env, seeds, **kw):
+        base = dict(train_batch_size=256, experience_buffer_size=1 << 19, layers=[512], mask_terminal=True, compute_dtype="bfloat16",
+                    packed_obs=True)
+        base.update(kw)
+        return [DQNAgent(ObservationSpec((env.n, env.obs_len)), ActionSpec(env.num_actions), RlaxRainbowParams(seed=s, **base),
+                         device="cuda") for s in seeds]
+
+    def window(sess, steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            sess.step()
+        sess.flush()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1000 / steps
+
+    # ---- step time ----------------------------------------------------------------------------------------------------------
+    sessions = {}
+    for name, make in (("selfplay", lambda e, a: SelfPlaySession(e, a)),
+                       ("selfplay_ordinary_path", lambda e, a: SelfPlaySession(e, a, native_chain=False)),
+                       ("off_belief", lambda e, a: OffBeliefSession(e, a))):
+        env = hanabi_hip.HanabiEnv("Hanabi-Full", 2, n_games=N, seed=1, packed=True)
+        sessions[name] = make(env, agents_for(env, (1, 2)))
+        window(sessions[name], WARM)
+    ms = {k: [] for k in sessions}
+    for _ in range(REPS):
+        for name, sess in sessions.items():
+            ms[name].append(round(window(sess, STEPS), 4))
+    obl = sessions["off_belief"]
+    out["step"] = dict(games=N, steps_per_window=STEPS, ms_per_step_best={k: min(v) for k, v in ms.items()}, ms_per_step_runs=ms,
+                       ratio_to_selfplay=round(min(ms["off_belief"]) / min(ms["selfplay"]), 3),
+                       ratio_to_ordinary_path=round(min(ms["off_belief"]) / min(ms["selfplay_ordinary_path"]), 3),
+                       native_steps=sessions["selfplay"].native_steps, dead_rows=obl.dead_rows, grad_steps=obl.grad_steps)
+    print(json.dumps(out["step"]), flush=True)
+
+    # ---- the branch, launch by launch ----------------------------------------------------------------------------------------
+    env, sc, agent, partner = obl.env, obl.scratch, obl.agents[0], obl.agents[1]
+    det = Determinizer(config=env.cfg)
+    rows = env.export_state()
+    det_rows, det_w = torch.empty_like(rows), torch.empty(N, dtype=torch.int32, device="cuda")
+    moves = env.random_legal_actions(seed=3, draw=1)
+    scratch = {}
+    buf = agent.experience
+
+    def insert_obl():
+        K.check(K.lib().hb_obl_insert(K.dptr(env.net_obs), K.dptr(moves), K.dptr(obl._rew), K.dptr(obl._term), K.dptr(sc.net_obs),
+                                      K.dptr(sc.legal), K.dptr(buf._obs_tm1_buf), K.dptr(buf._obs_t_buf), K.dptr(buf._act_tm1_buf),
+                                      K.dptr(buf._lms_t_buf), K.dptr(buf._rew_t_buf), K.dptr(buf._terminal_t_buf), N, 2,
+                                      env.net_obs.shape[1] * 4, env.num_actions, buf.capacity, 0, K.current_stream()))
+
+    def insert_replay():
+        hanabi_hip.ops.replay_insert(agent.last_obs, env.net_obs, env.legal, moves, env.agent_reward, env.agent_step_type, buf, 0)
+
+    def scratch_step():
+        sc.import_state(det_rows)   # (a finished game would make the step a no-op: start from the same states every time)
+        obl._scratch_step(moves, 0)
+
+    parts = dict(export_state=lambda: env.export_state(),
+                 determinize=lambda: det.sample(rows, seat=0, replicas=1, seed=1, draw=1, out=(det_rows, det_w)),
+                 import_state=lambda: sc.import_state(det_rows),
+                 import_and_env_step=scratch_step,
+                 partner_forward=lambda: _ask(partner, sc, 1, 1, obl.branch_moves[1], scratch),
+                 obl_insert=insert_obl, replay_insert=insert_replay)
+    split = {}
+    for name, fn in parts.items():
+        for _ in range(10):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(100):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        split[name] = round(e0.elapsed_time(e1) * 10, 2)
+    row = env.net_obs.shape[1] * 4
+    split["obl_insert_bytes"] = N * (4 * row + 2 * env.num_actions + 4 + 2 * (4 + 1) + 1 + 4 + 1)   # read + written, from shapes
+    split["obl_insert_GBps"] = round(split["obl_insert_bytes"] / split["obl_insert"] / 1e3, 1)
+    out["split_us"] = split
+    print(json.dumps(split), flush=True)
+    del sessions, obl, env, sc, agent, partner, buf
+    torch.cuda.empty_cache()
+
+    # ---- a short learning run --------------------------------------------------------------------------------------------------
+    if not opt.skip_learn:
+        n = 4096
+        pool, names = [], []
+        for kind, cls in (("off_belief", OffBeliefSession), ("selfplay", SelfPlaySession)):
+            for seed in (1, 2):
+                env = hanabi_hip.HanabiEnv("Hanabi-Small", 2, n_games=n, seed=100 + seed, packed=True)
+                # one agent per seat (an agent keeps one last_obs per game: plain self-play cannot share it between seats)
+                team = agents_for(env, (seed, seed + 10), experience_buffer_size=1 << 17, train_batch_size=128)
+                sess = cls(env, team)
+                t0 = time.perf_counter()
+                sess.run(learn_steps)
+                torch.cuda.synchronize()
+                pool += team
+                names.append(f"{kind}/{seed}")
+                print(json.dumps(dict(run=names[-1], env_steps=sess.env_steps, grad_steps=sess.grad_steps, seconds=round(time.perf_counter() - t0, 1),
+                                      train_score=round(sess.mean_score(), 3))), flush=True)
+        # run r's agents are pool[2r], pool[2r + 1] (seats 0, 1). Per kind: the two runs' own teams, then the seats swapped between them
+        teams = [(0, 1), (2, 3), (0, 3), (2, 1), (4, 5), (6, 7), (4, 7), (6, 5)]
+        res = CrossPlay("Hanabi-Small", 2, n_games=4096, seed=7, responses=True).run(pool, teams=teams)
+        dist = res.convention_distance()
+        cell = lambda k: [round(res.results[k].mean, 3), round(res.results[k].stderr, 3)]
+        table = {kind: dict(self_play=[cell(b), cell(b + 1)], cross_play=[cell(b + 2), cell(b + 3)],
+                            convention_distance=round(float(dist[b, b + 1]), 4)) for kind, b in (("off_belief", 0), ("selfplay", 4))}
+        out["learn"] = dict(game="Hanabi-Small", players=2, games=n, steps=learn_steps, env_steps=n * learn_steps, agents=names,
+                            eval_games=4096, teams=teams, table=table)
+        print(json.dumps(out["learn"]["table"]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
