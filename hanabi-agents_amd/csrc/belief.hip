@@ -27,6 +27,10 @@
 // popcount (one wavefront per root, rows copied with lane j < SW holding word j). No LDS, barrier or atomic either.
 // hb_belief_splice = splice-alive with alive NULL (the state the partner just moved from: every slot alive);
 // hb_belief_select = select-depth with depth 1: the same two kernels.
+//
+// hb_belief_history_step: a PartnerHistory (the [depth, m] stack of states the partner moved from, with its moves, alive masks and
+// valid flags) advanced by one turn in place: own move out of the alive masks, reset of re-dealt games, push of a new entry. One
+// launch; rows move as contiguous 16-byte items, the byte fields one game per lane (see the kernel).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -446,6 +450,114 @@ __global__ void __launch_bounds__(256) belief_select_depth_kernel(SelectDepthArg
   }
 }
 
+struct HistoryArgs {
+  const int32_t* own;     // [m] or null
+  const uint8_t* reset;   // [m] or null
+  const uint32_t* cur;    // [m, SW] or null: no push
+  const uint32_t* prev;   // [m, SW], with cur
+  uint32_t* rows;         // [depth, m, SW]
+  int32_t* moves;         // [depth, m]
+  uint8_t* alive;         // [depth, m]
+  uint8_t* valid;         // [depth, m]
+  long long m, n_items;   // n_items = m * SW / (words per item): the items of one entry's rows
+  unsigned row_blocks;    // the first row_blocks workgroups move rows, the others do the per-game fields
+  int depth, seat, SW, P, C, R, H;
+};
+
+// One launch, two kinds of workgroup, which touch disjoint memory. Workgroups below row_blocks shift the state rows: an entry's
+// [m, SW] rows are one contiguous run of n_items items (V = uint4 where every base is 16-byte aligned, else one word), thread t
+// owns item t of EVERY entry, loads entries 0 .. depth - 2 and the new row's item into registers and stores them one entry
+// deeper: every load and store of a wavefront is one contiguous run, and no other thread ever touches item t. The other
+// workgroups take one game per lane: its `depth` alive and valid bytes and moves live in registers through the three parts (own
+// move, reset, push), byte loads and stores of consecutive lanes are consecutive. The loops over the entries are unrolled to
+// MAX_DEPTH with uniform guards, so that the arrays stay in registers.
+template <typename V>
+__global__ void __launch_bounds__(256) belief_history_step_kernel(HistoryArgs a) {
+  if (blockIdx.x < a.row_blocks) {
+    const long long t = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (t >= a.n_items) return;
+    V* const rows = reinterpret_cast<V*>(a.rows);
+    V v[MAX_DEPTH - 1];
+#pragma unroll
+    for (int d = 0; d < MAX_DEPTH - 1; ++d) {
+      v[d] = V{};
+      if (d + 1 < a.depth) v[d] = rows[d * a.n_items + t];
+    }
+    const V fresh = reinterpret_cast<const V*>(a.prev)[t];
+#pragma unroll
+    for (int d = 0; d < MAX_DEPTH - 1; ++d)
+      if (d + 1 < a.depth) rows[(d + 1) * a.n_items + t] = v[d];
+    rows[t] = fresh;
+    return;
+  }
+  const long long g = static_cast<long long>(blockIdx.x - a.row_blocks) * 256 + threadIdx.x;
+  if (g >= a.m) return;
+  uint32_t al[MAX_DEPTH], vl[MAX_DEPTH];
+  int32_t mv[MAX_DEPTH];
+#pragma unroll
+  for (int d = 0; d < MAX_DEPTH; ++d) {
+    al[d] = d < a.depth ? a.alive[d * a.m + g] : 0u;
+    vl[d] = d < a.depth ? a.valid[d * a.m + g] : 0u;
+    mv[d] = d < a.depth && a.cur ? a.moves[d * a.m + g] : 0;
+  }
+  if (a.own) {   // a play or discard of slot s: the s-th set bit (of bits 0 .. 4) leaves every entry, valid or not
+    const int uid = a.own[g];
+    if (uid >= 0 && uid < 2 * a.H) {
+      const int s = uid % a.H;
+#pragma unroll
+      for (int d = 0; d < MAX_DEPTH; ++d) {
+        int seen = 0;
+        uint32_t kill = 0u;
+#pragma unroll
+        for (int b = 0; b < 5; ++b) {
+          const int bit = static_cast<int>((al[d] >> b) & 1u);
+          if (bit && seen == s) kill |= 1u << b;
+          seen += bit;
+        }
+        al[d] &= ~kill;
+      }
+    }
+  }
+  if (a.reset && a.reset[g] != 0) {   // a new deal: nothing stored is usable (rows and moves stay)
+#pragma unroll
+    for (int d = 0; d < MAX_DEPTH; ++d) al[d] = vl[d] = 0u;
+  }
+  if (a.cur) {
+    const uint32_t c0 = a.cur[g * a.SW], w2 = a.cur[g * a.SW + 2];
+    const uint32_t p0 = a.prev[g * a.SW], hand = a.prev[g * a.SW + 10 + a.seat];
+    // hanabi_hip.search.last_move_uid
+    const int kind = static_cast<int>((w2 >> 4) & 3u), idx = static_cast<int>((w2 >> 6) & 7u);
+    const int off = static_cast<int>((w2 >> 9) & 7u) - 1;
+    const int col = static_cast<int>((w2 >> 12) & 7u), rank = static_cast<int>((w2 >> 15) & 7u);
+    const int uid = kind == 1 ? idx : kind == 0 ? a.H + idx : kind == 2 ? 2 * a.H + off * a.C + col
+                                                                        : 2 * a.H + (a.P - 1) * a.C + off * a.R + rank;
+    const bool moved = (w2 & 1u) != 0;
+    const int partner = static_cast<int>((w2 >> 1) & 7u);   // the last mover
+    const bool ok = ((c0 >> 19) & 3u) == 0 && moved && partner != a.seat && ((p0 >> 19) & 3u) == 0 &&
+                    static_cast<int>((p0 >> 13) & 7u) == partner;
+    uint32_t occ = 0u;
+#pragma unroll
+    for (int s = 0; s < 5; ++s) occ |= ((hand >> (5 * s)) & 31u) != 31u ? 1u << s : 0u;
+#pragma unroll
+    for (int d = MAX_DEPTH - 1; d >= 1; --d) {
+      al[d] = al[d - 1];
+      vl[d] = vl[d - 1];
+      mv[d] = mv[d - 1];
+    }
+    al[0] = occ;
+    vl[0] = ok ? 1u : 0u;
+    mv[0] = moved ? uid : -1;
+  }
+#pragma unroll
+  for (int d = 0; d < MAX_DEPTH; ++d) {
+    if (d < a.depth) {
+      a.alive[d * a.m + g] = static_cast<uint8_t>(al[d]);
+      a.valid[d * a.m + g] = static_cast<uint8_t>(vl[d]);
+      if (a.cur) a.moves[d * a.m + g] = mv[d];
+    }
+  }
+}
+
 int have_device() {
   static const int ndev = [] {
     int n = 0;
@@ -636,4 +748,41 @@ extern "C" int hb_belief_select_depth(const hb_config* cfg, const uint32_t* src_
     return hb::fail(HB_ERR_INVALID, "m * n_cand * state words must stay below 2^31: split the roots");
   return launch_select(cfg, src_rows_dev, det_rows_dev, weight_dev, hyp_moves_dev, actual_dev, valid_dev, m, n_cand, replicas, depth,
                        out_rows_dev, out_weight_dev, n_surv_dev, depth_used_dev, fallback_dev, stream);
+}
+
+extern "C" int hb_belief_history_step(const hb_config* cfg, int64_t m, int32_t depth, int32_t seat, const int32_t* own_moves_dev,
+                                      const uint8_t* reset_dev, const uint32_t* cur_rows_dev, const uint32_t* prev_rows_dev,
+                                      uint32_t* hist_rows_dev, int32_t* hist_moves_dev, uint8_t* hist_alive_dev, uint8_t* hist_valid_dev,
+                                      void* stream) {
+  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  if (m < 0) return hb::fail(HB_ERR_INVALID, "m must be >= 0");
+  if (depth < 1 || depth > MAX_DEPTH) return hb::fail(HB_ERR_INVALID, "depth %d out of range 1..%d", depth, MAX_DEPTH);
+  if (seat < 0 || seat >= cfg->players) return hb::fail(HB_ERR_INVALID, "seat %d out of range 0..%d", seat, cfg->players - 1);
+  if ((cur_rows_dev == nullptr) != (prev_rows_dev == nullptr))
+    return hb::fail(HB_ERR_INVALID, "cur_rows and prev_rows go together: a push needs both, no push neither");
+  if (!hist_rows_dev || !hist_moves_dev || !hist_alive_dev || !hist_valid_dev) return hb::fail(HB_ERR_INVALID, "null argument");
+  const int SW = hb_state_words(cfg);
+  if (m > ((static_cast<int64_t>(1) << 31) - 1) / (static_cast<int64_t>(depth) * SW))
+    return hb::fail(HB_ERR_INVALID, "m * depth * state words must stay below 2^31: split the games");
+  if (m == 0 || (!own_moves_dev && !reset_dev && !cur_rows_dev)) return HB_OK;
+  if (int rc = have_device()) return rc;
+  HistoryArgs a{};
+  a.own = own_moves_dev; a.reset = reset_dev; a.cur = cur_rows_dev; a.prev = prev_rows_dev;
+  a.rows = hist_rows_dev; a.moves = hist_moves_dev; a.alive = hist_alive_dev; a.valid = hist_valid_dev;
+  a.m = m;
+  a.depth = depth; a.seat = seat; a.SW = SW;
+  a.P = cfg->players; a.C = cfg->colors; a.R = cfg->ranks; a.H = cfg->hand_size;
+  // 16-byte items where the row buffers allow it (a row is 128 or 192 bytes, so every row then starts on a 16-byte boundary)
+  const bool wide = cur_rows_dev && SW % 4 == 0 &&
+                    ((reinterpret_cast<uintptr_t>(hist_rows_dev) | reinterpret_cast<uintptr_t>(prev_rows_dev)) & 15u) == 0;
+  a.n_items = cur_rows_dev ? m * (wide ? SW / 4 : SW) : 0;
+  a.row_blocks = static_cast<unsigned>((a.n_items + 255) / 256);
+  const unsigned blocks = a.row_blocks + static_cast<unsigned>((m + 255) / 256);
+  if (wide)
+    hipLaunchKernelGGL(belief_history_step_kernel<uint4>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  else
+    hipLaunchKernelGGL(belief_history_step_kernel<uint32_t>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
 }

@@ -26,7 +26,9 @@
 * `ConditionedDeterminizer.sample_history` conditions it on the partner's last `depth` moves, kept in a `PartnerHistory`: the
   same candidates carried back to every earlier state the partner moved from (hb_belief_splice_alive: the cards of that older
   hand I still hold are a prefix of the candidate's hand, the others are public), the partner's `eval_moves` on each, and one
-  hb_belief_select_depth. `SearchPlayer(condition=True, depth=L)` keeps the stack itself.
+  hb_belief_select_depth. `SearchPlayer(condition=True, depth=L)` keeps the stack itself. `PartnerHistory.advance` is one turn
+  of that bookkeeping (own move, re-dealt games, push) in one kernel call (hb_belief_history_step): what a training env, whose
+  games end and are dealt anew at different steps, keeps its histories with (hanabi_hip.obl, off-belief learning level 2+).
 * `SearchPlayer` is an agent for `Evaluator.run`: the blueprint's move unless the search finds one that is better by more than
   `threshold` and, with `z` / `confirm_replicas`, by more than z standard errors of the paired difference.
 
@@ -333,6 +335,64 @@ class PartnerHistory:
         self.valid[0] = (vl != 0).to(torch.uint8)
         self.draws = [int(draw)] + self.draws[:-1]
         self.filled = min(self.filled + 1, self.depth)
+
+    def advance(self, own_moves=None, reset=None, cur_rows=None, prev_rows=None, seat=None, draw=None):
+        """One turn of the observer `seat`, for all m games, in this order; each part is skipped when its argument is None:
+
+          own_moves [m] int32   own_move(own_moves): the move I made since the last call;
+          reset [m] (!= 0)      a game that was dealt anew since the last call: its valid and alive entries are cleared;
+          cur_rows, prev_rows   [m, SW], given together with `seat` and `draw`: push(prev_rows, last_move_uid(cfg, cur_rows), draw,
+                                valid, seat=seat), where an entry is valid iff cur is running and names a last mover other than
+                                `seat` in word 2, and prev is running with that mover as its current player.
+
+        A history on the GPU makes ONE kernel call (hb_belief_history_step), in place; on the CPU the same thing is done with the
+        methods above, which is what the kernel is tested against."""
+        dev, m = self.alive.device, self.m
+        push = cur_rows is not None or prev_rows is not None
+        if push:
+            if cur_rows is None or prev_rows is None:
+                raise ValueError("cur_rows and prev_rows go together")
+            if seat is None or draw is None:
+                raise ValueError("a push needs the observer's seat and the draw of the partner's turn")
+        if seat is not None and not 0 <= int(seat) < self.cfg.players:
+            raise ValueError(f"seat {seat} out of range for {self.cfg.players} players")
+
+        def arg(x, shape, dtype, name):
+            if x is None:
+                return None
+            t = torch.as_tensor(x)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} has shape {shape}, got {tuple(t.shape)}")
+            if t.device != dev:
+                raise ValueError(f"{name} lives on {t.device}, the history on {dev}")
+            if dtype == torch.uint8 and t.dtype != torch.uint8:   # a flag of any type
+                t = t.view(torch.uint8) if t.dtype in (torch.int8, torch.bool) else (t != 0).to(torch.uint8)
+            return t.to(dtype).contiguous()
+
+        own = arg(own_moves, (m,), torch.int32, "own_moves")
+        rs = arg(reset, (m,), torch.uint8, "reset")
+        cur = arg(cur_rows, (m, self.state_words), torch.int32, "cur_rows")
+        prev = arg(prev_rows, (m, self.state_words), torch.int32, "prev_rows")
+        if dev.type == "cuda":
+            with torch.cuda.device(dev):
+                K.check(K.lib().hb_belief_history_step(C.byref(self.cfg), m, self.depth, 0 if seat is None else int(seat), K.dptr(own),
+                                                       K.dptr(rs), K.dptr(cur), K.dptr(prev), K.dptr(self.prev_rows),
+                                                       K.dptr(self.moves), K.dptr(self.alive), K.dptr(self.valid), K.current_stream()))
+            if push:
+                self.draws = [int(draw)] + self.draws[:-1]
+                self.filled = min(self.filled + 1, self.depth)
+            return
+        if own is not None:
+            self.own_move(own)
+        if rs is not None:
+            gone = rs != 0
+            self.valid[:, gone] = 0
+            self.alive[:, gone] = 0
+        if push:
+            w2 = cur[:, 2]
+            partner = (w2 >> 1) & 7
+            valid = running(cur) & ((w2 & 1) != 0) & (partner != int(seat)) & running(prev) & (current_player(prev) == partner)
+            self.push(prev, last_move_uid(self.cfg, cur), draw, valid, seat=seat)
 
 
 class ConditionedDeterminizer:

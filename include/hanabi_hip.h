@@ -912,7 +912,23 @@ int hb_train_tally(const hb_config* cfg, int64_t n_games, int32_t seat, const in
  * hb_belief_select = hb_belief_select_depth with depth 1 and no depth_used output: hyp_moves_dev [n_cand * m], actual_dev [m],
  * valid_dev [m] and n_surv_dev [m] are the [1][..] layouts above. Candidate (i, k) survives iff weight[i, k] != 0 and
  * hyp[k, i] == actual[i]; fallback = 2 for a root that is not running or has valid[i] == 0, 1 for one without a survivor.
- * All eight check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                    */
+ * hb_belief_history_step: one observer's partner history (hanabi_hip.search.PartnerHistory: hist_rows_dev [depth, m, SW] the
+ * states the partner moved from, hist_moves_dev [depth, m] int32 the uid it played, hist_alive_dev / hist_valid_dev [depth, m] u8;
+ * entry 0 the newest) advanced by one turn for all m games, in place, in ONE launch. Per game g, in this order, each part skipped
+ * when its pointer is NULL:
+ *   own move: own_moves_dev[g] = uid, a play or discard (0 <= uid < 2 * hand_size) of slot s = uid % hand_size, clears in EVERY
+ *   entry d (whatever its valid flag) the s-th set bit among bits 0 .. 4 of alive[d][g]; nothing when s >= their popcount;
+ *   reset: reset_dev[g] != 0 sets valid[d][g] = alive[d][g] = 0 for all d (a new deal; rows and moves stay);
+ *   push (cur_rows_dev and prev_rows_dev [m, SW], given together): every entry moves one deeper, the oldest is dropped, and entry
+ *   0 becomes rows = prev row g; moves = the last move recorded in word 2 of cur row g (kind 1 play: idx; 0 discard: hand_size +
+ *   idx; 2 colour hint: 2 * hand_size + (offset - 1) * colors + colour; 3 rank hint: 2 * hand_size + (players - 1) * colors +
+ *   (offset - 1) * ranks + rank; -1 when the word's valid bit 0 is clear); alive = the slots s of word 10 + seat of prev row g whose
+ *   5-bit field is not 31; valid = 1 iff cur is running (status bits 19-20 of word 0 are 0), word 2 of cur has bit 0 set, its
+ *   mover (bits 1-3) is not `seat`, prev is running and prev's current player (bits 13-15 of word 0) is that mover.
+ * 1 <= depth <= 8, 0 <= seat < players, m * depth * SW < 2^31. Every word of game g is read and written by that game's threads
+ * alone: no LDS, no atomics, no second buffer. Rows move in 16-byte items where hist_rows_dev and prev_rows_dev are 16-byte
+ * aligned, word by word otherwise; the result is the same.
+ * All nine check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                     */
 int hb_belief_determinize(const hb_config* cfg, const uint32_t* src_rows_dev, int64_t m, int32_t seat, int32_t replicas, uint64_t seed,
                           uint64_t draw, int64_t first_row_id, uint32_t* out_rows_dev, uint32_t* weight_dev, void* stream);
 int hb_search_reduce(const int8_t* score_dev, const uint32_t* weight_dev, const int8_t* legal_dev, int64_t m, int32_t n_actions,
@@ -934,6 +950,10 @@ int hb_belief_select_depth(const hb_config* cfg, const uint32_t* src_rows_dev, c
                            const int32_t* hyp_moves_dev, const int32_t* actual_dev, const uint8_t* valid_dev, int64_t m, int32_t n_cand,
                            int32_t replicas, int32_t depth, uint32_t* out_rows_dev, uint32_t* out_weight_dev, int32_t* n_surv_dev,
                            int32_t* depth_used_dev, uint8_t* fallback_dev, void* stream);
+int hb_belief_history_step(const hb_config* cfg, int64_t m, int32_t depth, int32_t seat, const int32_t* own_moves_dev,
+                           const uint8_t* reset_dev, const uint32_t* cur_rows_dev, const uint32_t* prev_rows_dev,
+                           uint32_t* hist_rows_dev, int32_t* hist_moves_dev, uint8_t* hist_alive_dev, uint8_t* hist_valid_dev,
+                           void* stream);
 
 /* ---- One host call per step: hb_chain_run (csrc/chain.hip, round 3) ------------------------------------------------------
  * The session that drives DQNAgent (rlax_rainbow.py:277-339: explore / add_experience / update once per env step) issues ~25

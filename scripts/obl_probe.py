@@ -11,7 +11,16 @@ run learns.
   learn     Hanabi-Small, 2 players: two runs (one agent per seat) each of off-belief and plain self-play for the same number of env steps,
             then greedy self-play score, cross-play between the runs (seats swapped) and convention distance (CrossPlay(responses=True)).
 
-Usage: obl_probe.py [out.json] [--skip-learn] [--learn-steps N]   (default profiles/obl/obl_probe.json)"""
+  level2    (--level2: this part alone, to profiles/obl/obl_level2_probe.json) off-belief learning level 2 (belief_policy =
+            frozen copies of the session's own starting agents): ms per step at depth 1 and 2 with oversample 4 against the
+            level-1 session and plain self-play, same size and windows as `step`; hb_belief_history_step event-timed alone
+            against the torch path it replaces (own_move + push + the validity rule + last_move_uid) at 32 768 games, depth 4;
+            the counters' rates; registers of the history kernel; and a short ladder on Hanabi-Small: level 1, a frozen_copy,
+            level 2 from fresh agents on that copy's belief, two runs, then self-play, cross-play between the runs and
+            convention distance for both levels.
+
+Usage: obl_probe.py [out.json] [--skip-learn] [--learn-steps N] [--level2] [--level2-steps N]
+       (default profiles/obl/obl_probe.json; with --level2 profiles/obl/obl_level2_probe.json)"""
 import json
 import os
 import re
@@ -25,9 +34,10 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "hanabi-agents_amd")]
 N, STEPS, REPS, WARM = 32768, 200, 3, 80
 
 
-def kernel_resources():
-    """{kernel: {sgprs, vgprs, spill, scratch, lds, occupancy}} of csrc/obl.hip for gfx950, from -Rpass-analysis."""
-    src = os.path.join(ROOT, "hanabi-agents_amd", "csrc", "obl.hip")
+def kernel_resources(name="obl.hip", only=None):
+    """{kernel: {sgprs, vgprs, spill, scratch, lds, occupancy}} of csrc/<name> for gfx950, from -Rpass-analysis (`only`: the
+    kernels whose mangled name contains it)."""
+    src = os.path.join(ROOT, "hanabi-agents_amd", "csrc", name)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     try:
         p = subprocess.run([hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-c", src, "-o", os.devnull,
@@ -45,17 +55,177 @@ def kernel_resources():
         m = re.search(r"remark: .*?\s{2,}([A-Za-z \[\]/]+): (\d+)", line)
         if m and cur is not None and m.group(1).strip() in keys:
             cur[keys[m.group(1).strip()]] = int(m.group(2))
+    if only is not None:
+        out = {k: v for k, v in out.items() if only in k}
     return out or {"error": p.stderr[-400:]}
+
+
+def level2(path, ladder_steps, skip_learn):
+    """The `level2` part; see the module docstring."""
+    import torch
+
+    import hanabi_hip
+    from hanabi_agents.rlax_dqn import ActionSpec, DQNAgent, ObservationSpec, RlaxRainbowParams
+    from hanabi_hip import CrossPlay, OffBeliefSession, PartnerHistory, last_move_uid
+    from hanabi_hip.obl import frozen_copy
+    from hanabi_hip.search import current_player, running
+    from hanabi_hip.selfplay import SelfPlaySession
+
+    if not torch.cuda.is_available():
+        raise SystemExit("obl_probe.py measures on the GPU: none found")
+    out = {"kernel": kernel_resources("belief.hip", only="history_step")}
+    print(json.dumps(out["kernel"]), flush=True)
+
+    def agents_for(env, seeds, **kw):
+        base = dict(train_batch_size=256, experience_buffer_size=1 << 19, layers=[512], mask_terminal=True, compute_dtype="bfloat16",
+                    packed_obs=True)
+        base.update(kw)
+        return [DQNAgent(ObservationSpec((env.n, env.obs_len)), ActionSpec(env.num_actions), RlaxRainbowParams(seed=s, **base),
+                         device="cuda") for s in seeds]
+
+    def window(sess, steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            sess.step()
+        sess.flush()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1000 / steps
+
+    def rates(sess):
+        c = {k: getattr(sess, k) for k in OffBeliefSession.LEVEL_COUNTERS}
+        rows = max(1, c["conditioned_rows"] + c["fallback_rows"] + c["unconditioned_rows"])
+        cond = max(1, c["conditioned_rows"])
+        return dict(c, belief_forwards=sess.belief_forwards, steps=sess.t,
+                    conditioned=round(c["conditioned_rows"] / rows, 4), fallback=round(c["fallback_rows"] / rows, 4),
+                    unconditioned=round(c["unconditioned_rows"] / rows, 4), survivors_per_conditioned_row=round(c["survivors"] / cond, 3),
+                    depth_used_per_conditioned_row=round(c["depth_used_sum"] / cond, 3),
+                    belief_forwards_per_step=round(sess.belief_forwards / max(1, sess.t), 2))
+
+    # ---- step time ----------------------------------------------------------------------------------------------------------
+    def level(depth):
+        return lambda e, a: OffBeliefSession(e, a, belief_policy=[frozen_copy(x) for x in a], depth=depth, oversample=4)
+
+    sessions = {}
+    for name, make in (("selfplay", lambda e, a: SelfPlaySession(e, a)), ("off_belief_level1", lambda e, a: OffBeliefSession(e, a)),
+                       ("level2_depth1", level(1)), ("level2_depth2", level(2))):
+        env = hanabi_hip.HanabiEnv("Hanabi-Full", 2, n_games=N, seed=1, packed=True)
+        sessions[name] = make(env, agents_for(env, (1, 2)))
+        window(sessions[name], WARM)
+    ms = {k: [] for k in sessions}
+    for _ in range(REPS):
+        for name, sess in sessions.items():
+            ms[name].append(round(window(sess, STEPS), 4))
+    best = {k: min(v) for k, v in ms.items()}
+    out["step"] = dict(games=N, steps_per_window=STEPS, oversample=4, ms_per_step_best=best, ms_per_step_runs=ms,
+                       over_level1_ms={k: round(best[k] - best["off_belief_level1"], 4) for k in ("level2_depth1", "level2_depth2")},
+                       estimate_ms={"level2_depth1": 0.36, "level2_depth2": 0.72},
+                       counters={k: rates(sessions[k]) for k in ("level2_depth1", "level2_depth2")})
+    print(json.dumps(out["step"]), flush=True)
+    del sessions
+    torch.cuda.empty_cache()
+
+    # ---- the history kernel against the torch path it replaces ------------------------------------------------------------------
+    depth = 4
+    env = hanabi_hip.HanabiEnv("Hanabi-Full", 2, n_games=N, seed=2, auto_reset=False, packed=True)
+    for t in range(7):
+        env.step(env.random_legal_actions(seed=3, draw=t))
+    prev = env.export_state()
+    own = env.random_legal_actions(seed=4, draw=0)
+    env.step(env.random_legal_actions(seed=3, draw=7))
+    cur = env.export_state()
+    reset = (torch.arange(N, device="cuda") % 7 == 0).to(torch.uint8)
+    cfg, seat = env.cfg, int(current_player(cur)[0].item())
+    hk, ht = PartnerHistory(cfg, N, depth, "cuda"), PartnerHistory(cfg, N, depth, "cuda")
+
+    def torch_path():
+        ht.own_move(own)
+        w2 = cur[:, 2]
+        partner = (w2 >> 1) & 7
+        valid = running(cur) & ((w2 & 1) != 0) & (partner != seat) & running(prev) & (current_player(prev) == partner)
+        ht.push(prev, last_move_uid(cfg, cur), 1, valid.to(torch.uint8), seat=seat)
+
+    def torch_path_with_reset():
+        ht.own_move(own)
+        gone = reset != 0
+        ht.valid[:, gone] = 0
+        ht.alive[:, gone] = 0
+        torch_path()
+
+    parts = dict(kernel=lambda: hk.advance(own_moves=own, cur_rows=cur, prev_rows=prev, seat=seat, draw=1),
+                 kernel_with_reset=lambda: hk.advance(own_moves=own, reset=reset, cur_rows=cur, prev_rows=prev, seat=seat, draw=1),
+                 kernel_no_push=lambda: hk.advance(own_moves=own, reset=reset),
+                 torch_path=torch_path, torch_path_with_reset=torch_path_with_reset)
+    hist = {}
+    for name, fn in parts.items():
+        for _ in range(10):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(100):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        hist[name] = round(e0.elapsed_time(e1) * 10, 2)
+    hist.update(games=N, depth=depth, state_words=env.state_words,
+                kernel_bytes=N * (2 * depth * env.state_words * 4 + 2 * depth * (4 + 1 + 1)),   # read + written, from shapes
+                torch_over_kernel=round(hist["torch_path"] / hist["kernel"], 1))
+    hist["kernel_GBps"] = round(hist["kernel_bytes"] / hist["kernel"] / 1e3, 1)
+    out["history_us"] = hist
+    print(json.dumps(hist), flush=True)
+    del env, hk, ht
+    torch.cuda.empty_cache()
+
+    # ---- a short ladder ------------------------------------------------------------------------------------------------------------
+    if not skip_learn:
+        n, pool, names, runs = 4096, [], [], []
+        for seed in (1, 2):
+            frozen = None
+            for lvl in (1, 2):
+                env = hanabi_hip.HanabiEnv("Hanabi-Small", 2, n_games=n, seed=100 * lvl + seed, packed=True)
+                team = agents_for(env, (seed + 20 * lvl, seed + 20 * lvl + 10), experience_buffer_size=1 << 17, train_batch_size=128)
+                sess = OffBeliefSession(env, team) if lvl == 1 else OffBeliefSession(env, team, belief_policy=frozen, depth=2, oversample=4)
+                t0 = time.perf_counter()
+                sess.run(ladder_steps)
+                torch.cuda.synchronize()
+                info = dict(run=f"level{lvl}/{seed}", env_steps=sess.env_steps, grad_steps=sess.grad_steps,
+                            seconds=round(time.perf_counter() - t0, 1), train_score=round(sess.mean_score(), 3))
+                if lvl == 1:
+                    frozen = [frozen_copy(a) for a in team]
+                else:
+                    info["counters"] = rates(sess)
+                print(json.dumps(info), flush=True)
+                runs.append(info)
+                pool += team
+                names.append(info["run"])
+        # pool: run 1 level 1 (0, 1), level 2 (2, 3); run 2 level 1 (4, 5), level 2 (6, 7). Per level: own teams, then seats swapped
+        teams = [(0, 1), (4, 5), (0, 5), (4, 1), (2, 3), (6, 7), (2, 7), (6, 3)]
+        res = CrossPlay("Hanabi-Small", 2, n_games=4096, seed=7, responses=True).run(pool, teams=teams)
+        dist = res.convention_distance()
+        cell = lambda k: [round(res.results[k].mean, 3), round(res.results[k].stderr, 3)]
+        table = {kind: dict(self_play=[cell(b), cell(b + 1)], cross_play=[cell(b + 2), cell(b + 3)],
+                            convention_distance=round(float(dist[b, b + 1]), 4)) for kind, b in (("level1", 0), ("level2", 4))}
+        out["ladder"] = dict(game="Hanabi-Small", players=2, games=n, steps=ladder_steps, env_steps=n * ladder_steps, depth=2, oversample=4,
+                             agents=names, runs=runs, eval_games=4096, teams=teams, table=table)
+        print(json.dumps(out["ladder"]["table"]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
 
 
 def main():
     import argparse
 
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("out", nargs="?", default=os.path.join(ROOT, "profiles", "obl", "obl_probe.json"))
+    ap.add_argument("out", nargs="?", default=None)
     ap.add_argument("--skip-learn", action="store_true")
     ap.add_argument("--learn-steps", type=int, default=4000)
+    ap.add_argument("--level2", action="store_true")
+    ap.add_argument("--level2-steps", type=int, default=20000)
     opt = ap.parse_args()
+    if opt.level2:
+        return level2(opt.out or os.path.join(ROOT, "profiles", "obl", "obl_level2_probe.json"), opt.level2_steps, opt.skip_learn)
+    opt.out = opt.out or os.path.join(ROOT, "profiles", "obl", "obl_probe.json")
     path, learn_steps = opt.out, opt.learn_steps
     out = {"kernel": kernel_resources()}
     print(json.dumps(out["kernel"]), flush=True)
