@@ -32,7 +32,7 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-static const EnvVariant* find_variant(const hb_config* c) {
+const EnvVariant* find_variant(const hb_config* c) {
   const EnvVariant* (*tables[])(int*) = {variants_full, variants_small, variants_vsmall};
   for (auto get : tables) {
     int n = 0;

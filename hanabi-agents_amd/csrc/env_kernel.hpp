@@ -28,6 +28,8 @@
 #include <stdint.h>
 #include <utility>
 
+struct hb_config;
+
 namespace hb {
 
 enum { MODE_STEP = 0, MODE_OBSERVE = 1, MODE_RESET = 2 };
@@ -380,6 +382,133 @@ __device__ __forceinline__ void wave_sync() {
 template <class K, int G>
 constexpr int env_lds_words() { return G * (K::SWP + K::NWP + K::LW); }
 
+// Sections 1-5 of the canonical observation and the legal-move mask of ONE game as seat `o` sees it, from the game's LDS row and
+// the scalar words the caller already holds (w0, w1, w2, the discard thermometers). `acc` and `legal` arrive cleared. `sg` (SHUF):
+// the observer's colour permutation. The one copy of the encoder: env_wave_step (o = the seat to act) and encode_rows_kernel
+// (any observer) both call it.
+// The way the arguments are passed is load-bearing: `row` and `o` by const reference, the words by value, is what keeps the register
+// counts of every existing env_kernel / env_kernel_shuf / actor+env instantiation where they were before the body moved here
+// (other combinations shift VGPRs of the Full-5p and shuffled kernels). Do not tidy the signature without re-comparing the
+// compiler's resource remarks: DESIGN.md section 4, "The stateless encoder".
+template <class K, bool SHUF>
+__device__ __forceinline__ void encode_seat(const uint32_t* const& row, uint32_t w0, uint32_t w1, uint32_t w2, uint64_t disc, const int& o, uint32_t sg,
+                                            BitAcc<K::NW>& acc, uint64_t& legal) {
+  constexpr int P = K::P, C = K::C, R = K::R, H = K::H;
+  auto hand_n = [&](int p) -> int { return (w1 >> (15 + 3 * p)) & 7; };
+  auto fw = [&](int c) -> int { return (w1 >> (3 * c)) & 7; };
+  auto sig = [&](int c) -> int { return static_cast<int>((sg >> (3 * c)) & 7u); };
+  const int deck_size = w0 & 63, info = (w0 >> 6) & 15, life = (w0 >> 10) & 7;
+  const int n_o = hand_n(o);
+  // 1. other players' hands + "hand is short" flags; hint legality falls out of the same pass
+  static_for<P>([&](auto REL) {
+    constexpr int rel = decltype(REL)::value;
+    int p = o + rel;
+    if (p >= P) p -= P;
+    const int n_p = hand_n(p);
+    acc.template put<K::FLAGS_OFF + rel, 1>(n_p < H ? 1u : 0u);
+    if constexpr (rel >= 1) {
+      const uint32_t hc = row[K::W_HANDS + p];
+      uint32_t cmask = 0, rmask = 0;
+      static_for<H>([&](auto I) {
+        constexpr int i = decltype(I)::value;
+        const int card = (hc >> (5 * i)) & 31;
+        const bool have = i < n_p;
+        if constexpr (SHUF) {  // the card as the observer sees it; a colour hint is legal on the colour it sees
+          const int col = have ? card / R : 0, rk = card - col * R, sc = sig(col);
+          acc.template put<((rel - 1) * H + i) * K::BITS, K::BITS>(have ? (1u << (sc * R + rk)) : 0u);
+          if (have) { cmask |= 1u << sc; rmask |= 1u << rk; }
+        } else {
+          acc.template put<((rel - 1) * H + i) * K::BITS, K::BITS>(have ? (1u << card) : 0u);
+          if (have) { cmask |= 1u << (card / R); rmask |= 1u << (card % R); }
+        }
+      });
+      if (info > 0) {
+        legal |= static_cast<uint64_t>(cmask) << (2 * H + (rel - 1) * C);
+        legal |= static_cast<uint64_t>(rmask) << (2 * H + (P - 1) * C + (rel - 1) * R);
+      }
+    }
+  });
+  const uint32_t own = (1u << n_o) - 1u;
+  if (info < K::INFO) legal |= own;
+  legal |= static_cast<uint64_t>(own) << H;
+  // 2. board
+  acc.template put64<K::BOARD_OFF, K::DECK_T>((1ull << deck_size) - 1ull);
+  if constexpr (SHUF) {  // firework c moves to block sig(c)
+    uint32_t fwv = 0;
+    static_for<C>([&](auto CI) {
+      constexpr int c = decltype(CI)::value;
+      fwv |= ((1u << fw(c)) >> 1) << (R * sig(c));
+    });
+    acc.template put<K::FW_OFF, K::BITS>(fwv);
+  } else {
+    static_for<C>([&](auto CI) {
+      constexpr int c = decltype(CI)::value;
+      acc.template put<K::FW_OFF + c * R, R>((1u << fw(c)) >> 1);
+    });
+  }
+  acc.template put<K::INFO_OFF, K::INFO>((1u << info) - 1u);
+  acc.template put<K::LIFE_OFF, K::LIFE>((1u << life) - 1u);
+  // 3. discards: one thermometer per card identity,
+  if constexpr (SHUF) {  // colour-major blocks of CPC bits: block c moves to block sig(c)
+    uint64_t dv = 0;
+    static_for<C>([&](auto CI) {
+      constexpr int c = decltype(CI)::value;
+      dv |= ((disc >> (c * K::CPC)) & ((1ull << K::CPC) - 1ull)) << (K::CPC * sig(c));
+    });
+    acc.template put64<K::DISC_OFF, K::D>(dv);
+  } else {
+    acc.template put64<K::DISC_OFF, K::D>(disc);  // kept in this very form in the state row
+  }
+  // 4. most recent move, observer-relative
+  {
+    const uint32_t valid = w2 & 1u;
+    const int la_player = (w2 >> 1) & 7, la_type = (w2 >> 4) & 3, la_ci = (w2 >> 6) & 7, la_toff = (w2 >> 9) & 7;
+    const int la_color_t = (w2 >> 12) & 7, la_rank = (w2 >> 15) & 7;
+    const int la_color = SHUF ? sig(la_color_t) : la_color_t;
+    const uint32_t la_scored = (w2 >> 18) & 1u, la_info = (w2 >> 19) & 1u, la_mask = (w2 >> 20) & 31u;
+    int actor = la_player - o;
+    if (actor < 0) actor += P;
+    int target = actor + la_toff;
+    if (target >= P) target -= P;
+    const uint32_t reveal = valid & static_cast<uint32_t>(la_type >= MV_RCOLOR);
+    const uint32_t cardmv = valid & static_cast<uint32_t>(la_type <= MV_DISCARD);
+    const uint32_t is_rc = valid & static_cast<uint32_t>(la_type == MV_RCOLOR);
+    const uint32_t is_rr = valid & static_cast<uint32_t>(la_type == MV_RRANK);
+    const uint32_t is_play = valid & static_cast<uint32_t>(la_type == MV_PLAY);
+    constexpr int o1 = K::LA_OFF, o2 = o1 + P, o3 = o2 + 4, o4 = o3 + P, o5 = o4 + C, o6 = o5 + R, o7 = o6 + H,
+                  o8 = o7 + H, o9 = o8 + K::BITS;
+    acc.template put<o1, P>(valid << actor);
+    acc.template put<o2, 4>(valid << la_type);
+    acc.template put<o3, P>(reveal << target);
+    acc.template put<o4, C>(is_rc << la_color);
+    acc.template put<o5, R>(is_rr << la_rank);
+    acc.template put<o6, H>(reveal ? la_mask : 0u);
+    acc.template put<o7, H>(cardmv << la_ci);
+    acc.template put<o8, K::BITS>(cardmv << (la_color * R + la_rank));
+    acc.template put<o9, 2>((is_play & la_scored) | ((is_play & la_info) << 1));
+  }
+  // 5. card knowledge, observer first
+  static_for<P>([&](auto REL) {
+    constexpr int rel = decltype(REL)::value;
+    int p = o + rel;
+    if (p >= P) p -= P;
+    const int n_p = hand_n(p);
+    const uint64_t kn = (static_cast<uint64_t>(row[K::W_KNOW + 2 * p + 1]) << 32) | row[K::W_KNOW + 2 * p];
+    static_for<H>([&](auto I) {
+      constexpr int i = decltype(I)::value;
+      const uint32_t k = static_cast<uint32_t>(kn >> (12 * i)) & 0xFFFu;
+      // (SHUF: colour-plausibility bit c moves to bit sig(c), for the plausible identities and the revealed colour alike)
+      const uint32_t cp = seen_colours<SHUF, C>(k & 31u, sg), rp = (k >> 5) & 31u;
+      const uint32_t plaus = __umul24(spread_colors<C, R>(cp), rp);  // disjoint R-bit fields: no carries
+      const uint32_t ch = (k >> 10) & 1u, rh = (k >> 11) & 1u;
+      uint64_t v = plaus | (static_cast<uint64_t>(ch ? cp : 0u) << K::BITS) |
+                   (static_cast<uint64_t>(rh ? rp : 0u) << (K::BITS + C));
+      if (i >= n_p) v = 0;
+      acc.template put64<K::KN_OFF + (rel * H + i) * K::KN_SLOT, K::KN_SLOT>(v);
+    });
+  });
+}
+
 // The env step of ONE wavefront: games [g0, g0 + G) of the batch, lane g < G owning game g0 + g. `srow` is the wavefront's own LDS
 // slice of env_lds_words<K, G>() words, `uid_in` the lane's move (MODE_STEP; ignored by the other modes, and by lanes past the
 // batch), `wslot` the wavefront's slot in the per-wavefront stats (g0 / G). Shared by env_kernel and by the one-kernel actor's
@@ -691,121 +820,11 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
       const int o = (w0 >> 13) & 7;
       uint32_t sg = 0;  // (SHUF) the observer's permutation: true colour c is seen as colour sig(c)
       if constexpr (SHUF) sg = perm_of(pm, o);
-      auto sig = [&](int c) -> int { return static_cast<int>((sg >> (3 * c)) & 7u); };
       if constexpr (LPG == 1) {
-        const int deck_size = w0 & 63, info = (w0 >> 6) & 15, life = (w0 >> 10) & 7;
         BitAcc<K::NW> acc;
         acc.clear();
         uint64_t legal = 0;
-        const int n_o = hand_n(o);
-        // 1. other players' hands + "hand is short" flags; hint legality falls out of the same pass
-        static_for<P>([&](auto REL) {
-          constexpr int rel = decltype(REL)::value;
-          int p = o + rel;
-          if (p >= P) p -= P;
-          const int n_p = hand_n(p);
-          acc.template put<K::FLAGS_OFF + rel, 1>(n_p < H ? 1u : 0u);
-          if constexpr (rel >= 1) {
-            const uint32_t hc = row[K::W_HANDS + p];
-            uint32_t cmask = 0, rmask = 0;
-            static_for<H>([&](auto I) {
-              constexpr int i = decltype(I)::value;
-              const int card = (hc >> (5 * i)) & 31;
-              const bool have = i < n_p;
-              if constexpr (SHUF) {  // the card as the observer sees it; a colour hint is legal on the colour it sees
-                const int col = have ? card / R : 0, rk = card - col * R, sc = sig(col);
-                acc.template put<((rel - 1) * H + i) * K::BITS, K::BITS>(have ? (1u << (sc * R + rk)) : 0u);
-                if (have) { cmask |= 1u << sc; rmask |= 1u << rk; }
-              } else {
-                acc.template put<((rel - 1) * H + i) * K::BITS, K::BITS>(have ? (1u << card) : 0u);
-                if (have) { cmask |= 1u << (card / R); rmask |= 1u << (card % R); }
-              }
-            });
-            if (info > 0) {
-              legal |= static_cast<uint64_t>(cmask) << (2 * H + (rel - 1) * C);
-              legal |= static_cast<uint64_t>(rmask) << (2 * H + (P - 1) * C + (rel - 1) * R);
-            }
-          }
-        });
-        const uint32_t own = (1u << n_o) - 1u;
-        if (info < K::INFO) legal |= own;
-        legal |= static_cast<uint64_t>(own) << H;
-        // 2. board
-        acc.template put64<K::BOARD_OFF, K::DECK_T>((1ull << deck_size) - 1ull);
-        if constexpr (SHUF) {  // firework c moves to block sig(c)
-          uint32_t fwv = 0;
-          static_for<C>([&](auto CI) {
-            constexpr int c = decltype(CI)::value;
-            fwv |= ((1u << fw(c)) >> 1) << (R * sig(c));
-          });
-          acc.template put<K::FW_OFF, K::BITS>(fwv);
-        } else {
-          static_for<C>([&](auto CI) {
-            constexpr int c = decltype(CI)::value;
-            acc.template put<K::FW_OFF + c * R, R>((1u << fw(c)) >> 1);
-          });
-        }
-        acc.template put<K::INFO_OFF, K::INFO>((1u << info) - 1u);
-        acc.template put<K::LIFE_OFF, K::LIFE>((1u << life) - 1u);
-        // 3. discards: one thermometer per card identity,
-        if constexpr (SHUF) {  // colour-major blocks of CPC bits: block c moves to block sig(c)
-          uint64_t dv = 0;
-          static_for<C>([&](auto CI) {
-            constexpr int c = decltype(CI)::value;
-            dv |= ((disc >> (c * K::CPC)) & ((1ull << K::CPC) - 1ull)) << (K::CPC * sig(c));
-          });
-          acc.template put64<K::DISC_OFF, K::D>(dv);
-        } else {
-          acc.template put64<K::DISC_OFF, K::D>(disc);  // kept in this very form in the state row
-        }
-        // 4. most recent move, observer-relative
-        {
-          const uint32_t valid = w2 & 1u;
-          const int la_player = (w2 >> 1) & 7, la_type = (w2 >> 4) & 3, la_ci = (w2 >> 6) & 7, la_toff = (w2 >> 9) & 7;
-          const int la_color_t = (w2 >> 12) & 7, la_rank = (w2 >> 15) & 7;
-          const int la_color = SHUF ? sig(la_color_t) : la_color_t;
-          const uint32_t la_scored = (w2 >> 18) & 1u, la_info = (w2 >> 19) & 1u, la_mask = (w2 >> 20) & 31u;
-          int actor = la_player - o;
-          if (actor < 0) actor += P;
-          int target = actor + la_toff;
-          if (target >= P) target -= P;
-          const uint32_t reveal = valid & static_cast<uint32_t>(la_type >= MV_RCOLOR);
-          const uint32_t cardmv = valid & static_cast<uint32_t>(la_type <= MV_DISCARD);
-          const uint32_t is_rc = valid & static_cast<uint32_t>(la_type == MV_RCOLOR);
-          const uint32_t is_rr = valid & static_cast<uint32_t>(la_type == MV_RRANK);
-          const uint32_t is_play = valid & static_cast<uint32_t>(la_type == MV_PLAY);
-          constexpr int o1 = K::LA_OFF, o2 = o1 + P, o3 = o2 + 4, o4 = o3 + P, o5 = o4 + C, o6 = o5 + R, o7 = o6 + H,
-                        o8 = o7 + H, o9 = o8 + K::BITS;
-          acc.template put<o1, P>(valid << actor);
-          acc.template put<o2, 4>(valid << la_type);
-          acc.template put<o3, P>(reveal << target);
-          acc.template put<o4, C>(is_rc << la_color);
-          acc.template put<o5, R>(is_rr << la_rank);
-          acc.template put<o6, H>(reveal ? la_mask : 0u);
-          acc.template put<o7, H>(cardmv << la_ci);
-          acc.template put<o8, K::BITS>(cardmv << (la_color * R + la_rank));
-          acc.template put<o9, 2>((is_play & la_scored) | ((is_play & la_info) << 1));
-        }
-        // 5. card knowledge, observer first
-        static_for<P>([&](auto REL) {
-          constexpr int rel = decltype(REL)::value;
-          int p = o + rel;
-          if (p >= P) p -= P;
-          const int n_p = hand_n(p);
-          const uint64_t kn = (static_cast<uint64_t>(row[K::W_KNOW + 2 * p + 1]) << 32) | row[K::W_KNOW + 2 * p];
-          static_for<H>([&](auto I) {
-            constexpr int i = decltype(I)::value;
-            const uint32_t k = static_cast<uint32_t>(kn >> (12 * i)) & 0xFFFu;
-            // (SHUF: colour-plausibility bit c moves to bit sig(c), for the plausible identities and the revealed colour alike)
-            const uint32_t cp = seen_colours<SHUF, C>(k & 31u, sg), rp = (k >> 5) & 31u;
-            const uint32_t plaus = __umul24(spread_colors<C, R>(cp), rp);  // disjoint R-bit fields: no carries
-            const uint32_t ch = (k >> 10) & 1u, rh = (k >> 11) & 1u;
-            uint64_t v = plaus | (static_cast<uint64_t>(ch ? cp : 0u) << K::BITS) |
-                         (static_cast<uint64_t>(rh ? rp : 0u) << (K::BITS + C));
-            if (i >= n_p) v = 0;
-            acc.template put64<K::KN_OFF + (rel * H + i) * K::KN_SLOT, K::KN_SLOT>(v);
-          });
-        });
+        encode_seat<K, SHUF>(row, w0, w1, w2, disc, o, sg, acc, legal);
         uint32_t* ob = obits + lane * K::NWP;
   #pragma unroll
         for (int i = 0; i < K::NW; ++i) ob[i] = acc.w[i];
@@ -976,20 +995,112 @@ void launch_env_shuf(const EnvArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL((env_kernel_shuf<K, G>), dim3(blocks), dim3(256), 0, stream, a);
 }
 
+// ---- stateless encoder (hb_encode_rows; csrc/encode_rows.hip) ---------------------------------------------
+// The observation and legal mask of state rows that belong to no env: phase 1's row copy, encode_seat, phase 3's stores, and
+// nothing else of the env step (no move, no re-deal, no deck pool, no counters). The rows are read only.
+struct EncodeArgs {
+  const uint32_t* rows;  // [n, SW], hb_env_export_state's layout
+  uint32_t* obs_bits;    // [n, NW] or NULL
+  int8_t* obs;           // [n, OBS_LEN] or NULL
+  int8_t* legal;         // [n, A] or NULL
+  long long n;
+  int seat;              // -1: each row's seat to act; else the observer of every row (legal all zero where it is not to act)
+};
+
+template <class K, int G>
+__global__ __launch_bounds__(256) void encode_rows_kernel(const EncodeArgs a) {
+  __shared__ uint32_t lds[4 * env_lds_words<K, G>()];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const long long g0 = (static_cast<long long>(blockIdx.x) * 4 + wave) * G;
+  uint32_t* const srow = lds + wave * env_lds_words<K, G>();
+  uint32_t* const obits = srow + G * K::SWP;
+  uint32_t* const lbits = obits + G * K::NWP;
+  const long long left = a.n - g0;
+  if (left <= 0) return;  // (wave-uniform; waves share nothing)
+  const int nvalid = left < G ? static_cast<int>(left) : G;
+  {  // rows HBM -> LDS: every 16-byte piece requested before the first is written (env_wave_step, phase 1)
+    constexpr int Q = K::SW / 4;
+    constexpr int ROUNDS = (G * Q + 63) / 64;
+    const uint4* src = reinterpret_cast<const uint4*>(a.rows + g0 * K::SW);
+    uint4 v[ROUNDS];
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+      const int e = lane + 64 * r;
+      v[r] = e < nvalid * Q ? src[e] : make_uint4(0u, 0u, 0u, 0u);
+    }
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) {
+      const int e = lane + 64 * r;
+      if (e < nvalid * Q) {
+        const int g = e / Q, q = e - g * Q;
+        uint32_t* d = srow + g * K::SWP + 4 * q;
+        d[0] = v[r].x; d[1] = v[r].y; d[2] = v[r].z; d[3] = v[r].w;
+      }
+    }
+  }
+  wave_sync();
+  if (lane < nvalid) {  // one lane per game (nvalid <= G <= 64)
+    const uint32_t* row = srow + lane * K::SWP;
+    const uint32_t w0 = row[0], w1 = row[1], w2 = row[2];
+    const uint64_t disc = (static_cast<uint64_t>(row[9]) << 32) | row[8];
+    const int cur = (w0 >> 13) & 7;
+    const int o = a.seat < 0 ? cur : a.seat;
+    BitAcc<K::NW> acc;
+    acc.clear();
+    uint64_t legal = 0;
+    encode_seat<K, false>(row, w0, w1, w2, disc, o, 0u, acc, legal);
+    if (o != cur) legal = 0;  // not this seat's turn: it has no move
+    uint32_t* ob = obits + lane * K::NWP;
+#pragma unroll
+    for (int i = 0; i < K::NW; ++i) ob[i] = acc.w[i];
+#pragma unroll
+    for (int i = K::NW; i < K::NWP; ++i) ob[i] = 0;
+    uint32_t* lb = lbits + lane * K::LW;
+    lb[0] = static_cast<uint32_t>(legal);
+    lb[1] = static_cast<uint32_t>(legal >> 32);
+    lb[2] = 0;
+  }
+  wave_sync();
+  if (a.obs_bits) {  // the wave's nvalid x NW words are one contiguous span (env_wave_step, phase 3)
+    uint32_t* dst = a.obs_bits + g0 * K::NW;
+    for (int e = lane; e < nvalid * K::NW; e += 64) {
+      const int g = e / K::NW, i = e - g * K::NW;
+      dst[e] = obits[g * K::NWP + i];
+    }
+  }
+  if (a.obs) expand_rows<K::OBS_LEN>(obits, K::NWP, nvalid, a.obs + g0 * K::OBS_LEN, lane);
+  if (a.legal) expand_rows<K::A>(lbits, K::LW, nvalid, a.legal + g0 * K::A, lane);
+}
+
+template <class K, int G>
+void launch_encode(const EncodeArgs& a, hipStream_t stream) {
+  const long long per_block = 4LL * G;
+  const unsigned blocks = static_cast<unsigned>((a.n + per_block - 1) / per_block);
+  if (blocks == 0) return;
+  hipLaunchKernelGGL((encode_rows_kernel<K, G>), dim3(blocks), dim3(256), 0, stream, a);
+}
+
 using LaunchFn = void (*)(const EnvArgs&, hipStream_t);
+using EncodeFn = void (*)(const EncodeArgs&, hipStream_t);
 struct EnvVariant {
   int P, C, R, H, INFO, LIFE;
   int obs_len, n_actions, deck, state_words;
   LaunchFn g8, g16, g32, g64, refill;
   LaunchFn s8, s16, s32, s64;  // the colour-permuted step (env_kernel_shuf)
+  EncodeFn e16, e32;           // the stateless encoder (encode_rows_kernel)
 };
 
 template <class K>
 constexpr EnvVariant make_variant() {
   return EnvVariant{K::P, K::C, K::R, K::H, K::INFO, K::LIFE, K::OBS_LEN, K::A, K::D, K::SW,
                     &launch_env<K, 8>, &launch_env<K, 16>, &launch_env<K, 32>, &launch_env<K, 64>, &launch_refill<K>,
-                    &launch_env_shuf<K, 8>, &launch_env_shuf<K, 16>, &launch_env_shuf<K, 32>, &launch_env_shuf<K, 64>};
+                    &launch_env_shuf<K, 8>, &launch_env_shuf<K, 16>, &launch_env_shuf<K, 32>, &launch_env_shuf<K, 64>,
+                    &launch_encode<K, 16>, &launch_encode<K, 32>};
 }
+
+// the compiled variant of a configuration, or nullptr (env_api.hip)
+const EnvVariant* find_variant(const ::hb_config* c);
 
 // The one-kernel actor with the env step as its tail (actor_fused.hip; hb_actor_fused_act_step): the configurations it is compiled
 // for, and its launch with the env arguments `env` prepared as for hb_env_step_packed (actions are the kernel's own selections)

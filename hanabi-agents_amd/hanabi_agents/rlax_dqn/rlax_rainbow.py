@@ -114,6 +114,10 @@ class DQNLearning:
 
 
 class DQNAgent:
+    # eval_moves reads observations[1], the (observation, legal mask) pair, and nothing else of what it is handed: a caller
+    # that has the pair from somewhere else than an env (hanabi_hip.encode_rows) may pass (None, (obs, legal))
+    obs_only_eval = True
+
     def __init__(self, observation_spec, action_spec, params: RlaxRainbowParams = RlaxRainbowParams(), device=None,
                  process_group=None, use_graphs=True, use_fused_learner=True):
         if not callable(params.epsilon):

@@ -5,7 +5,7 @@ PyTorch is used only for device memory and streams: every call hands raw device 
 There is no CPU path: constructing an env or a tree without the compiled library or
 without a GPU raises.
 
-Public names: `HanabiEnv`, `SumTree`, `Evaluator`, `EvalResult`, `CrossPlay`, `CrossPlayResult`, `PartnerPool`, `PartnerStats`, `Determinizer`, `ConditionedDeterminizer`, `RolloutSearch`, `SearchPlayer`, `SearchResult`, `belief_splice`, `belief_select`, `belief_splice_alive`, `belief_select_depth`, `PartnerHistory`, `last_move_uid`, `OffBeliefSession`, `make_config`, `HbConfig`, `lib`, flag constants.
+Public names: `HanabiEnv`, `SumTree`, `Evaluator`, `EvalResult`, `CrossPlay`, `CrossPlayResult`, `PartnerPool`, `PartnerStats`, `Determinizer`, `ConditionedDeterminizer`, `RolloutSearch`, `SearchPlayer`, `SearchResult`, `belief_splice`, `belief_select`, `belief_splice_alive`, `belief_select_depth`, `PartnerHistory`, `last_move_uid`, `OffBeliefSession`, `encode_rows`, `encode_rows_ref`, `make_config`, `HbConfig`, `lib`, flag constants.
 """
 from ._capi import (FLAG_AUTO_RESET, FLAG_LENIENT_REWARD, FLAG_RESET_START_NEXT, GAME_TYPES, HbConfig, HbError,
                     lib, library_path, make_config)
@@ -19,6 +19,7 @@ from .search import (ConditionedDeterminizer, Determinizer, PartnerHistory, Roll
                      last_move_uid)
 from .tree import SumTree
 from .obl import OffBeliefSession
+from .encode import encode_rows, encode_rows_ref
 
-__all__ = ["ops", "HanabiEnv", "SumTree", "Evaluator", "EvalResult", "CrossPlay", "CrossPlayResult", "PartnerPool", "PartnerStats", "Determinizer", "ConditionedDeterminizer", "RolloutSearch", "SearchPlayer", "SearchResult", "belief_splice", "belief_select", "belief_splice_alive", "belief_select_depth", "PartnerHistory", "last_move_uid", "OffBeliefSession", "make_config", "HbConfig", "HbError", "lib", "library_path", "GAME_TYPES",
+__all__ = ["ops", "HanabiEnv", "SumTree", "Evaluator", "EvalResult", "CrossPlay", "CrossPlayResult", "PartnerPool", "PartnerStats", "Determinizer", "ConditionedDeterminizer", "RolloutSearch", "SearchPlayer", "SearchResult", "belief_splice", "belief_select", "belief_splice_alive", "belief_select_depth", "PartnerHistory", "last_move_uid", "OffBeliefSession", "encode_rows", "encode_rows_ref", "make_config", "HbConfig", "HbError", "lib", "library_path", "GAME_TYPES",
            "FLAG_AUTO_RESET", "FLAG_RESET_START_NEXT", "FLAG_LENIENT_REWARD"]

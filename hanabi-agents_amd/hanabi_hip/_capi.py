@@ -124,6 +124,7 @@ SIGNATURES = {
     "hb_env_export_state": (C.c_int, [_P, _P, _P]),
     "hb_env_import_state": (C.c_int, [_P, _P, _P]),
     "hb_env_state": (_P, [_P]),
+    "hb_encode_rows": (C.c_int, [_CFG, _P, _I64, _I32, _P, _P, _P, _P]),
     "hb_env_set_color_shuffle": (C.c_int, [_P, _P, C.c_uint8, _P]),
     "hb_env_color_perms": (C.c_int, [_P, _P, _P]),
     "hb_env_color_shuffled": (C.c_int, [_P]),

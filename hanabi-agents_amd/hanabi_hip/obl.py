@@ -44,9 +44,11 @@ to the V0 belief. Fallbacks are normal; they are counted (`conditioned_rows`, `f
 `depth_used_sum`, `belief_forwards`), never errors. With `belief_policy=None` (the default) nothing of this exists and the session
 is level 1, bit for bit.
 
-Not built: three and more players at level 2+, the branch on hb_chain_run, a stateless row-to-observation encoder or one forward
-over all `oversample` slabs (either would take the import and observe per slab away), and soft (epsilon-aware) likelihood weights
-instead of exact-match filtering.
+The frozen policy's observations of the K candidate slabs come from one hb_encode_rows call (`self.cdet.stateless`, on by default;
+False: an import and an observe per slab on a scratch env, the same bits).
+
+Not built: three and more players at level 2+, the branch on hb_chain_run, one forward over all `oversample` slabs, and soft
+(epsilon-aware) likelihood weights instead of exact-match filtering.
 """
 import weakref
 

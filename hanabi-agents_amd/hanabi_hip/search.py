@@ -40,6 +40,7 @@ import weakref
 import torch
 
 from . import _capi as K
+from .encode import encode_rows
 from .env import HanabiEnv
 from .evaluate import eval_config, max_turns
 
@@ -399,11 +400,17 @@ class ConditionedDeterminizer:
     """The V0 belief conditioned on the partner's last move: candidates from `Determinizer`, the previous
     state with each candidate hand spliced in (hb_belief_splice), the partner's move in each of them (its `eval_moves` on an
     m-game scratch env, one slab of candidates at a time), and the first `replicas` candidates under which that move is the one
-    the partner made (hb_belief_select). The scratch env and the buffers are kept per (m, K)."""
+    the partner made (hb_belief_select). The scratch env and the buffers are kept per (m, K).
 
-    def __init__(self, game="Hanabi-Full", players=2, config=None):
+    stateless (default True; an attribute that may be switched between calls): a partner that declares `obs_only_eval = True`
+    (DQNAgent: its eval_moves reads only the observation and legal mask it is handed) gets them from ONE hb_encode_rows call over
+    all K slabs instead of an import and an observe per slab; the scratch env is not touched and the results are the same bits.
+    Every other partner, and stateless=False, takes the scratch env."""
+
+    def __init__(self, game="Hanabi-Full", players=2, config=None, stateless=True):
         self.det = Determinizer(game, players, config)
         self.cfg, self.players, self.state_words = self.det.cfg, self.det.players, self.det.state_words
+        self.stateless = bool(stateless)   # may be switched at any time; False: every slab through the scratch env
         self._sized = {}   # (m, K) -> scratch env and buffers
         self._scratch = weakref.WeakKeyDictionary()   # agent -> the buffers its eval_moves writes
 
@@ -419,6 +426,29 @@ class ConditionedDeterminizer:
                 hyp_rows=torch.empty((Kn, m, SW), dtype=torch.int32, device=dev),
                 hyp_moves=torch.empty((Kn, m), dtype=torch.int32, device=dev))
         return b
+
+    def _slab_views(self, b, partner, m, Kn, dev):
+        """The stateless path: all Kn slabs of b["hyp_rows"] encoded by ONE hb_encode_rows call, for a
+        partner whose eval_moves reads nothing but the (observation, legal mask) pair it is handed (`obs_only_eval`). -> (obs
+        [Kn, m, obs_words], legal [Kn, m, A]), or None: this partner, or stateless=False, takes the scratch env. Every slab
+        starts on a 16-byte boundary, as the scratch env's buffers do: where m rows of either output are no multiple of 16
+        bytes (m not a multiple of 4, for the built games) the slabs are padded apart and encoded one call each."""
+        if not (self.stateless and getattr(partner, "obs_only_eval", False)):
+            return None
+        SW = self.state_words
+        if "slab_obs" not in b:
+            L = K.lib()
+            NW, A = L.hb_obs_words(C.byref(self.cfg)), L.hb_num_actions(C.byref(self.cfg))
+            mp = m if (m * NW * 4) % 16 == 0 and (m * A) % 16 == 0 else (m + 15) // 16 * 16
+            b["slab_obs"] = torch.empty((Kn, mp, NW), dtype=torch.int32, device=dev)
+            b["slab_legal"] = torch.empty((Kn, mp, A), dtype=torch.int8, device=dev)
+        obs, legal = b["slab_obs"], b["slab_legal"]
+        if obs.shape[1] == m:
+            encode_rows(self.cfg, b["hyp_rows"].view(Kn * m, SW), out=(obs.view(Kn * m, -1), legal.view(Kn * m, -1)))
+            return obs, legal
+        for k in range(Kn):
+            encode_rows(self.cfg, b["hyp_rows"][k], out=(obs[k, :m], legal[k, :m]))
+        return obs[:, :m], legal[:, :m]
 
     @torch.no_grad()
     def sample(self, rows, prev_rows, partner, seat, replicas, oversample, seed, draw, partner_seed, partner_draw, first_game_id,
@@ -453,7 +483,12 @@ class ConditionedDeterminizer:
             belief_splice(self.cfg, prev, b["cand_rows"], int(seat), Kn, out=b["hyp_rows"])
             env.first_game_id = int(first_game_id)   # (the scratch env never deals: its game ids key the partner's draws only)
             vec = partner.requires_vectorized_observation()
+            slabs = self._slab_views(b, partner, m, Kn, dev)
             for k in range(Kn):
+                if slabs is not None:
+                    partner.eval_moves((None, (slabs[0][k], slabs[1][k])), int(partner_seed), int(partner_draw), b["hyp_moves"][k],
+                                       scratch=self._scratch.setdefault(partner, {}))
+                    continue
                 env.import_state(b["hyp_rows"][k])
                 if vec:   # import_state moves the rows only: the acting seat's observation and legal mask are encoded here
                     env.observe()
@@ -505,7 +540,12 @@ class ConditionedDeterminizer:
             for d in range(min(D, history.filled)):
                 prev = torch.where((chain[d] != 0).view(m, 1), history.prev_rows[d], r).contiguous()
                 belief_splice_alive(self.cfg, prev, history.alive[d].contiguous(), b["cand_rows"], int(seat), Kn, out=b["hyp_rows"])
+                slabs = self._slab_views(b, partner, m, Kn, dev)
                 for k in range(Kn):
+                    if slabs is not None:
+                        partner.eval_moves((None, (slabs[0][k], slabs[1][k])), int(partner_seed), int(history.draws[d]), hyp[d, k],
+                                           scratch=self._scratch.setdefault(partner, {}))
+                        continue
                     env.import_state(b["hyp_rows"][k])
                     if vec:
                         env.observe()

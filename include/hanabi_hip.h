@@ -167,6 +167,25 @@ int hb_env_stats(hb_env* env, int64_t* episodes, int64_t* score_sum);
 int hb_env_export_state(hb_env* env, uint32_t* rows_dev, void* stream);
 int hb_env_import_state(hb_env* env, const uint32_t* rows_dev, void* stream);
 
+/* ---- stateless encoder (csrc/encode_rows.hip) --------------------------------------------------
+ * The canonical observation and legal-move mask of state rows that belong to no env: rows_dev [n_rows, hb_state_words()] u32
+ * in hb_env_export_state's layout (logged rows, determinized rows, the K slabs of a [K, m, SW] buffer as one call with
+ * n_rows = K * m), read only. No env, no deck pool, no counters; agent_reward / agent_step_type are not produced.
+ *   seat = -1: every row is encoded for its own seat to act. Bit for bit what hb_env_import_state + hb_env_observe_packed /
+ *     hb_env_observe write for that row on an env without colour shuffling, finished games and the zero pad bits of the last
+ *     packed word included.
+ *   seat = 0 .. players - 1: that seat is the observer of every row (the other hands, the missing-card flags, the last move's
+ *     actor and target offsets and the knowledge order are relative to it); legal is all zero in the rows where it is not the
+ *     seat to act and the ordinary mask where it is.
+ * obs_bits_dev [n_rows, hb_obs_words()] u32 and obs_dev [n_rows, hb_obs_len()] int8: either may be NULL, not both;
+ * legal_dev [n_rows, hb_num_actions()] int8 or NULL. The identity colour frame only.
+ * One lane per row, 16 or 32 rows per wavefront (the env step's rule: 32 for packed-only output of >= 32 768 rows).
+ * Checked before any device call: null cfg / rows_dev, a configuration without a compiled kernel, seat, both observation
+ * outputs NULL (HB_ERR_INVALID); outputs and rows_dev not 16-byte aligned (HB_ERR_ALIGN). n_rows == 0 is a no-op; without a
+ * device: HB_ERR_NO_DEVICE.                                                                                              */
+int hb_encode_rows(const hb_config* cfg, const uint32_t* rows_dev, int64_t n_rows, int32_t seat, uint32_t* obs_bits_dev,
+                   int8_t* obs_dev, int8_t* legal_dev, void* stream);
+
 /* ---- colour-permuted frames (Other-Play, Hu et al. 2020) ------------------------------------
  * Each game g and seat p has a permutation sigma_{g,p} of the colours, fixed for one deal: the seat sees true colour c as
  * sigma(c). The observation and legal mask the env writes are in the frame of the seat to act, and the move it submits is in

@@ -19,8 +19,21 @@ run learns.
             level 2 from fresh agents on that copy's belief, two runs, then self-play, cross-play between the runs and
             convention distance for both levels.
 
+  encode    (--encode-rows: this part alone, to profiles/obl/encode_rows_probe.json) the stateless encoder hb_encode_rows
+            (csrc/encode_rows.hip): event-timed us per call on 4 x 32 768 rows of 2-player Hanabi-Full in ONE call against the
+            loop of 4 x (import_state + observe) on a 32 768-game scratch env that it replaces, with bytes per second from the
+            shapes (128 B row + 84 B packed observation + 20 B legal mask); the level-2 step (`level2`'s protocol: 32 768 games,
+            oversample 4, depth 1 and 2, alternated windows, best of REPS) with ConditionedDeterminizer.stateless on and off; and
+            (--sessions-in-a-row: in a fresh process, merged into the same file) four level-2 sessions built in a row on either
+            path: a session's place in its process can move its step time by a factor of three, on the scratch-env path as well,
+            which is why the step is timed on ONE session with the switch toggled; and
+            the kernel's registers / LDS per configuration from the compiler's remarks (--resources-only: that part alone, no GPU;
+            --skip-resources: everything else). Parts already in the output file are kept.
+
 Usage: obl_probe.py [out.json] [--skip-learn] [--learn-steps N] [--level2] [--level2-steps N]
-       (default profiles/obl/obl_probe.json; with --level2 profiles/obl/obl_level2_probe.json)"""
+                    [--encode-rows [--resources-only | --skip-resources]] [--sessions-in-a-row]
+       (default profiles/obl/obl_probe.json; with --level2 profiles/obl/obl_level2_probe.json; with --encode-rows
+       profiles/obl/encode_rows_probe.json)"""
 import json
 import os
 import re
@@ -58,6 +71,231 @@ def kernel_resources(name="obl.hip", only=None):
     if only is not None:
         out = {k: v for k, v in out.items() if only in k}
     return out or {"error": p.stderr[-400:]}
+
+
+def encode_rows_probe(path, resources, measure):
+    """The `encode` part; see the module docstring."""
+    out = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            out = json.load(f)
+
+    def save():
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+
+    if resources:
+        table = {}
+        for src in ("env_full.hip", "env_small.hip", "env_vsmall.hip"):
+            res = kernel_resources(src)
+            for name, r in res.items():
+                m = re.search(r"(encode_rows_kernel|env_kernel)INS_3CfgILi(\d)ELi(\d)ELi(\d)ELi(\d)ELi(\d+)ELi(\d)EEELi(\d+)E", name)
+                if not m or not isinstance(r, dict):
+                    continue
+                key = "players=%s colors=%s ranks=%s hand=%s G=%s" % (m.group(2), m.group(3), m.group(4), m.group(5), m.group(8))
+                table.setdefault(key, {})[m.group(1)] = r
+        # the encoder does a subset of the env step's work: its scratch must not exceed the env kernel's for the same configuration
+        out["kernel"] = {k: dict(v["encode_rows_kernel"], env_kernel_scratch=v["env_kernel"]["scratch"])
+                         for k, v in sorted(table.items()) if "encode_rows_kernel" in v and "env_kernel" in v}
+        out["kernel_scratch_within_env_kernel"] = all(v["scratch"] <= v["env_kernel_scratch"] for v in out["kernel"].values())
+        print(json.dumps(out["kernel"]), flush=True)
+        save()
+    if not measure:
+        return
+
+    import torch
+
+    import hanabi_hip
+    from hanabi_agents.rlax_dqn import ActionSpec, DQNAgent, ObservationSpec, RlaxRainbowParams
+    from hanabi_hip import OffBeliefSession, encode_rows
+    from hanabi_hip.obl import frozen_copy
+
+    if not torch.cuda.is_available():
+        raise SystemExit("obl_probe.py measures on the GPU: none found")
+
+    # ---- the kernel alone against the loop it replaces ---------------------------------------------------------------------------
+    slabs = 4
+    env = hanabi_hip.HanabiEnv("Hanabi-Full", 2, n_games=N, seed=2, packed=True)
+    for t in range(9):
+        env.step(env.random_legal_actions(seed=3, draw=t))
+    cfg, SW = env.cfg, env.state_words
+    rows = env.export_state().repeat(slabs, 1).view(slabs, N, SW).contiguous()
+    scratch = hanabi_hip.HanabiEnv(config=cfg, n_games=N, packed=True)
+    obs = torch.empty((slabs * N, env.obs_words), dtype=torch.int32, device="cuda")
+    legal = torch.empty((slabs * N, env.num_actions), dtype=torch.int8, device="cuda")
+    flat = rows.view(slabs * N, SW)
+
+    def loop():
+        for k in range(slabs):
+            scratch.import_state(rows[k])
+            scratch.observe()
+
+    # the same call over SETS distinct sets of rows and outputs in turn (SETS x 30.4 MB, more than the 256 MiB last-level cache),
+    # the rows of every set from another depth of the game: nothing a call touches is left in cache from the call before
+    SETS = 10
+    cold = []
+    for k in range(SETS):
+        for t in range(3):
+            env.step(env.random_legal_actions(seed=3, draw=100 + 3 * k + t))
+        cold.append((env.export_state().repeat(slabs, 1).contiguous(), torch.empty_like(obs), torch.empty_like(legal)))
+    turn = [0]
+
+    def encode_cold():
+        r, o, l = cold[turn[0] % SETS]
+        turn[0] += 1
+        encode_rows(cfg, r, out=(o, l))
+
+    parts = dict(encode_rows=lambda: encode_rows(cfg, flat, out=(obs, legal)), import_observe_loop=loop,
+                 encode_rows_one_slab=lambda: encode_rows(cfg, rows[0], out=(obs[:N], legal[:N])), encode_rows_cold=encode_cold)
+    kern = {}
+    for name, fn in parts.items():
+        for _ in range(10):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(100):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        kern[name] = round(e0.elapsed_time(e1) * 10, 2)
+    # the same bits, while both are here
+    loop()
+    same = bool(torch.equal(obs[(slabs - 1) * N:], scratch.obs_bits)) and bool(torch.equal(legal[(slabs - 1) * N:], scratch.legal))
+    row_bytes = SW * 4 + env.obs_words * 4 + env.num_actions
+    kern.update(rows=slabs * N, bytes_per_row=row_bytes, bytes=slabs * N * row_bytes, equal_outputs=same)
+    kern["encode_rows_TBps"] = round(kern["bytes"] / kern["encode_rows"] / 1e6, 3)
+    kern["encode_rows_cold_TBps"] = round(kern["bytes"] / kern["encode_rows_cold"] / 1e6, 3)
+    kern["cold_sets"], kern["cold_bytes"] = SETS, SETS * kern["bytes"]
+    kern["note"] = ("event time over 100 calls from Python: host-bound (one slab takes no less than four), so an upper bound on the kernel's "
+                    "time; `encode_rows` re-reads and re-writes the same 30 MB, which stay in the 256 MiB last-level cache, `encode_rows_cold` "
+                    "cycles over distinct buffers larger than that cache")
+    kern["import_observe_loop_TBps"] = round(kern["bytes"] / kern["import_observe_loop"] / 1e6, 3)
+    kern["loop_over_kernel"] = round(kern["import_observe_loop"] / kern["encode_rows"], 2)
+    kern["not_slower_than_the_loop"] = kern["encode_rows"] <= kern["import_observe_loop"]
+    kern["history_step_TBps"] = 3.45     # hb_belief_history_step, profiles/obl/obl_level2_probe.json (host-bound: a floor)
+    kern["fraction_of_history_step_rate"] = round(kern["encode_rows_TBps"] / 3.45, 3)
+    out["kernel_us"] = kern
+    print(json.dumps(kern), flush=True)
+    save()
+    del env, scratch, rows, obs, legal, flat, cold
+    torch.cuda.empty_cache()
+
+    # ---- the level-2 step --------------------------------------------------------------------------------------------------------
+    def agents_for(env, seeds):
+        base = dict(train_batch_size=256, experience_buffer_size=1 << 19, layers=[512], mask_terminal=True, compute_dtype="bfloat16",
+                    packed_obs=True)
+        return [DQNAgent(ObservationSpec((env.n, env.obs_len)), ActionSpec(env.num_actions), RlaxRainbowParams(seed=s, **base),
+                         device="cuda") for s in seeds]
+
+    def window(sess, steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            sess.step()
+        sess.flush()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1000 / steps
+
+    # `level2`'s sessions, built in its order; the two level-2 sessions run every window twice, with the determinizer's stateless
+    # switch on and off: the same session, streams and buffers, and (the moves being the same bits) the same trajectory either way
+    from hanabi_hip.selfplay import SelfPlaySession
+
+    def level(depth):
+        return lambda e, a: OffBeliefSession(e, a, belief_policy=[frozen_copy(x) for x in a], depth=depth, oversample=4)
+
+    sessions = {}
+    for name, make in (("selfplay", lambda e, a: SelfPlaySession(e, a)), ("off_belief_level1", lambda e, a: OffBeliefSession(e, a)),
+                       ("depth1", level(1)), ("depth2", level(2))):
+        env = hanabi_hip.HanabiEnv("Hanabi-Full", 2, n_games=N, seed=1, packed=True)
+        sessions[name] = make(env, agents_for(env, (1, 2)))
+        window(sessions[name], WARM)
+    runs = [(name, None) for name in ("selfplay", "off_belief_level1")] + [(d, on) for d in ("depth1", "depth2") for on in (True, False)]
+    label = lambda name, on: name if on is None else name + ("_stateless" if on else "_scratch_env")
+    for name, on in runs[2:]:      # both paths warm (buffers, the partner's scratch)
+        sessions[name].cdet.stateless = on
+        window(sessions[name], 20)
+    ms = {label(*r): [] for r in runs}
+    for _ in range(REPS):
+        for name, on in runs:
+            if on is not None:
+                sessions[name].cdet.stateless = on
+            ms[label(name, on)].append(round(window(sessions[name], STEPS), 4))
+    best = {k: min(v) for k, v in ms.items()}
+    spread = {k: round(max(v) - min(v), 4) for k, v in ms.items()}
+    step = dict(games=N, steps_per_window=STEPS, oversample=4, ms_per_step_best=best, ms_per_step_runs=ms, window_spread_ms=spread,
+                estimate_saved_ms={"depth1": 0.14, "depth2": 0.29}, saved_ms={}, not_slower_within_spread={},
+                belief_forwards={k: sessions[k].belief_forwards for k in ("depth1", "depth2")})
+    for d in ("depth1", "depth2"):
+        on, off = d + "_stateless", d + "_scratch_env"
+        step["saved_ms"][d] = round(best[off] - best[on], 4)
+        step["not_slower_within_spread"][d] = best[on] - best[off] <= max(spread[on], spread[off])
+    out["step"] = step
+    print(json.dumps(step), flush=True)
+    save()
+
+
+def sessions_in_a_row(path):
+    """The `encode` part's look at a session's place in its process; see the module docstring. Merged into the output file."""
+    import torch
+
+    import hanabi_hip
+    from hanabi_agents.rlax_dqn import ActionSpec, DQNAgent, ObservationSpec, RlaxRainbowParams
+    from hanabi_hip import OffBeliefSession
+    from hanabi_hip.obl import frozen_copy
+
+    out = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            out = json.load(f)
+
+    def save():
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+
+    def agents_for(env, seeds):
+        base = dict(train_batch_size=256, experience_buffer_size=1 << 19, layers=[512], mask_terminal=True, compute_dtype="bfloat16",
+                    packed_obs=True)
+        return [DQNAgent(ObservationSpec((env.n, env.obs_len)), ActionSpec(env.num_actions), RlaxRainbowParams(seed=s, **base),
+                         device="cuda") for s in seeds]
+
+    def window(sess, steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            sess.step()
+        sess.flush()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1000 / steps
+
+    def level(depth):
+        return lambda e, a: OffBeliefSession(e, a, belief_policy=[frozen_copy(x) for x in a], depth=depth, oversample=4)
+
+    # ---- what the position of a session among the sessions of a process does to it -----------------------------------------------------
+    # In a process of its own (--sessions-in-a-row): the effect depends on what the process built before. Four level-2 sessions
+    # built one after the other (depth 1, 1, 2, 2), all on the scratch-env path, which is the code as it was
+    # before the encoder existed; then the same four with stateless on. Same configuration = same work: any difference between the
+    # two sessions of a depth is the session's place in the process, not its path.
+    row = {}
+    for on in (False, True):
+        four = []
+        for depth in (1, 1, 2, 2):
+            env = hanabi_hip.HanabiEnv("Hanabi-Full", 2, n_games=N, seed=1, packed=True)
+            sess = level(depth)(env, agents_for(env, (1, 2)))
+            sess.cdet.stateless = on
+            window(sess, WARM)
+            four.append(sess)
+        ms4 = [[] for _ in four]
+        for _ in range(2):
+            for i, sess in enumerate(four):
+                ms4[i].append(round(window(sess, 100), 4))
+        row["stateless" if on else "scratch_env"] = {"built_%d_depth%d" % (i, d): ms4[i] for i, d in enumerate((1, 1, 2, 2))}
+        del four, sess, env
+        torch.cuda.empty_cache()
+    out["sessions_in_a_row_ms_per_step"] = row
+    print(json.dumps(row), flush=True)
+    save()
 
 
 def level2(path, ladder_steps, skip_learn):
@@ -222,7 +460,16 @@ def main():
     ap.add_argument("--learn-steps", type=int, default=4000)
     ap.add_argument("--level2", action="store_true")
     ap.add_argument("--level2-steps", type=int, default=20000)
+    ap.add_argument("--encode-rows", action="store_true")
+    ap.add_argument("--resources-only", action="store_true")
+    ap.add_argument("--skip-resources", action="store_true")
+    ap.add_argument("--sessions-in-a-row", action="store_true")
     opt = ap.parse_args()
+    if opt.sessions_in_a_row:
+        return sessions_in_a_row(opt.out or os.path.join(ROOT, "profiles", "obl", "encode_rows_probe.json"))
+    if opt.encode_rows:
+        return encode_rows_probe(opt.out or os.path.join(ROOT, "profiles", "obl", "encode_rows_probe.json"),
+                                 resources=not opt.skip_resources, measure=not opt.resources_only)
     if opt.level2:
         return level2(opt.out or os.path.join(ROOT, "profiles", "obl", "obl_level2_probe.json"), opt.level2_steps, opt.skip_learn)
     opt.out = opt.out or os.path.join(ROOT, "profiles", "obl", "obl_probe.json")
