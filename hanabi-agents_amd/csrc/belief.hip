@@ -28,6 +28,10 @@
 // hb_belief_splice = splice-alive with alive NULL (the state the partner just moved from: every slot alive);
 // hb_belief_select = select-depth with depth 1: the same two kernels.
 //
+// hb_belief_select_soft: select-depth's inputs read as a likelihood instead of a filter: every candidate weighs its importance
+// weight times the product of P(real move | hypothetical move, legal moves) over the usable entries, quantised to integers, and the
+// replicas are drawn in proportion (Philox, integer prefix sums: one wavefront per root, see the kernel). No LDS, barrier or atomic.
+//
 // hb_belief_history_step: a PartnerHistory (the [depth, m] stack of states the partner moved from, with its moves, alive masks and
 // valid flags) advanced by one turn in place: own move out of the alive masks, reset of re-dealt games, push of a new entry. One
 // launch; rows move as contiguous 16-byte items, the byte fields one game per lane (see the kernel).
@@ -450,6 +454,185 @@ __global__ void __launch_bounds__(256) belief_select_depth_kernel(SelectDepthArg
   }
 }
 
+struct SelectSoftArgs {
+  const uint32_t* src;
+  const uint32_t* det;
+  const uint32_t* weight;
+  const int32_t* hyp;       // [depth][K * m]
+  const int32_t* n_legal;   // [depth][K * m]
+  const int32_t* actual;    // [depth][m]
+  const uint8_t* valid;     // [depth][m]; may be null: every entry valid
+  const double* p_table;    // [2][A + 1]
+  uint32_t* out;
+  uint32_t* out_weight;
+  int32_t* n_surv;          // [depth][m]
+  int32_t* depth_used;
+  uint8_t* fallback;
+  float* ess;
+  long long m, first_row;
+  unsigned long long seed, draw;
+  int K, R, SW, depth, A;
+};
+
+// 64-bit values across the wavefront, as two 32-bit halves
+__device__ __forceinline__ unsigned long long lane_read64(unsigned long long v, int l) {
+  return (static_cast<unsigned long long>(lane_read(static_cast<uint32_t>(v >> 32), l)) << 32) | lane_read(static_cast<uint32_t>(v), l);
+}
+
+// inclusive prefix sum over the wavefront (six shuffle-up steps)
+__device__ __forceinline__ unsigned long long wave_scan(unsigned long long v, int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const uint32_t lo = static_cast<uint32_t>(__shfl_up(static_cast<int>(static_cast<uint32_t>(v)), off));
+    const uint32_t hi = static_cast<uint32_t>(__shfl_up(static_cast<int>(static_cast<uint32_t>(v >> 32)), off));
+    if (lane >= off) v += (static_cast<unsigned long long>(hi) << 32) | lo;
+  }
+  return v;
+}
+
+// the largest of a non-negative double over the wavefront (exact: no rounding, so no order)
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(v));
+    const uint32_t lo = static_cast<uint32_t>(__shfl_xor(static_cast<int>(static_cast<uint32_t>(b)), off));
+    const uint32_t hi = static_cast<uint32_t>(__shfl_xor(static_cast<int>(static_cast<uint32_t>(b >> 32)), off));
+    const double o = __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+// The likelihood of this lane's candidate k of root i: the product over the entries d < L, in that order, of
+// p_table[hyp == actual ? 0 : 1][n_legal]; 0 for a candidate that is not live or has an n_legal outside 1 .. A. `lead` = its
+// leading matches. Multiplications only. The loop is unrolled to MAX_DEPTH with wave-uniform guards, as its callers' are.
+__device__ __forceinline__ double soft_likelihood(const SelectSoftArgs& a, long long i, long long slab, int k, bool live, int L,
+                                                  const int32_t (&act)[MAX_DEPTH], int& lead) {
+  double lik = live ? 1.0 : 0.0;
+  bool on = live;
+  lead = 0;
+#pragma unroll
+  for (int d = 0; d < MAX_DEPTH; ++d) {
+    if (d < L && live) {   // (d < L is wave-uniform)
+      const long long at = d * slab + static_cast<long long>(k) * a.m + i;
+      const bool match = a.hyp[at] == act[d];
+      const int n = a.n_legal[at];
+      const bool n_ok = n >= 1 && n <= a.A;
+      lik *= n_ok ? a.p_table[(match ? 0 : a.A + 1) + n] : 0.0;
+      on = on && match;
+      lead += on ? 1 : 0;
+    }
+  }
+  return lik;
+}
+
+// W_k = w_k * floor(lik_k / mx * 2^24) in 64-bit integers; 0 when mx == 0
+__device__ __forceinline__ unsigned long long soft_weight(uint32_t wk, double lik, double mx) {
+  if (!(mx > 0.0)) return 0ull;
+  return static_cast<unsigned long long>(wk) * static_cast<unsigned long long>(floor(lik / mx * 16777216.0));
+}
+
+// One wavefront per root, candidates 64 at a time, one per lane. L = the leading valid entries of the root (0 when it is not
+// running). Sweep 1: every candidate's likelihood; their largest (mx) and, by ballot, cnt[D - 1] = the candidates with at least D
+// leading matches. Sweep 2: W_k, their integer sum T and the f64 sum of their squares. Then the outputs, 64 at a time, output r
+// in lane r: its Philox target in [0, T), and sweep 3 over the candidates with an inclusive integer scan of W per chunk on a
+// running base: output r belongs to the chunk with base <= target < base + chunk sum, and its candidate is the first lane whose
+// prefix exceeds the target (ballot, find-first; such a lane has W > 0, hence k < K). Everything that decides a branch is
+// wave-uniform; the likelihoods are recomputed per sweep instead of kept (K may be 64 chunks), so nothing is indexed dynamically.
+__global__ void __launch_bounds__(256) belief_select_soft_kernel(SelectSoftArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long long i = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (i >= a.m) return;
+  const uint32_t* det = a.det + i * a.K * a.SW;
+  const uint32_t* w = a.weight + i * a.K;
+  uint32_t* out = a.out + i * a.R * a.SW;
+  uint32_t* ow = a.out_weight + i * a.R;
+  const long long slab = static_cast<long long>(a.K) * a.m;
+  const bool running = ((a.src[i * a.SW] >> 19) & 3u) == 0;
+  int L = 0;
+  if (running) {
+    while (L < a.depth && (!a.valid || a.valid[L * a.m + i] != 0)) ++L;
+  }
+  int32_t act[MAX_DEPTH];
+  int cnt[MAX_DEPTH];
+#pragma unroll
+  for (int d = 0; d < MAX_DEPTH; ++d) {
+    act[d] = d < L ? a.actual[d * a.m + i] : 0;
+    cnt[d] = 0;
+  }
+  double mx = 0.0;
+  for (int k0 = 0; k0 < a.K; k0 += 64) {
+    const int k = k0 + lane;
+    const bool live = k < a.K && w[k] != 0u;
+    int lead;
+    const double lik = soft_likelihood(a, i, slab, k, live, L, act, lead);
+    mx = lik > mx ? lik : mx;
+#pragma unroll
+    for (int d = 0; d < MAX_DEPTH; ++d) {
+      if (d < L) cnt[d] += __popcll(__ballot(live && lead > d));
+    }
+  }
+  mx = wave_max_f64(mx);
+  unsigned long long T = 0;
+  double sq = 0.0;
+  for (int k0 = 0; k0 < a.K; k0 += 64) {
+    const int k = k0 + lane;
+    const uint32_t wk = k < a.K ? w[k] : 0u;
+    int lead;
+    const double lik = soft_likelihood(a, i, slab, k, wk != 0u, L, act, lead);
+    const unsigned long long W = soft_weight(wk, lik, mx);
+    T += W;
+    sq += static_cast<double>(W) * static_cast<double>(W);
+  }
+  T = static_cast<unsigned long long>(wave_sum(static_cast<long long>(T)));
+  sq = wave_sum_f64(sq);
+#pragma unroll
+  for (int d = 0; d < MAX_DEPTH; ++d) {
+    if (d < a.depth && lane == 0) a.n_surv[d * a.m + i] = cnt[d];
+  }
+  if (lane == 0) {
+    a.depth_used[i] = L;
+    a.fallback[i] = L == 0 ? 2 : 0;
+    a.ess[i] = T == 0 ? 0.0f : static_cast<float>(static_cast<double>(T) * static_cast<double>(T) / sq);
+  }
+  if (T == 0) {   // nothing to draw from: dead copies of the root
+    const uint32_t sj = lane < a.SW ? a.src[i * a.SW + lane] : 0u;
+    for (int r = 0; r < a.R; ++r)
+      if (lane < a.SW) out[r * a.SW + lane] = sj;
+    for (int r = lane; r < a.R; r += 64) ow[r] = 0u;
+    return;
+  }
+  const unsigned long long row_id = static_cast<unsigned long long>(a.first_row + i);
+  for (int r0 = 0; r0 < a.R; r0 += 64) {
+    const int nr = min(64, a.R - r0);
+    uint32_t rnd[4];
+    hb::philox4x32_10(0x10000u + static_cast<uint32_t>(r0 + lane), static_cast<uint32_t>(a.draw), static_cast<uint32_t>(row_id),
+                      static_cast<uint32_t>(row_id >> 32), static_cast<uint32_t>(a.seed),
+                      static_cast<uint32_t>(a.seed >> 32) ^ static_cast<uint32_t>(a.draw >> 32), rnd);
+    const unsigned long long target = __umul64hi((static_cast<unsigned long long>(rnd[0]) << 32) | rnd[1], T);   // < T
+    if (lane < nr) ow[r0 + lane] = 1u;
+    unsigned long long base = 0;
+    for (int k0 = 0; k0 < a.K; k0 += 64) {
+      const int k = k0 + lane;
+      const uint32_t wk = k < a.K ? w[k] : 0u;
+      int lead;
+      const double lik = soft_likelihood(a, i, slab, k, wk != 0u, L, act, lead);
+      const unsigned long long incl = base + wave_scan(soft_weight(wk, lik, mx), lane);
+      const unsigned long long end = lane_read64(incl, 63);
+      if (end != base) {
+        for (int j = 0; j < nr; ++j) {
+          const unsigned long long t = lane_read64(target, j);
+          if (t >= base && t < end) {
+            const int kk = k0 + __ffsll(static_cast<unsigned long long>(__ballot(incl > t))) - 1;
+            if (lane < a.SW) out[(r0 + j) * a.SW + lane] = det[kk * a.SW + lane];
+          }
+        }
+      }
+      base = end;
+    }
+  }
+}
+
 struct HistoryArgs {
   const int32_t* own;     // [m] or null
   const uint8_t* reset;   // [m] or null
@@ -748,6 +931,41 @@ extern "C" int hb_belief_select_depth(const hb_config* cfg, const uint32_t* src_
     return hb::fail(HB_ERR_INVALID, "m * n_cand * state words must stay below 2^31: split the roots");
   return launch_select(cfg, src_rows_dev, det_rows_dev, weight_dev, hyp_moves_dev, actual_dev, valid_dev, m, n_cand, replicas, depth,
                        out_rows_dev, out_weight_dev, n_surv_dev, depth_used_dev, fallback_dev, stream);
+}
+
+extern "C" int hb_belief_select_soft(const hb_config* cfg, const uint32_t* src_rows_dev, const uint32_t* det_rows_dev,
+                                     const uint32_t* weight_dev, const int32_t* hyp_moves_dev, const int32_t* n_legal_dev,
+                                     const int32_t* actual_dev, const uint8_t* valid_dev, const double* p_table_dev, int64_t m,
+                                     int32_t n_cand, int32_t replicas, int32_t depth, uint64_t seed, uint64_t draw, int64_t first_row_id,
+                                     uint32_t* out_rows_dev, uint32_t* out_weight_dev, int32_t* n_surv_dev, int32_t* depth_used_dev,
+                                     uint8_t* fallback_dev, float* ess_dev, void* stream) {
+  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  if (m < 0) return hb::fail(HB_ERR_INVALID, "m must be >= 0");
+  if (replicas < 1) return hb::fail(HB_ERR_INVALID, "replicas must be >= 1, got %d", replicas);
+  if (n_cand < 1 || n_cand > 4096)
+    return hb::fail(HB_ERR_INVALID, "n_cand %d out of range 1..4096 (the 64-bit sum of the quantised weights)", n_cand);
+  if (depth < 1 || depth > MAX_DEPTH) return hb::fail(HB_ERR_INVALID, "depth %d out of range 1..%d", depth, MAX_DEPTH);
+  if (!src_rows_dev || !det_rows_dev || !weight_dev || !hyp_moves_dev || !n_legal_dev || !actual_dev || !p_table_dev || !out_rows_dev ||
+      !out_weight_dev || !n_surv_dev || !depth_used_dev || !fallback_dev || !ess_dev)
+    return hb::fail(HB_ERR_INVALID, "null argument");
+  const int SW = hb_state_words(cfg);
+  if (m > ((static_cast<int64_t>(1) << 31) - 1) / (static_cast<int64_t>(n_cand > replicas ? n_cand : replicas) * SW))
+    return hb::fail(HB_ERR_INVALID, "m * max(n_cand, replicas) * state words must stay below 2^31: split the roots");
+  if (m == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  SelectSoftArgs a{};
+  a.src = src_rows_dev; a.det = det_rows_dev; a.weight = weight_dev; a.hyp = hyp_moves_dev; a.n_legal = n_legal_dev;
+  a.actual = actual_dev; a.valid = valid_dev; a.p_table = p_table_dev;
+  a.out = out_rows_dev; a.out_weight = out_weight_dev; a.n_surv = n_surv_dev; a.depth_used = depth_used_dev; a.fallback = fallback_dev;
+  a.ess = ess_dev;
+  a.m = m; a.first_row = first_row_id;
+  a.seed = seed; a.draw = draw;
+  a.K = n_cand; a.R = replicas; a.SW = SW; a.depth = depth; a.A = hb_num_actions(cfg);
+  const unsigned blocks = static_cast<unsigned>((m + 3) / 4);   // four wavefronts = four roots per workgroup
+  hipLaunchKernelGGL(belief_select_soft_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
 }
 
 extern "C" int hb_belief_history_step(const hb_config* cfg, int64_t m, int32_t depth, int32_t seat, const int32_t* own_moves_dev,

@@ -44,11 +44,18 @@ to the V0 belief. Fallbacks are normal; they are counted (`conditioned_rows`, `f
 `depth_used_sum`, `belief_forwards`), never errors. With `belief_policy=None` (the default) nothing of this exists and the session
 is level 1, bit for bit.
 
+`belief_epsilon=eps` (default None: the exact-match filter above; needs a belief policy) reads the partner as epsilon-greedy on the
+frozen policy, which is what the real partner is while it explores: every candidate keeps a likelihood (1 - eps + eps / n per
+reproduced move, eps / n per missed one, n = the legal moves of the hypothetical state) and the fictitious state is drawn in
+proportion to importance weight times likelihood (`ConditionedDeterminizer`'s epsilon, hb_belief_select_soft). There is no depth
+fallback: `fallback_rows` stays 0, `conditioned_rows` counts the live rows with at least one usable partner move, `depth_used_sum`
+their usable moves, and `ess_sum` adds up the effective sample size of the conditioned rows' weighted candidates (a move nobody
+explains leaves the likelihoods equal: the V0 belief, by itself). No learning gain is claimed for it.
+
 The frozen policy's observations of the K candidate slabs come from one hb_encode_rows call (`self.cdet.stateless`, on by default;
 False: an import and an observe per slab on a scratch env, the same bits).
 
-Not built: three and more players at level 2+, the branch on hb_chain_run, one forward over all `oversample` slabs, and soft
-(epsilon-aware) likelihood weights instead of exact-match filtering.
+Not built: three and more players at level 2+, the branch on hb_chain_run, and one forward over all `oversample` slabs.
 """
 import weakref
 
@@ -56,7 +63,8 @@ import torch
 
 from . import _capi as K
 from .env import HanabiEnv
-from .search import MAX_DEPTH, ConditionedDeterminizer, Determinizer, PartnerHistory, _ask, running
+from .search import (MAX_DEPTH, MAX_SOFT_CANDIDATES, ConditionedDeterminizer, Determinizer, PartnerHistory, _ask, running,
+                     soft_table)
 from .selfplay import SelfPlaySession
 
 
@@ -71,14 +79,14 @@ class OffBeliefSession(SelfPlaySession):
     conditioned_rows (live rows whose fictitious state reproduces at least one partner move: fallback == 0), fallback_rows (usable
     moves, no surviving candidate: the V0 belief), unconditioned_rows (no usable move), survivors (sum over the conditioned rows
     of the candidates that pass the filter of the depth used), depth_used_sum, and belief_forwards (eval_moves calls made for the
-    belief, counted on the host)."""
+    belief, counted on the host). belief_epsilon (the soft filter, see the module docstring) adds ess_sum (a float)."""
 
     LEVEL_COUNTERS = ("conditioned_rows", "fallback_rows", "unconditioned_rows", "survivors", "depth_used_sum")
 
     _select_in_env = False   # a_t is needed before the env steps
 
     def __init__(self, env, agents, train_seats=None, belief_seed=1, updates_per_step=1, min_replay=None, belief_policy=None,
-                 depth=1, oversample=4):
+                 depth=1, oversample=4, belief_epsilon=None):
         import torch.distributed as dist
 
         from .partner_pool import PartnerPool
@@ -107,6 +115,13 @@ class OffBeliefSession(SelfPlaySession):
             if int(getattr(a, "actor_lag", 0)) != 0:
                 raise ValueError(f"seat {s}: actor_lag must be 0, got {a.actor_lag}")
         depth, oversample = int(depth), int(oversample)
+        if belief_epsilon is not None:
+            if belief_policy is None:
+                raise ValueError("belief_epsilon belongs to a belief policy: it is the exploration rate that policy's moves are read with")
+            belief_epsilon = float(belief_epsilon)
+            soft_table(belief_epsilon, 1)   # (the range check)
+            if oversample > MAX_SOFT_CANDIDATES:
+                raise ValueError(f"the soft filter takes at most {MAX_SOFT_CANDIDATES} candidates per row, got oversample = {oversample}")
         if belief_policy is None:
             if depth != 1 or oversample != 4:
                 raise ValueError("depth and oversample belong to a belief policy: without one the belief is the V0 belief (level 1)")
@@ -150,6 +165,7 @@ class OffBeliefSession(SelfPlaySession):
         self.branch_steps = 0
         # level k >= 2: the partner histories of the training env and what advancing them needs from the last two steps
         self.belief_policy, self.depth, self.oversample = belief_policy, depth, oversample
+        self.belief_epsilon = belief_epsilon
         self.belief_forwards = 0
         if belief_policy is not None:
             self.cdet = ConditionedDeterminizer(config=env.cfg)
@@ -161,11 +177,17 @@ class OffBeliefSession(SelfPlaySession):
             self._term_old = torch.zeros(n, dtype=torch.int8, device=dev)   # the terminal flags of the step before the last
             self._reset = torch.zeros(n, dtype=torch.int8, device=dev)
             self._level = torch.zeros(len(self.LEVEL_COUNTERS), dtype=torch.int64, device=dev)
+            self._ess = torch.zeros((), dtype=torch.float64, device=dev)
             self.last_belief = None         # (n_surv [depth, n], depth_used [n], fallback [n]) of the last branch
 
     @property
     def dead_rows(self):
         return int(self._dead.item())
+
+    @property
+    def ess_sum(self):
+        """belief_epsilon: the sum over the conditioned rows of their candidates' effective sample size (0.0 without)."""
+        return 0.0 if self.belief_policy is None else float(self._ess.item())
 
     def _clear_histories(self):
         for h in self.histories.values():
@@ -189,14 +211,18 @@ class OffBeliefSession(SelfPlaySession):
         if not first:
             h.advance(own_moves=self._own[seat] if self._own_t.get(seat) == t - 2 else None, reset=self._reset, cur_rows=rows,
                       prev_rows=self._prev_rows, seat=seat, draw=t - 1)
-        _, _, n_surv, used, fb = self.cdet.sample_history(
+        got = self.cdet.sample_history(
             rows, h, partner=self.belief_policy[1 - seat], seat=seat, replicas=1, oversample=self.oversample, seed=self.belief_seed,
             draw=t, partner_seed=self.belief_seed, first_game_id=env.first_game_id, first_row_id=env.first_game_id,
-            out=(self._det_rows, self._det_w))
+            out=(self._det_rows, self._det_w), epsilon=self.belief_epsilon)
+        n_surv, used, fb = got[2:5]
         self.belief_forwards += min(h.depth, h.filled) * self.oversample
         self.last_belief = (n_surv, used, fb)
         # fallback 0 and 1 are running rows by construction (hb_belief_select_depth: a finished row has no usable entry)
+        # (the soft filter: fallback is 0 with a usable move and 2 without, never 1)
         cond = fb == 0
+        if self.belief_epsilon is not None:
+            self._ess += (got[5].double() * cond).sum()
         surv = n_surv.gather(0, (used.long() - 1).clamp(min=0).view(1, -1)).view(-1)
         self._level += torch.stack([cond.sum(), (fb == 1).sum(), (running(rows) & (fb == 2)).sum(), (surv * cond).sum(), used.sum()])
 

@@ -29,6 +29,11 @@
   hb_belief_select_depth. `SearchPlayer(condition=True, depth=L)` keeps the stack itself. `PartnerHistory.advance` is one turn
   of that bookkeeping (own move, re-dealt games, push) in one kernel call (hb_belief_history_step): what a training env, whose
   games end and are dealt anew at different steps, keeps its histories with (hanabi_hip.obl, off-belief learning level 2+).
+* `epsilon=e` (to `ConditionedDeterminizer.sample` / `sample_history`, `RolloutSearch`, `SearchPlayer(condition=True)`; default
+  None: the exact-match filters above, unchanged) reads the partner as epsilon-greedy on its policy: every candidate keeps a
+  likelihood (`soft_table`: 1 - e + e / n per reproduced move, e / n per missed one, n = the legal moves of the hypothetical
+  state) and the replicas are drawn in proportion to importance weight times likelihood (hb_belief_select_soft;
+  `belief_select_soft_ref` is its numpy restatement). No depth fallback; the results carry the candidates' effective sample size.
 * `SearchPlayer` is an agent for `Evaluator.run`: the blueprint's move unless the search finds one that is better by more than
   `threshold` and, with `z` / `confirm_replicas`, by more than z standard errors of the paired difference.
 
@@ -217,6 +222,132 @@ def belief_select_depth(cfg, src_rows, det_rows, weights, hyp_moves, actual, val
 
 
 MAX_DEPTH = 8   # hb_belief_select_depth's
+MAX_SOFT_CANDIDATES = 4096   # hb_belief_select_soft's: the 64-bit sum of the quantised weights
+
+
+def soft_table(epsilon, n_actions, device=None):
+    """The likelihood of an epsilon-greedy partner's move: [2, A + 1] float64, indexed by the number n of legal moves;
+    table[0][n] = 1 - eps + eps / n (the move is the policy's: kept, or drawn by the uniform part), table[1][n] = eps / n (it is
+    not: the uniform part alone); column 0 is 0. epsilon in [1e-6, 1]: at 0 a single off-policy move would leave no candidate, which is
+    the exact-match filter (epsilon=None)."""
+    eps, A = float(epsilon), int(n_actions)
+    if not 1e-6 <= eps <= 1.0:
+        raise ValueError(f"epsilon must be in [1e-6, 1], got {epsilon}")
+    if A < 1:
+        raise ValueError(f"n_actions must be >= 1, got {n_actions}")
+    # (host floats: one correctly rounded division per entry)
+    t = torch.tensor([[0.0] + [1.0 - eps + eps / n for n in range(1, A + 1)], [0.0] + [eps / n for n in range(1, A + 1)]],
+                     dtype=torch.float64)
+    return t if device is None else t.to(device)
+
+
+def belief_select_soft(cfg, src_rows, det_rows, weights, hyp_moves, n_legal, actual, valid, p_table, replicas, seed, draw,
+                       first_row_id=0, out=None):
+    """hb_belief_select_soft: belief_select_depth's inputs, with n_legal [D, K, m] int32 (the legal moves of the hypothetical state
+    each hypothetical move was computed on) and p_table [2, A + 1] float64 (soft_table), read as a likelihood: `replicas`
+    candidates per root drawn with (seed, draw, row id first_row_id + i) in proportion to importance weight times likelihood ->
+    (rows [m * R, SW] int32, weights [m * R] int32 (1: drawn, 0: dead), n_surv [D, m] int32, depth_used [m] int32, fallback [m]
+    uint8, ess [m] float32). `out`: an optional tuple of these six buffers to write into."""
+    m, SW = src_rows.shape
+    if hyp_moves.dim() != 3:
+        raise ValueError(f"hyp_moves has shape [depth, K, m], got {tuple(hyp_moves.shape)}")
+    D, Kn, R, dev = hyp_moves.shape[0], hyp_moves.shape[1], int(replicas), src_rows.device
+    if not 1 <= D <= MAX_DEPTH:
+        raise ValueError(f"depth must be in 1..{MAX_DEPTH}, got {D}")
+    if not 1 <= Kn <= MAX_SOFT_CANDIDATES:
+        raise ValueError(f"the soft filter takes 1..{MAX_SOFT_CANDIDATES} candidates per root, got {Kn}")
+    A = K.lib().hb_num_actions(C.byref(cfg))
+    _bufs(dev, (src_rows, det_rows, weights, hyp_moves, n_legal, actual, p_table), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32),
+          ((m * Kn,), torch.int32), ((D, Kn, m), torch.int32), ((D, Kn, m), torch.int32), ((D, m), torch.int32),
+          ((2, A + 1), torch.float64))
+    if valid is not None:
+        _bufs(dev, (valid,), ((D, m), torch.uint8))
+    for t in (src_rows, det_rows, weights, hyp_moves, n_legal, actual, p_table) + (() if valid is None else (valid,)):
+        if not t.is_cuda or t.device != dev:
+            raise K.HbError("hb_belief_select_soft reads tensors of one GPU (there is no CPU path)")
+    n = m * max(R, 0)
+    rows, w, n_surv, depth_used, fallback, ess = _bufs(dev, out, ((n, SW), torch.int32), ((n,), torch.int32), ((D, m), torch.int32),
+                                                       ((m,), torch.int32), ((m,), torch.uint8), ((m,), torch.float32))
+    with torch.cuda.device(dev):
+        K.check(K.lib().hb_belief_select_soft(C.byref(cfg), K.dptr(src_rows), K.dptr(det_rows), K.dptr(weights), K.dptr(hyp_moves),
+                                              K.dptr(n_legal), K.dptr(actual), K.dptr(valid), K.dptr(p_table), m, Kn, R, D,
+                                              int(seed) & _M64, int(draw) & _M64, int(first_row_id), K.dptr(rows), K.dptr(w),
+                                              K.dptr(n_surv), K.dptr(depth_used), K.dptr(fallback), K.dptr(ess), K.current_stream()))
+    return rows, w, n_surv, depth_used, fallback, ess
+
+
+_M32, _M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+
+
+def _philox_np(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on numpy arrays (broadcast) -> the four output words as uint64 arrays below 2^32."""
+    import numpy as np
+
+    c0, c1, c2, c3 = (np.asarray(x, np.uint64) & np.uint64(_M32) for x in np.broadcast_arrays(c0, c1, c2, c3))
+    k0, k1 = int(k0) & _M32, int(k1) & _M32
+    lo, sh = np.uint64(_M32), np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ np.uint64(k0), p1 & lo, (p0 >> sh) ^ c3 ^ np.uint64(k1), p0 & lo
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0, c1, c2, c3
+
+
+def belief_select_soft_ref(src_rows, det_rows, weights, hyp_moves, n_legal, actual, valid, p_table, replicas, seed, draw,
+                           first_row_id=0, details=False):
+    """hb_belief_select_soft restated in numpy, the same arithmetic in the same order (include/hanabi_hip.h): arrays shaped as
+    belief_select_soft's tensors (32-bit words of either sign) -> (rows uint32 [m * R, SW], weights uint32 [m * R], n_surv int32
+    [D, m], depth_used int32 [m], fallback uint8 [m], ess float32 [m]). details=True appends a dict of the intermediate figures:
+    lik float64 [m, K], q and W uint64 [m, K], T uint64 [m], target uint64 [m, R] and pick int64 [m, R] (-1: dead)."""
+    import numpy as np
+
+    u32 = lambda x: (np.asarray(x).astype(np.int64) & _M32).astype(np.uint32)
+    src, det = u32(src_rows), u32(det_rows)
+    (m, SW), R = src.shape, int(replicas)
+    hyp, nl, act = np.asarray(hyp_moves).astype(np.int64), np.asarray(n_legal).astype(np.int64), np.asarray(actual).astype(np.int64)
+    D, Kn = hyp.shape[0], hyp.shape[1]
+    assert hyp.shape == nl.shape == (D, Kn, m) and act.shape == (D, m) and det.shape == (m * Kn, SW)
+    w = u32(weights).reshape(m, Kn).astype(np.uint64)
+    table = np.asarray(p_table, np.float64)
+    A = table.shape[1] - 1
+    run = ((src[:, 0] >> np.uint32(19)) & np.uint32(3)) == 0
+    usable = np.ones((D, m), bool) if valid is None else np.asarray(valid).reshape(D, m) != 0
+    chain = np.cumprod(usable & run[None], axis=0).astype(bool)   # [D, m]: entry d is one of the root's L leading valid ones
+    L = chain.sum(0).astype(np.int32)
+    live = w != 0
+    lik, on = np.where(live, 1.0, 0.0), live.copy()
+    n_surv = np.zeros((D, m), np.int32)
+    for d in range(D):
+        match, n = hyp[d].T == act[d][:, None], nl[d].T   # [m, K]
+        factor = np.where((n >= 1) & (n <= A), table[np.where(match, 0, 1), np.clip(n, 0, A)], 0.0)
+        lik = np.where(chain[d][:, None] & live, lik * factor, lik)
+        on = on & match & chain[d][:, None]
+        n_surv[d] = on.sum(1)
+    mx = lik.max(1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(mx[:, None] > 0, np.floor(lik / mx[:, None] * 16777216.0), 0.0).astype(np.uint64)
+    W = w * q
+    T = W.sum(1, dtype=np.uint64)
+    Wf = W.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ess = np.where(T > 0, T.astype(np.float64) * T.astype(np.float64) / (Wf * Wf).sum(1), 0.0).astype(np.float32)
+    rid = [(int(first_row_id) + i) & _M64 for i in range(m)]
+    x = _philox_np(0x10000 + np.arange(R, dtype=np.uint64)[None], int(draw) & _M32, np.array([v & _M32 for v in rid], np.uint64)[:, None],
+                   np.array([v >> 32 for v in rid], np.uint64)[:, None], int(seed) & _M32, ((int(seed) >> 32) ^ (int(draw) >> 32)) & _M32)
+    u = (x[0] << np.uint64(32)) | x[1]   # [m, R]
+    target, pick = np.zeros((m, R), np.uint64), np.full((m, R), -1, np.int64)
+    rows, ow = np.empty((m * R, SW), np.uint32), np.zeros(m * R, np.uint32)
+    prefix = np.cumsum(W, axis=1, dtype=np.uint64)
+    for i in range(m):
+        if T[i] == 0:
+            rows[i * R:(i + 1) * R] = src[i]
+            continue
+        target[i] = np.array([(int(v) * int(T[i])) >> 64 for v in u[i]], np.uint64)
+        pick[i] = np.searchsorted(prefix[i], target[i], side="right")   # the first k whose inclusive prefix exceeds the target
+        rows[i * R:(i + 1) * R] = det[i * Kn + pick[i]]
+        ow[i * R:(i + 1) * R] = 1
+    out = (rows, ow, n_surv, L, np.where(L == 0, 2, 0).astype(np.uint8), ess)
+    return out + (dict(lik=lik, q=q, W=W, T=T, target=target, pick=pick),) if details else out
 
 
 def running(rows):
@@ -405,7 +536,13 @@ class ConditionedDeterminizer:
     stateless (default True; an attribute that may be switched between calls): a partner that declares `obs_only_eval = True`
     (DQNAgent: its eval_moves reads only the observation and legal mask it is handed) gets them from ONE hb_encode_rows call over
     all K slabs instead of an import and an observe per slab; the scratch env is not touched and the results are the same bits.
-    Every other partner, and stateless=False, takes the scratch env."""
+    Every other partner, and stateless=False, takes the scratch env.
+
+    epsilon (to sample / sample_history; default None: the exact-match filter above, unchanged): the partner is read as
+    epsilon-greedy on `partner`'s policy. Every candidate keeps a likelihood (soft_table: 1 - eps + eps / n per reproduced move,
+    eps / n per missed one, n = the legal moves of the hypothetical state, recorded per slab from the legal mask the partner is
+    shown) and the replicas are drawn in proportion to importance weight times likelihood (hb_belief_select_soft): no depth
+    fallback, every replica weighs 1, and the result carries the candidates' effective sample size `ess` at the end."""
 
     def __init__(self, game="Hanabi-Full", players=2, config=None, stateless=True):
         self.det = Determinizer(game, players, config)
@@ -413,6 +550,19 @@ class ConditionedDeterminizer:
         self.stateless = bool(stateless)   # may be switched at any time; False: every slab through the scratch env
         self._sized = {}   # (m, K) -> scratch env and buffers
         self._scratch = weakref.WeakKeyDictionary()   # agent -> the buffers its eval_moves writes
+        self._tables = {}   # (epsilon, device) -> soft_table on the device
+
+    def _soft(self, b, epsilon, D, Kn, m, dev):
+        """What the soft filter needs beside the hard one's buffers -> (p_table on the device, n_legal [D, Kn, m] int32)."""
+        if Kn > MAX_SOFT_CANDIDATES:
+            raise ValueError(f"the soft filter takes at most {MAX_SOFT_CANDIDATES} candidates per root, got replicas * oversample = {Kn}")
+        key = (float(epsilon), dev)
+        if key not in self._tables:
+            self._tables[key] = soft_table(epsilon, K.lib().hb_num_actions(C.byref(self.cfg)), device=dev)
+        nleg = b.get("n_legal")
+        if nleg is None or nleg.shape[0] != D:
+            nleg = b["n_legal"] = torch.ones((D, Kn, m), dtype=torch.int32, device=dev)
+        return self._tables[key], nleg
 
     def _setup(self, m, Kn, dev):
         b = self._sized.get((m, Kn))
@@ -452,7 +602,7 @@ class ConditionedDeterminizer:
 
     @torch.no_grad()
     def sample(self, rows, prev_rows, partner, seat, replicas, oversample, seed, draw, partner_seed, partner_draw, first_game_id,
-               valid=None, first_row_id=0, out=None):
+               valid=None, first_row_id=0, out=None, epsilon=None):
         """rows [m, SW] the current states (seat `seat` to act), prev_rows [m, SW] the states the partner moved from, partner:
         the agent that moved (its eval_moves is called with partner_seed / partner_draw on games first_game_id + i: what it was
         called with in the real game), valid [m] (0: no usable previous state; the root keeps the unconditioned belief). K =
@@ -460,7 +610,9 @@ class ConditionedDeterminizer:
         that is not the state the partner moved from (another deal, a hand of another size for `seat`) gives some legal
         hypothetical state, not a specified one.
         -> (rows_out [m * replicas, SW] int32, weights [m * replicas] int64, n_surv [m] int32, fallback [m] uint8). `out`: an
-        optional (rows_out, weights_u32) pair to write into (the weights then come back as the int32 buffer)."""
+        optional (rows_out, weights_u32) pair to write into (the weights then come back as the int32 buffer). epsilon: see the
+        class docstring; the tuple then ends with ess [m] float32, and the replicas are drawn with (seed, draw) and row ids
+        first_row_id + i."""
         r = _rows(rows, self.state_words)
         m, R, ov = r.shape[0], int(replicas), int(oversample)
         if R < 1 or ov < 1:
@@ -473,6 +625,7 @@ class ConditionedDeterminizer:
         prev, _, _, _, valid = _history((prev_rows, 0, 0, 0, valid), m, self.state_words, dev)
         b = self._setup(m, Kn, dev)
         env = b["env"]
+        table, nleg = (None, None) if epsilon is None else self._soft(b, epsilon, 1, Kn, m, dev)
         with torch.cuda.device(dev):
             usable = running(r) if valid is None else running(r) & (valid != 0)
             # a root without a usable previous state is never filtered: its slab rows only have to be states the partner's
@@ -484,15 +637,26 @@ class ConditionedDeterminizer:
             env.first_game_id = int(first_game_id)   # (the scratch env never deals: its game ids key the partner's draws only)
             vec = partner.requires_vectorized_observation()
             slabs = self._slab_views(b, partner, m, Kn, dev)
+            if slabs is not None and nleg is not None:
+                torch.sum(slabs[1], dim=-1, dtype=torch.int32, out=nleg[0])
             for k in range(Kn):
                 if slabs is not None:
                     partner.eval_moves((None, (slabs[0][k], slabs[1][k])), int(partner_seed), int(partner_draw), b["hyp_moves"][k],
                                        scratch=self._scratch.setdefault(partner, {}))
                     continue
                 env.import_state(b["hyp_rows"][k])
-                if vec:   # import_state moves the rows only: the acting seat's observation and legal mask are encoded here
+                if vec or nleg is not None:   # import_state moves the rows only: the seat's observation and legal mask are encoded here
                     env.observe()
+                if nleg is not None:
+                    torch.sum(env.legal, dim=1, dtype=torch.int32, out=nleg[0, k])
                 _ask(partner, env, int(partner_seed), int(partner_draw), b["hyp_moves"][k], self._scratch)
+            if epsilon is not None:
+                res = belief_select_soft(self.cfg, r, b["cand_rows"], b["cand_w"], b["hyp_moves"].view(1, Kn, m), nleg,
+                                         last_move_uid(self.cfg, r).view(1, m), usable.to(torch.uint8).view(1, m), table, R, seed, draw,
+                                         first_row_id=first_row_id,
+                                         out=None if out is None else tuple(out) + _bufs(dev, None, ((1, m), torch.int32), ((m,), torch.int32),
+                                                                                         ((m,), torch.uint8), ((m,), torch.float32)))
+                return (res[0], res[1] if out is not None else res[1].long() & 0xFFFFFFFF, res[2][0], res[4], res[5])
             res = belief_select(self.cfg, r, b["cand_rows"], b["cand_w"], b["hyp_moves"], last_move_uid(self.cfg, r),
                                 usable.to(torch.uint8), R,
                                 out=None if out is None else tuple(out) + _bufs(dev, None, ((m,), torch.int32), ((m,), torch.uint8)))
@@ -502,13 +666,14 @@ class ConditionedDeterminizer:
 
     @torch.no_grad()
     def sample_history(self, rows, history, partner, seat, replicas, oversample, seed, draw, partner_seed, first_game_id,
-                       first_row_id=0, out=None):
+                       first_row_id=0, out=None, epsilon=None):
         """sample() over the partner's last history.depth moves (a PartnerHistory of these m roots, observer `seat`): the
         candidates are drawn ONCE, as in sample(); for each entry d they are carried back to its previous state with its alive
         mask (hb_belief_splice_alive) and the partner's eval_moves runs on the K slabs with (partner_seed, history.draws[d]);
         one hb_belief_select_depth keeps, per root, the first `replicas` candidates that reproduce the most leading moves.
         Entries that were never pushed cost no slab pass. -> (rows_out [m * replicas, SW] int32, weights [m * replicas] int64,
-        n_surv [depth, m] int32, depth_used [m] int32, fallback [m] uint8); `out` as in sample()."""
+        n_surv [depth, m] int32, depth_used [m] int32, fallback [m] uint8); `out` and `epsilon` as in sample() (with an epsilon
+        depth_used is the number of usable moves, fallback 0 or 2, and the tuple ends with ess [m] float32)."""
         r = _rows(rows, self.state_words)
         m, R, ov = r.shape[0], int(replicas), int(oversample)
         if R < 1 or ov < 1:
@@ -529,6 +694,7 @@ class ConditionedDeterminizer:
         hyp = b.get("hyp_depth")
         if hyp is None or hyp.shape[0] != D:
             hyp = b["hyp_depth"] = torch.zeros((D, Kn, m), dtype=torch.int32, device=dev)
+        table, nleg = (None, None) if epsilon is None else self._soft(b, epsilon, D, Kn, m, dev)
         with torch.cuda.device(dev):
             # the chain of usable entries, root by root: an entry behind an invalid one is never read, so its slab rows only
             # have to be states the partner's policy can be run on, and the current row is one (as in sample())
@@ -541,15 +707,25 @@ class ConditionedDeterminizer:
                 prev = torch.where((chain[d] != 0).view(m, 1), history.prev_rows[d], r).contiguous()
                 belief_splice_alive(self.cfg, prev, history.alive[d].contiguous(), b["cand_rows"], int(seat), Kn, out=b["hyp_rows"])
                 slabs = self._slab_views(b, partner, m, Kn, dev)
+                if slabs is not None and nleg is not None:
+                    torch.sum(slabs[1], dim=-1, dtype=torch.int32, out=nleg[d])
                 for k in range(Kn):
                     if slabs is not None:
                         partner.eval_moves((None, (slabs[0][k], slabs[1][k])), int(partner_seed), int(history.draws[d]), hyp[d, k],
                                            scratch=self._scratch.setdefault(partner, {}))
                         continue
                     env.import_state(b["hyp_rows"][k])
-                    if vec:
+                    if vec or nleg is not None:
                         env.observe()
+                    if nleg is not None:
+                        torch.sum(env.legal, dim=1, dtype=torch.int32, out=nleg[d, k])
                     _ask(partner, env, int(partner_seed), int(history.draws[d]), hyp[d, k], self._scratch)
+            if epsilon is not None:
+                res = belief_select_soft(self.cfg, r, b["cand_rows"], b["cand_w"], hyp, nleg, history.moves.contiguous(), chain, table, R,
+                                         seed, draw, first_row_id=first_row_id,
+                                         out=None if out is None else tuple(out) + _bufs(dev, None, ((D, m), torch.int32), ((m,), torch.int32),
+                                                                                         ((m,), torch.uint8), ((m,), torch.float32)))
+                return (res[0], res[1] if out is not None else res[1].long() & 0xFFFFFFFF) + tuple(res[2:])
             res = belief_select_depth(self.cfg, r, b["cand_rows"], b["cand_w"], hyp, history.moves.contiguous(), chain, R,
                                       out=None if out is None else tuple(out) + _bufs(dev, None, ((D, m), torch.int32), ((m,), torch.int32),
                                                                                       ((m,), torch.uint8)))
@@ -568,14 +744,15 @@ class SearchResult:
     `n_pair` [m] int32 the live replicas (hb_search_compare). None when not computed. With `history` (the belief conditioned on
     the partner's last move): `n_surv` [m] int32 and `fallback` [m] uint8 of hb_belief_select; None without. With a
     `PartnerHistory` (its last `depth` moves): `n_surv` [depth, m], `fallback` and `depth_used` [m] int32 of
-    hb_belief_select_depth; `depth_used` is None when not computed."""
+    hb_belief_select_depth; `depth_used` is None when not computed. With the search's `epsilon` (the soft filter,
+    hb_belief_select_soft): `ess` [m] float32, the effective sample size of each root's weighted candidates; None without."""
 
     def __init__(self, value, wsum, n_live, best, rollouts, turns, dead=0, replicas=0, diff=None, se=None, n_pair=None, cand=None,
-                 best_uid=None, n_surv=None, fallback=None, depth_used=None):
+                 best_uid=None, n_surv=None, fallback=None, depth_used=None, ess=None):
         self.value, self.wsum, self.n_live, self.best = value, wsum, n_live, best
         self.rollouts, self.turns, self.dead, self.replicas = int(rollouts), int(turns), int(dead), int(replicas)
         self.diff, self.se, self.n_pair, self.cand, self.best_uid = diff, se, n_pair, cand, best_uid
-        self.n_surv, self.fallback, self.depth_used = n_surv, fallback, depth_used
+        self.n_surv, self.fallback, self.depth_used, self.ess = n_surv, fallback, depth_used, ess
 
     def __repr__(self):
         return f"SearchResult(roots={self.value.shape[0]}, rollouts={self.rollouts}, turns={self.turns})"
@@ -623,10 +800,11 @@ class RolloutSearch:
     roots' current player with those Philox keys) with `oversample` candidates per replica; everything after the
     determinization is the same. history may also be a `PartnerHistory` of the roots (the partner's last `depth` moves, with its
     partner_seed and first_game_id): the replicas then come from `ConditionedDeterminizer.sample_history` and the result carries
-    `depth_used`."""
+    `depth_used`. epsilon (default None: the exact-match filter): with a history, the candidates are weighed by the likelihood of
+    an epsilon-greedy partner instead of filtered (`ConditionedDeterminizer`'s epsilon) and the result carries `ess`."""
 
     def __init__(self, game="Hanabi-Full", players=2, replicas=32, seed=1, device=None, config=None, check_every=8, first_game_id=0,
-                 oversample=8):
+                 oversample=8, epsilon=None):
         self.cfg = eval_config(game, players, config)
         self.players = self.cfg.players
         self.replicas = int(replicas)
@@ -642,6 +820,12 @@ class RolloutSearch:
             raise ValueError(f"oversample must be >= 1, got {oversample}")
         self.cdet = None   # ConditionedDeterminizer, built by the first search with a history
         self.num_actions = K.lib().hb_num_actions(C.byref(self.cfg))
+        self.epsilon = None if epsilon is None else float(epsilon)
+        if self.epsilon is not None:
+            soft_table(self.epsilon, self.num_actions)   # (the range check)
+            if self.replicas * self.oversample > MAX_SOFT_CANDIDATES:
+                raise ValueError(f"the soft filter takes at most {MAX_SOFT_CANDIDATES} candidates per root, got replicas * oversample = "
+                                 f"{self.replicas * self.oversample}")
         self.n_counters = K.lib().hb_eval_counters(C.byref(self.cfg))
         self._sized = {}   # (m, C, replicas) -> the rollout env and buffers of that size, with the scratch of its blueprint
         self._uid = None   # [1, A] int32: every uid, on the device (built by the first run())
@@ -708,7 +892,7 @@ class RolloutSearch:
         if not cps:
             return self._nothing(m, Cn, dev, compared=base_slot is not None)
         cp, env = int(cps[0]), b["env"]
-        n_surv = fallback = depth_used = None
+        n_surv = fallback = depth_used = ess = None
         with torch.cuda.device(dev):
             if history is None:
                 self.det.sample(r, seat=cp, replicas=R, seed=self.seed, draw=draw, first_row_id=first_row_id,
@@ -716,16 +900,20 @@ class RolloutSearch:
             elif isinstance(history, PartnerHistory):
                 if self.cdet is None:
                     self.cdet = ConditionedDeterminizer(config=self.cfg)
-                _, _, n_surv, depth_used, fallback = self.cdet.sample_history(
+                got = self.cdet.sample_history(
                     r, history, blueprint[(cp - 1) % self.players], cp, R, self.oversample, self.seed, draw, history.partner_seed,
-                    history.first_game_id, first_row_id=first_row_id, out=(b["det_rows"], b["weights"]))
+                    history.first_game_id, first_row_id=first_row_id, out=(b["det_rows"], b["weights"]), epsilon=self.epsilon)
+                n_surv, depth_used, fallback = got[2:5]
+                ess = got[5] if self.epsilon is not None else None
             else:
                 prev, p_seed, p_draw, gid, valid = history
                 if self.cdet is None:
                     self.cdet = ConditionedDeterminizer(config=self.cfg)
-                _, _, n_surv, fallback = self.cdet.sample(r, prev, blueprint[(cp - 1) % self.players], cp, R, self.oversample,
-                                                          self.seed, draw, p_seed, p_draw, gid, valid=valid,
-                                                          first_row_id=first_row_id, out=(b["det_rows"], b["weights"]))
+                got = self.cdet.sample(r, prev, blueprint[(cp - 1) % self.players], cp, R, self.oversample, self.seed, draw, p_seed,
+                                       p_draw, gid, valid=valid, first_row_id=first_row_id, out=(b["det_rows"], b["weights"]),
+                                       epsilon=self.epsilon)
+                n_surv, fallback = got[2:4]
+                ess = got[4] if self.epsilon is not None else None
             # [m, C, R]: block c of root i holds the same R replicas. A slot without a candidate (an illegal action, in run()) is
             # never counted (done up front); its games move in step with the others on the root's filler move, so that no illegal
             # move reaches the env
@@ -748,7 +936,7 @@ class RolloutSearch:
             value, wsum, n_live, best = search_reduce(scores, weights, slots)
             rollouts, dead, roots = counts.tolist()
             res = SearchResult(value, wsum, n_live, best, rollouts, turns, dead=dead, replicas=roots * R, n_surv=n_surv,
-                               fallback=fallback, depth_used=depth_used)
+                               fallback=fallback, depth_used=depth_used, ess=ess)
             if base_slot is not None:
                 res.diff, res.se, res.n_pair = search_compare(scores, weights, cand, base_slot)
         return res
@@ -884,6 +1072,11 @@ class SearchPlayer:
     first. A root whose deepest filter leaves no survivor takes the deepest that does: `last_result.depth_used` says which, and
     that is a fallback, not the exact posterior given L moves. depth_stats() gives the sums per depth.
 
+    epsilon (default None: the exact-match filter above, unchanged; needs condition=True): the partner is read as epsilon-greedy
+    on blueprint[partner] (RolloutSearch's epsilon, hb_belief_select_soft): the candidates of a conditioned root are weighed, not
+    filtered, every usable move counts (`depth_used` = their number, `fallbacks` stays 0, `survivors` counts the candidates that
+    reproduce all of them) and depth_stats() gains `ess`, the mean effective sample size of the conditioned roots' candidates.
+
     Counters: `moves` (moves made in live games), `deviations` (those that left the blueprint), `dead_replicas` /
     `replicas_drawn` (of the first stage), `confirmed` (challengers that went to the second stage), `rejected` (of those, the
     ones not played), `rollouts` (games played, both stages); with condition=True, of the first stage: `conditioned` (live roots
@@ -896,7 +1089,7 @@ class SearchPlayer:
                 "depth_used")
 
     def __init__(self, blueprint, seat, replicas=32, threshold=0.0, seed=1, check_every=8, z=None, confirm_replicas=0,
-                 condition=False, oversample=8, depth=1):
+                 condition=False, oversample=8, depth=1, epsilon=None):
         self.blueprint = list(blueprint)
         self.seat = int(seat)
         if not 0 <= self.seat < len(self.blueprint):
@@ -922,6 +1115,14 @@ class SearchPlayer:
             raise ValueError(f"depth must be in 1..{MAX_DEPTH}, got {depth}")
         if self.depth > 1 and not self.condition:
             raise ValueError(f"depth={depth} needs condition=True")
+        self.epsilon = None if epsilon is None else float(epsilon)
+        if self.epsilon is not None:
+            if not self.condition:
+                raise ValueError(f"epsilon={epsilon} needs condition=True")
+            soft_table(self.epsilon, 1)   # (the range check)
+            if self.replicas * self.oversample > MAX_SOFT_CANDIDATES:
+                raise ValueError(f"the soft filter takes at most {MAX_SOFT_CANDIDATES} candidates per root, got replicas * oversample = "
+                                 f"{self.replicas * self.oversample}")
         self._history = None   # depth > 1: the PartnerHistory of the env of the last call
         self._search = None
         self.last_result = None   # the SearchResult of the last call's first stage
@@ -936,6 +1137,7 @@ class SearchPlayer:
         self._stats = None   # [len(COUNTERS)] int64 on the device, built by the first eval_moves: read through the properties
         self.dead_replicas = self.replicas_drawn = self.searches = self.rollouts = 0
         self._by_depth = None   # depth > 1: [4, depth] int64 on the device, see depth_stats()
+        self._ess = None        # epsilon: [2] float64 on the device, sum of ess and count over the conditioned roots
 
     def depth_stats(self):
         """depth > 1: sums over the first stage's conditioned roots since reset_stats(), one figure per D = 1 .. depth:
@@ -943,7 +1145,11 @@ class SearchPlayer:
         the last D moves), `used` (roots whose replicas reproduce exactly D moves) and `shallow` (roots with exactly D usable
         moves that use fewer: the deepest filter left no survivor; roots without any survivor among them)."""
         t = torch.zeros((4, self.depth), dtype=torch.int64) if self._by_depth is None else self._by_depth.cpu()
-        return dict(zip(("reached", "survivors", "used", "shallow"), t.tolist()))
+        out = dict(zip(("reached", "survivors", "used", "shallow"), t.tolist()))
+        if self.epsilon is not None:   # the mean effective sample size of the conditioned roots' candidates (0.0: none yet)
+            total, count = (0.0, 0.0) if self._ess is None else self._ess.tolist()
+            out["ess"] = total / count if count else 0.0
+        return out
 
     def _previous(self, env, rows, draw):
         """history for this call: the remembered rows stepped with the remembered moves, and which roots that is usable for."""
@@ -1000,7 +1206,7 @@ class SearchPlayer:
             raise ValueError(f"condition=True is built for 2 players, the env has {env.cfg.players}")
         if self._search is None or self._search.cfg.players != env.cfg.players:
             self._search = RolloutSearch(config=env.cfg, replicas=self.replicas, seed=self.seed, device=env.device,
-                                         check_every=self.check_every, oversample=self.oversample)
+                                         check_every=self.check_every, oversample=self.oversample, epsilon=self.epsilon)
         rows = env.export_state()
         staged = self.z is not None or self.confirm_replicas > 0
         history = None
@@ -1038,6 +1244,9 @@ class SearchPlayer:
             self._memory = (weakref.ref(env), int(draw), rows, actions_out.clone())
             if res.fallback is not None:   # (None: no root was running)
                 filtered = live & (res.fallback != 2)
+                if res.ess is not None:
+                    ess = torch.stack([(res.ess.double() * filtered).sum(), filtered.sum().double()])
+                    self._ess = ess if self._ess is None else self._ess + ess
                 if self.depth == 1:
                     n_surv, used = res.n_surv, (res.fallback == 0).long()
                 else:   # the candidates that pass the filter of the depth used, root by root

@@ -947,7 +947,28 @@ int hb_train_tally(const hb_config* cfg, int64_t n_games, int32_t seat, const in
  * 1 <= depth <= 8, 0 <= seat < players, m * depth * SW < 2^31. Every word of game g is read and written by that game's threads
  * alone: no LDS, no atomics, no second buffer. Rows move in 16-byte items where hist_rows_dev and prev_rows_dev are 16-byte
  * aligned, word by word otherwise; the result is the same.
- * All nine check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                     */
+ * hb_belief_select_soft: hb_belief_select_depth's inputs read as a likelihood instead of a filter (an epsilon-greedy partner:
+ * a share of its moves is off the policy by construction). More inputs: n_legal_dev [depth][n_cand * m] int32 (laid out like
+ * hyp_moves_dev: the number of legal moves in the hypothetical state the hypothetical move was computed on), p_table_dev
+ * [2][A + 1] f64 on the device, A = hb_num_actions(cfg) (row 0: P(the real move | it is the policy's move, n legal moves), row 1:
+ * P(the real move | it is not), indexed by n), and the Philox keys seed / draw / first_row_id. Per root i, L_i as above:
+ *   lik_k = 0 if weight[i, k] == 0, else 1 times, for d = 0 .. L_i - 1 in that order, p_table[hyp[d][k, i] == actual[d][i] ? 0 : 1]
+ *   [n_legal[d][k, i]] (f64, multiplications only; an n_legal outside 1 .. A makes the factor 0);
+ *   mx = max_k lik_k; q_k = (u64) floor(lik_k / mx * 2^24); W_k = weight[i, k] * q_k in u64 (all 0 when mx == 0); T = sum_k W_k
+ *   (integers: no order); ess_dev [m] f32 = (f64) T * T / sum_k (f64) W_k^2, 0 when T == 0;
+ *   output replica r < replicas: u = (out[0] << 32 | out[1]) of Philox4x32-10 on counter (0x10000 + r, draw low word, row id low,
+ *   row id high) with row id = first_row_id + i and hb_belief_determinize's key (seed low, seed high ^ draw high);
+ *   target = (u * T) >> 64; the candidate is the first k whose inclusive prefix sum W_0 + .. + W_k exceeds target: its row
+ *   copied whole, out_weight = 1 (the replicas are drawn in proportion to importance weight times likelihood, with
+ *   replacement, so they weigh the same). T == 0: every replica is dead (weight 0, an unchanged copy of src row i);
+ *   n_surv_dev as hb_belief_select_depth's (candidates with at least D leading matches); depth_used_dev [m] = L_i; fallback_dev
+ *   [m] = 2 if L_i == 0 (lik = 1 for every live candidate: the draws follow the importance weights alone), else 0: there is no
+ *   fallback to a shallower filter, a move that no candidate explains scales every likelihood alike.
+ * One wavefront per root, candidates 64 at a time: a sweep for mx and n_surv, one for T, and per 64 outputs one with an inclusive
+ * integer scan per chunk on a running base, ballot and find-first; no atomics, no LDS, a pure function of the inputs.
+ * 1 <= n_cand <= 4096 (weights below 2^28 and q <= 2^24 keep T below 2^64), replicas >= 1 (n_cand < replicas is allowed),
+ * 1 <= depth <= 8, m * max(n_cand, replicas) * SW < 2^31.
+ * All ten check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                      */
 int hb_belief_determinize(const hb_config* cfg, const uint32_t* src_rows_dev, int64_t m, int32_t seat, int32_t replicas, uint64_t seed,
                           uint64_t draw, int64_t first_row_id, uint32_t* out_rows_dev, uint32_t* weight_dev, void* stream);
 int hb_search_reduce(const int8_t* score_dev, const uint32_t* weight_dev, const int8_t* legal_dev, int64_t m, int32_t n_actions,
@@ -969,6 +990,11 @@ int hb_belief_select_depth(const hb_config* cfg, const uint32_t* src_rows_dev, c
                            const int32_t* hyp_moves_dev, const int32_t* actual_dev, const uint8_t* valid_dev, int64_t m, int32_t n_cand,
                            int32_t replicas, int32_t depth, uint32_t* out_rows_dev, uint32_t* out_weight_dev, int32_t* n_surv_dev,
                            int32_t* depth_used_dev, uint8_t* fallback_dev, void* stream);
+int hb_belief_select_soft(const hb_config* cfg, const uint32_t* src_rows_dev, const uint32_t* det_rows_dev, const uint32_t* weight_dev,
+                          const int32_t* hyp_moves_dev, const int32_t* n_legal_dev, const int32_t* actual_dev, const uint8_t* valid_dev,
+                          const double* p_table_dev, int64_t m, int32_t n_cand, int32_t replicas, int32_t depth, uint64_t seed,
+                          uint64_t draw, int64_t first_row_id, uint32_t* out_rows_dev, uint32_t* out_weight_dev, int32_t* n_surv_dev,
+                          int32_t* depth_used_dev, uint8_t* fallback_dev, float* ess_dev, void* stream);
 int hb_belief_history_step(const hb_config* cfg, int64_t m, int32_t depth, int32_t seat, const int32_t* own_moves_dev,
                            const uint8_t* reset_dev, const uint32_t* cur_rows_dev, const uint32_t* prev_rows_dev,
                            uint32_t* hist_rows_dev, int32_t* hist_moves_dev, uint8_t* hist_alive_dev, uint8_t* hist_valid_dev,

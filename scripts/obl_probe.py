@@ -30,10 +30,20 @@ run learns.
             the kernel's registers / LDS per configuration from the compiler's remarks (--resources-only: that part alone, no GPU;
             --skip-resources: everything else). Parts already in the output file are kept.
 
-Usage: obl_probe.py [out.json] [--skip-learn] [--learn-steps N] [--level2] [--level2-steps N]
+  soft      (--level2 --soft: this part alone, to profiles/obl/obl_soft_probe.json) the epsilon-aware soft likelihood filter
+            (OffBeliefSession(belief_epsilon=...), hb_belief_select_soft) against the exact-match filter: `level2`'s sessions at
+            depth 1 and 2 (32 768 games, oversample 4), ONE session per depth with `belief_epsilon` toggled between None and the
+            training epsilon (0.1) from window to window, alternated windows, all REPS figures and their spread; the counters'
+            rates and the mean effective sample size per leg (differences of the session's counters around each window);
+            registers of the kernel (--resources-only: that part alone, no GPU; --skip-resources: everything else); the ladder's
+            level-2 session (Hanabi-Small, 4 096 games) timed with the same toggle; and `level2`'s short ladder on Hanabi-Small
+            with belief_epsilon = the training epsilon at level 2 (--skip-learn: not).
+            It is a different estimator, not a speed-up: no time is gated. Parts already in the output file are kept.
+
+Usage: obl_probe.py [out.json] [--skip-learn] [--learn-steps N] [--level2 [--soft]] [--level2-steps N]
                     [--encode-rows [--resources-only | --skip-resources]] [--sessions-in-a-row]
-       (default profiles/obl/obl_probe.json; with --level2 profiles/obl/obl_level2_probe.json; with --encode-rows
-       profiles/obl/encode_rows_probe.json)"""
+       (default profiles/obl/obl_probe.json; with --level2 profiles/obl/obl_level2_probe.json; with --level2 --soft
+       profiles/obl/obl_soft_probe.json; with --encode-rows profiles/obl/encode_rows_probe.json)"""
 import json
 import os
 import re
@@ -451,6 +461,151 @@ def level2(path, ladder_steps, skip_learn):
         json.dump(out, f, indent=1)
 
 
+def level2_soft(path, ladder_steps, skip_learn, resources, measure):
+    """The `soft` part; see the module docstring."""
+    out = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            out = json.load(f)
+
+    def save():
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+
+    if resources:
+        out["kernel"] = kernel_resources("belief.hip", only="select_soft")
+        print(json.dumps(out["kernel"]), flush=True)
+        save()
+    if not measure:
+        return
+    import torch
+
+    import hanabi_hip
+    from hanabi_agents.rlax_dqn import ActionSpec, DQNAgent, ObservationSpec, RlaxRainbowParams
+    from hanabi_hip import CrossPlay, OffBeliefSession
+    from hanabi_hip.obl import frozen_copy
+
+    if not torch.cuda.is_available():
+        raise SystemExit("obl_probe.py measures on the GPU: none found")
+    EPS = 0.1   # RlaxRainbowParams.epsilon's default: what the live agents explore with
+
+    def agents_for(env, seeds, **kw):
+        base = dict(train_batch_size=256, experience_buffer_size=1 << 19, layers=[512], mask_terminal=True, compute_dtype="bfloat16",
+                    packed_obs=True)
+        base.update(kw)
+        agents = [DQNAgent(ObservationSpec((env.n, env.obs_len)), ActionSpec(env.num_actions), RlaxRainbowParams(seed=s, **base),
+                           device="cuda") for s in seeds]
+        assert all(float(a.params.epsilon(0)) == EPS for a in agents)
+        return agents
+
+    def window(sess, steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            sess.step()
+        sess.flush()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1000 / steps
+
+    names = OffBeliefSession.LEVEL_COUNTERS + ("ess_sum", "belief_forwards", "t")
+    read = lambda sess: {k: getattr(sess, k) for k in names}
+
+    def rates(c):
+        rows = max(1, c["conditioned_rows"] + c["fallback_rows"] + c["unconditioned_rows"])
+        cond = max(1, c["conditioned_rows"])
+        return dict(c, conditioned=round(c["conditioned_rows"] / rows, 4), fallback=round(c["fallback_rows"] / rows, 4),
+                    unconditioned=round(c["unconditioned_rows"] / rows, 4), survivors_per_conditioned_row=round(c["survivors"] / cond, 3),
+                    depth_used_per_conditioned_row=round(c["depth_used_sum"] / cond, 3), mean_ess=round(c["ess_sum"] / cond, 3),
+                    belief_forwards_per_step=round(c["belief_forwards"] / max(1, c["t"]), 2))
+
+    # ---- step time: one session per depth, the switch toggled between its windows ------------------------------------------------
+    sessions = {}
+    for depth in (1, 2):
+        env = hanabi_hip.HanabiEnv("Hanabi-Full", 2, n_games=N, seed=1, packed=True)
+        agents = agents_for(env, (1, 2))
+        sess = sessions["depth%d" % depth] = OffBeliefSession(env, agents, belief_policy=[frozen_copy(x) for x in agents], depth=depth,
+                                                              oversample=4)
+        window(sess, WARM)
+        sess.belief_epsilon = EPS   # both paths warm
+        window(sess, 20)
+    legs = [(d, soft) for d in sessions for soft in (False, True)]
+    label = lambda d, soft: d + ("_soft" if soft else "_hard")
+    ms = {label(*leg): [] for leg in legs}
+    sums = {label(*leg): dict.fromkeys(names, 0) for leg in legs}
+    for _ in range(REPS):
+        for d, soft in legs:
+            sess = sessions[d]
+            sess.belief_epsilon = EPS if soft else None
+            before = read(sess)
+            ms[label(d, soft)].append(round(window(sess, STEPS), 4))
+            after = read(sess)
+            for k in names:
+                sums[label(d, soft)][k] += after[k] - before[k]
+    out["step"] = dict(games=N, steps_per_window=STEPS, oversample=4, belief_epsilon=EPS, ms_per_step_runs=ms,
+                       ms_per_step_best={k: min(v) for k, v in ms.items()},
+                       window_spread_ms={k: round(max(v) - min(v), 4) for k, v in ms.items()},
+                       counters={k: rates(v) for k, v in sums.items()})
+    print(json.dumps(out["step"]), flush=True)
+    save()
+    del sessions, sess, env, agents
+    torch.cuda.empty_cache()
+
+    # ---- the ladder's level-2 session (Hanabi-Small, 4 096 games, batch 128, depth 2), timed the same way: a ladder run's seconds
+    # depend on its session's place in the process (DESIGN.md section 11g), the toggled windows of one session do not
+    env = hanabi_hip.HanabiEnv("Hanabi-Small", 2, n_games=4096, seed=201, packed=True)
+    team = agents_for(env, (41, 51), experience_buffer_size=1 << 17, train_batch_size=128)
+    sess = OffBeliefSession(env, team, belief_policy=[frozen_copy(a) for a in team], depth=2, oversample=4)
+    window(sess, WARM)
+    sess.belief_epsilon = EPS
+    window(sess, 20)
+    small = {"hard": [], "soft": []}
+    for _ in range(REPS):
+        for soft in (False, True):
+            sess.belief_epsilon = EPS if soft else None
+            small["soft" if soft else "hard"].append(round(window(sess, STEPS), 4))
+    out["ladder_step"] = dict(game="Hanabi-Small", games=4096, depth=2, oversample=4, steps_per_window=STEPS, ms_per_step_runs=small,
+                              ms_per_step_best={k: min(v) for k, v in small.items()})
+    print(json.dumps(out["ladder_step"]), flush=True)
+    save()
+    del sess, env, team
+    torch.cuda.empty_cache()
+
+    # ---- `level2`'s short ladder, level 2 with the soft filter ---------------------------------------------------------------------
+    if not skip_learn:
+        n, pool, runs = 4096, [], []
+        for seed in (1, 2):
+            frozen = None
+            for lvl in (1, 2):
+                env = hanabi_hip.HanabiEnv("Hanabi-Small", 2, n_games=n, seed=100 * lvl + seed, packed=True)
+                team = agents_for(env, (seed + 20 * lvl, seed + 20 * lvl + 10), experience_buffer_size=1 << 17, train_batch_size=128)
+                sess = OffBeliefSession(env, team) if lvl == 1 else OffBeliefSession(env, team, belief_policy=frozen, depth=2, oversample=4,
+                                                                                     belief_epsilon=EPS)
+                t0 = time.perf_counter()
+                sess.run(ladder_steps)
+                torch.cuda.synchronize()
+                info = dict(run=f"level{lvl}{'_soft' if lvl == 2 else ''}/{seed}", env_steps=sess.env_steps, grad_steps=sess.grad_steps,
+                            seconds=round(time.perf_counter() - t0, 1), train_score=round(sess.mean_score(), 3))
+                if lvl == 1:
+                    frozen = [frozen_copy(a) for a in team]
+                else:
+                    info["counters"] = rates(read(sess))
+                print(json.dumps(info), flush=True)
+                runs.append(info)
+                pool += team
+        # pool and teams as in `level2`: per level its own teams, then the seats swapped between the runs
+        teams = [(0, 1), (4, 5), (0, 5), (4, 1), (2, 3), (6, 7), (2, 7), (6, 3)]
+        res = CrossPlay("Hanabi-Small", 2, n_games=4096, seed=7, responses=True).run(pool, teams=teams)
+        dist = res.convention_distance()
+        cell = lambda k: [round(res.results[k].mean, 3), round(res.results[k].stderr, 3)]
+        table = {kind: dict(self_play=[cell(b), cell(b + 1)], cross_play=[cell(b + 2), cell(b + 3)],
+                            convention_distance=round(float(dist[b, b + 1]), 4)) for kind, b in (("level1", 0), ("level2_soft", 4))}
+        out["ladder"] = dict(game="Hanabi-Small", players=2, games=n, steps=ladder_steps, env_steps=n * ladder_steps, depth=2, oversample=4,
+                             belief_epsilon=EPS, runs=runs, eval_games=4096, teams=teams, table=table)
+        print(json.dumps(out["ladder"]["table"]), flush=True)
+        save()
+
+
 def main():
     import argparse
 
@@ -460,6 +615,7 @@ def main():
     ap.add_argument("--learn-steps", type=int, default=4000)
     ap.add_argument("--level2", action="store_true")
     ap.add_argument("--level2-steps", type=int, default=20000)
+    ap.add_argument("--soft", action="store_true")
     ap.add_argument("--encode-rows", action="store_true")
     ap.add_argument("--resources-only", action="store_true")
     ap.add_argument("--skip-resources", action="store_true")
@@ -470,6 +626,9 @@ def main():
     if opt.encode_rows:
         return encode_rows_probe(opt.out or os.path.join(ROOT, "profiles", "obl", "encode_rows_probe.json"),
                                  resources=not opt.skip_resources, measure=not opt.resources_only)
+    if opt.level2 and opt.soft:
+        return level2_soft(opt.out or os.path.join(ROOT, "profiles", "obl", "obl_soft_probe.json"), opt.level2_steps, opt.skip_learn,
+                           resources=not opt.skip_resources, measure=not opt.resources_only)
     if opt.level2:
         return level2(opt.out or os.path.join(ROOT, "profiles", "obl", "obl_level2_probe.json"), opt.level2_steps, opt.skip_learn)
     opt.out = opt.out or os.path.join(ROOT, "profiles", "obl", "obl_probe.json")
