@@ -35,6 +35,10 @@
 // hb_belief_history_step: a PartnerHistory (the [depth, m] stack of states the partner moved from, with its moves, alive masks and
 // valid flags) advanced by one turn in place: own move out of the alive masks, reset of re-dealt games, push of a new entry. One
 // launch; rows move as contiguous 16-byte items, the byte fields one game per lane (see the kernel).
+//
+// hb_belief_score: any of these beliefs scored against the cards the seat really holds: per slot the weight of the replicas that
+// hold the true card (and, on request, of every card), the weight of those that hold the whole hand, and the card-counting prior
+// read from the true row alone. One wavefront per root, 64-bit integer sums, no float arithmetic; no LDS, barrier or atomic.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -741,6 +745,116 @@ __global__ void __launch_bounds__(256) belief_history_step_kernel(HistoryArgs a)
   }
 }
 
+struct ScoreArgs {
+  const uint32_t* truth_rows;   // [m, SW]
+  const uint32_t* det;          // [m * R, SW]
+  const uint32_t* weight;       // [m * R]
+  int8_t* truth;                // [m, H]
+  long long* hit;               // [m, H]
+  long long* joint;             // [m]
+  long long* wsum;              // [m]
+  int32_t* n_live;              // [m]
+  long long* counts;            // [m, H, NC] or null
+  int8_t* prior;                // [m, H, NC]
+  long long m;
+  int seat, R, P, C, Rk, H, D, SW, NC;
+};
+
+constexpr int MAX_HAND = 5;   // hb_config_validate's largest hand: the slots of one hand word
+
+// One wavefront per root, integers only. Lane j < SW holds word j of the TRUE row; its scalars travel by v_readlane. Lane c < NC
+// owns card c: the copies of c in the seat's pool (its hand slots, then the undealt deck bytes, walked by v_readlane of the deck
+// words) give prior[s][c] under slot s's knowledge bits. The replicas come 64 at a time, one (hand word, weight) pair per lane:
+// wsum, n_live, joint and hit[s] are sums over the replicas, each lane adding its own and one xor butterfly at the end; counts (when
+// asked for) walks the batch by v_readlane, lane c adding the weight of every replica whose slot s holds c to its H accumulators.
+// The loops over the slots are unrolled to MAX_HAND with wave-uniform guards, so that the accumulators stay in registers.
+__global__ void __launch_bounds__(256) belief_score_kernel(ScoreArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long long i = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  if (i >= a.m) return;
+  const uint32_t wj = lane < a.SW ? a.truth_rows[i * a.SW + lane] : 0u;
+  const uint32_t w0 = lane_read(wj, 0), w1 = lane_read(wj, 1);
+  const int seat = a.seat < 0 ? static_cast<int>((w0 >> 13) & 7u) : a.seat;
+  const bool scored = ((w0 >> 19) & 3u) == 0 && seat < a.P;   // (wave-uniform)
+  const int st = scored ? seat : 0;                           // (a seat whose words exist, whatever the row says)
+  const uint32_t hand = lane_read(wj, 10 + st);
+  const uint64_t know = (static_cast<uint64_t>(lane_read(wj, 10 + a.P + 2 * st + 1)) << 32) | lane_read(wj, 10 + a.P + 2 * st);
+  const int n_hand = scored ? min(static_cast<int>((w1 >> (15 + 3 * st)) & 7u), a.H) : 0;
+  const uint32_t hand_mask = (1u << (5 * n_hand)) - 1u;   // the fields of the slots that count (n_hand <= H <= 5)
+
+  // ---- truth and prior, from the true row alone ---------------------------------------------------------------------------------
+  const uint32_t me = static_cast<uint32_t>(lane);   // the card this lane owns (meaningful below NC)
+  int pool = 0;
+#pragma unroll
+  for (int s = 0; s < MAX_HAND; ++s) pool += s < n_hand && ((hand >> (5 * s)) & 31u) == me ? 1 : 0;
+  if (scored) {
+    const int deck_size = min(static_cast<int>(w0 & 63u), a.D);
+    const int W_DECK = 10 + 3 * a.P;
+    for (int q = a.D - deck_size; q < a.D; ++q) {   // (wave-uniform bounds; W_DECK + (D - 1) / 4 < SW)
+      const uint32_t card = (lane_read(wj, W_DECK + (q >> 2)) >> (8 * (q & 3))) & 255u;
+      pool += card == me ? 1 : 0;
+    }
+  }
+  const uint32_t col = me / static_cast<uint32_t>(a.Rk), rk = me - col * static_cast<uint32_t>(a.Rk);
+  bool truth_ok = true;   // every slot of the true hand holds a card a replica can match
+#pragma unroll
+  for (int s = 0; s < MAX_HAND; ++s) {
+    if (s < a.H) {
+      const uint32_t t = (hand >> (5 * s)) & 31u;
+      const uint32_t kn = static_cast<uint32_t>(know >> (12 * s)) & 0xFFFu;
+      const bool allowed = s < n_hand && ((kn >> col) & 1u) && ((kn >> (5u + rk)) & 1u);
+      if (lane < a.NC) a.prior[(i * a.H + s) * a.NC + lane] = static_cast<int8_t>(allowed ? pool : 0);
+      if (lane == s) a.truth[i * a.H + s] = static_cast<int8_t>(s < n_hand ? static_cast<int>(t) : -1);
+      if (s < n_hand) truth_ok = truth_ok && t < static_cast<uint32_t>(a.NC);
+    }
+  }
+
+  // ---- the replicas, 64 at a time -------------------------------------------------------------------------------------------------
+  long long sw = 0, nl = 0, jn = 0, hit[MAX_HAND], cnt[MAX_HAND];
+#pragma unroll
+  for (int s = 0; s < MAX_HAND; ++s) hit[s] = cnt[s] = 0;
+  const uint32_t* w = a.weight + i * a.R;
+  const uint32_t* dh = a.det + i * a.R * a.SW + 10 + st;   // the hand word of replica 0
+  for (int r0 = 0; r0 < a.R && scored; r0 += 64) {
+    const int r = r0 + lane;
+    const uint32_t wr = r < a.R ? w[r] : 0u;
+    const uint32_t hr = r < a.R ? dh[static_cast<long long>(r) * a.SW] : 0u;
+    sw += wr;
+    nl += wr != 0u ? 1 : 0;
+    jn += truth_ok && ((hr ^ hand) & hand_mask) == 0u ? wr : 0u;
+#pragma unroll
+    for (int s = 0; s < MAX_HAND; ++s) {
+      const uint32_t f = (hr >> (5 * s)) & 31u;
+      hit[s] += s < n_hand && f < static_cast<uint32_t>(a.NC) && f == ((hand >> (5 * s)) & 31u) ? wr : 0u;
+    }
+    if (a.counts) {
+      const int nb = min(64, a.R - r0);
+      for (int j = 0; j < nb; ++j) {
+        const uint32_t wv = lane_read(wr, j), hv = lane_read(hr, j);
+        if (wv == 0u) continue;   // (wave-uniform)
+#pragma unroll
+        for (int s = 0; s < MAX_HAND; ++s) cnt[s] += s < n_hand && ((hv >> (5 * s)) & 31u) == me ? wv : 0u;
+      }
+    }
+  }
+  sw = wave_sum(sw);
+  nl = wave_sum(nl);
+  jn = wave_sum(jn);
+  long long mine = 0;   // hit of slot `lane`
+#pragma unroll
+  for (int s = 0; s < MAX_HAND; ++s) {
+    const long long h = wave_sum(hit[s]);
+    mine = lane == s ? h : mine;
+    if (a.counts && s < a.H && lane < a.NC) a.counts[(i * a.H + s) * a.NC + lane] = cnt[s];
+  }
+  if (lane < a.H) a.hit[i * a.H + lane] = mine;
+  if (lane == 0) {
+    a.joint[i] = jn;
+    a.wsum[i] = sw;
+    a.n_live[i] = static_cast<int32_t>(nl);
+  }
+}
+
 int have_device() {
   static const int ndev = [] {
     int n = 0;
@@ -1001,6 +1115,37 @@ extern "C" int hb_belief_history_step(const hb_config* cfg, int64_t m, int32_t d
     hipLaunchKernelGGL(belief_history_step_kernel<uint4>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   else
     hipLaunchKernelGGL(belief_history_step_kernel<uint32_t>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+extern "C" int hb_belief_score(const hb_config* cfg, const uint32_t* true_rows_dev, const uint32_t* det_rows_dev, const uint32_t* weight_dev,
+                               int64_t m, int32_t seat, int32_t replicas, int8_t* truth_dev, int64_t* hit_dev, int64_t* joint_dev,
+                               int64_t* wsum_dev, int32_t* n_live_dev, int64_t* counts_dev, int8_t* prior_dev, void* stream) {
+  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  if (m < 0) return hb::fail(HB_ERR_INVALID, "m must be >= 0");
+  if (replicas < 1 || replicas > (1 << 20)) return hb::fail(HB_ERR_INVALID, "replicas %d out of range 1..2^20 (64-bit sums)", replicas);
+  if (seat < -1 || seat >= cfg->players)
+    return hb::fail(HB_ERR_INVALID, "seat %d out of range: -1 (each row's current player) or 0..%d", seat, cfg->players - 1);
+  if (!true_rows_dev || !det_rows_dev || !weight_dev || !truth_dev || !hit_dev || !joint_dev || !wsum_dev || !n_live_dev || !prior_dev)
+    return hb::fail(HB_ERR_INVALID, "null argument");   // (counts may be null)
+  if (m > (static_cast<int64_t>(1) << 31) - 8) return hb::fail(HB_ERR_INVALID, "m must stay below 2^31 roots");
+  if (m == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  ScoreArgs a{};
+  a.truth_rows = true_rows_dev; a.det = det_rows_dev; a.weight = weight_dev;
+  a.truth = truth_dev; a.hit = reinterpret_cast<long long*>(hit_dev); a.joint = reinterpret_cast<long long*>(joint_dev);
+  a.wsum = reinterpret_cast<long long*>(wsum_dev); a.n_live = n_live_dev; a.counts = reinterpret_cast<long long*>(counts_dev);
+  a.prior = prior_dev;
+  a.m = m;
+  a.seat = seat; a.R = replicas;
+  a.P = cfg->players; a.C = cfg->colors; a.Rk = cfg->ranks; a.H = cfg->hand_size;
+  a.D = hb_deck_size(cfg);
+  a.SW = hb_state_words(cfg);
+  a.NC = cfg->colors * cfg->ranks;
+  const unsigned blocks = static_cast<unsigned>((m + 3) / 4);   // four wavefronts = four roots per workgroup
+  hipLaunchKernelGGL(belief_score_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   HB_HIP(hipGetLastError());
   return HB_OK;
 }

@@ -52,6 +52,13 @@ fallback: `fallback_rows` stays 0, `conditioned_rows` counts the live rows with 
 their usable moves, and `ess_sum` adds up the effective sample size of the conditioned rows' weighted candidates (a move nobody
 explains leaves the likelihoods equal: the V0 belief, by itself). No learning gain is claimed for it.
 
+`score_belief=True` (default False: nothing is computed, and training is the same bits either way) scores the fictitious state of
+every branch against the real cards before the branch is played (hb_belief_score, `hanabi_hip.search.belief_score`, one replica per
+game): `belief_cards` (the cards scored), `belief_hit_sum` (those the fictitious hand gets right, slot by slot), `belief_prior_sum`
+(the sum of the mass card counting alone puts on the true card), `belief_joint_sum` (whole hands right) and `belief_roots`. At one
+replica per game hit_sum / cards is still an unbiased estimate of the mass the belief puts on the true card; a cross-entropy needs
+more replicas and is not reported here.
+
 The frozen policy's observations of the K candidate slabs come from one hb_encode_rows call (`self.cdet.stateless`, on by default;
 False: an import and an observe per slab on a scratch env, the same bits).
 
@@ -63,8 +70,8 @@ import torch
 
 from . import _capi as K
 from .env import HanabiEnv
-from .search import (MAX_DEPTH, MAX_SOFT_CANDIDATES, ConditionedDeterminizer, Determinizer, PartnerHistory, _ask, running,
-                     soft_table)
+from .search import (MAX_DEPTH, MAX_SOFT_CANDIDATES, ConditionedDeterminizer, Determinizer, PartnerHistory, _ask, belief_score,
+                     running, soft_table)
 from .selfplay import SelfPlaySession
 
 
@@ -79,14 +86,18 @@ class OffBeliefSession(SelfPlaySession):
     conditioned_rows (live rows whose fictitious state reproduces at least one partner move: fallback == 0), fallback_rows (usable
     moves, no surviving candidate: the V0 belief), unconditioned_rows (no usable move), survivors (sum over the conditioned rows
     of the candidates that pass the filter of the depth used), depth_used_sum, and belief_forwards (eval_moves calls made for the
-    belief, counted on the host). belief_epsilon (the soft filter, see the module docstring) adds ess_sum (a float)."""
+    belief, counted on the host). belief_epsilon (the soft filter, see the module docstring) adds ess_sum (a float).
+    score_belief (both levels; see the module docstring) adds belief_cards, belief_roots (ints), belief_hit_sum, belief_prior_sum
+    and belief_joint_sum (floats): device sums, read with one sync each, 0 in a session built without the switch (one built with
+    it may set `score_belief` to False and back between steps)."""
 
     LEVEL_COUNTERS = ("conditioned_rows", "fallback_rows", "unconditioned_rows", "survivors", "depth_used_sum")
+    BELIEF_COUNTERS = ("belief_cards", "belief_hit_sum", "belief_prior_sum", "belief_joint_sum", "belief_roots")
 
     _select_in_env = False   # a_t is needed before the env steps
 
     def __init__(self, env, agents, train_seats=None, belief_seed=1, updates_per_step=1, min_replay=None, belief_policy=None,
-                 depth=1, oversample=4, belief_epsilon=None):
+                 depth=1, oversample=4, belief_epsilon=None, score_belief=False):
         import torch.distributed as dist
 
         from .partner_pool import PartnerPool
@@ -114,6 +125,8 @@ class OffBeliefSession(SelfPlaySession):
                                  "bootstrap through)")
             if int(getattr(a, "actor_lag", 0)) != 0:
                 raise ValueError(f"seat {s}: actor_lag must be 0, got {a.actor_lag}")
+        if not isinstance(score_belief, bool):
+            raise TypeError(f"score_belief is a switch (True or False), got {score_belief!r}")
         depth, oversample = int(depth), int(oversample)
         if belief_epsilon is not None:
             if belief_policy is None:
@@ -163,6 +176,8 @@ class OffBeliefSession(SelfPlaySession):
         self._dead = torch.zeros((), dtype=torch.int64, device=dev)
         self._ask_scratch = weakref.WeakKeyDictionary()   # agent -> the buffers its eval_moves writes
         self.branch_steps = 0
+        self.score_belief = score_belief
+        self._belief = torch.zeros(len(self.BELIEF_COUNTERS), dtype=torch.float64, device=dev) if score_belief else None
         # level k >= 2: the partner histories of the training env and what advancing them needs from the last two steps
         self.belief_policy, self.depth, self.oversample = belief_policy, depth, oversample
         self.belief_epsilon = belief_epsilon
@@ -226,6 +241,13 @@ class OffBeliefSession(SelfPlaySession):
         surv = n_surv.gather(0, (used.long() - 1).clamp(min=0).view(1, -1)).view(-1)
         self._level += torch.stack([cond.sum(), (fb == 1).sum(), (running(rows) & (fb == 2)).sum(), (surv * cond).sum(), used.sum()])
 
+    def _score(self, rows, seat):
+        """score_belief: the fictitious states in _det_rows / _det_w against the real `rows`, one replica per game."""
+        if not self.score_belief:
+            return
+        s = belief_score(self.det.cfg, rows, self._det_rows, self._det_w, seat, 1).sums()
+        self._belief += torch.stack([s[0].sum(), s[1].sum(), s[2].sum(), s[6, 0], s[5, 0]])
+
     def _record(self, agent, seat, observations):
         """Nothing: the real transition is not inserted (trained seats), and a passive seat's replay is never read."""
 
@@ -248,8 +270,10 @@ class OffBeliefSession(SelfPlaySession):
         if seat not in self.branch_seats:
             return
         with torch.cuda.device(self.env.device):
-            self.det.sample(self.env.export_state(), seat=seat, replicas=1, seed=self.belief_seed, draw=self.t,
-                            first_row_id=self.env.first_game_id, out=(self._det_rows, self._det_w))
+            rows = self.env.export_state()
+            self.det.sample(rows, seat=seat, replicas=1, seed=self.belief_seed, draw=self.t, first_row_id=self.env.first_game_id,
+                            out=(self._det_rows, self._det_w))
+            self._score(rows, seat)
             self._branch(agent, seat, actions)
 
     def _before_env_step_conditioned(self, agent, seat, actions):
@@ -263,6 +287,7 @@ class OffBeliefSession(SelfPlaySession):
                 torch.bitwise_or(env.terminal, self._term_old, out=self._reset)
             if seat in self.branch_seats:
                 self._conditioned_sample(seat, rows, first)
+                self._score(rows, seat)
                 self._branch(agent, seat, actions)
                 self._own[seat].copy_(actions)
                 self._own_t[seat] = self.t
@@ -302,6 +327,12 @@ def _without_reset(cfg):
 for _j, _name in enumerate(OffBeliefSession.LEVEL_COUNTERS):   # the level k >= 2 device counters as read-only ints (0 at level 1)
     setattr(OffBeliefSession, _name,
             property(lambda self, j=_j: 0 if self.belief_policy is None else int(self._level[j].item())))
+
+
+for _j, _name in enumerate(OffBeliefSession.BELIEF_COUNTERS):   # score_belief's device sums (0 in a session built without it)
+    setattr(OffBeliefSession, _name,
+            property(lambda self, j=_j, kind=(float if _name.endswith("_sum") else int): kind(0 if self._belief is None else
+                                                                                              self._belief[j].item())))
 
 
 def frozen_copy(agent):

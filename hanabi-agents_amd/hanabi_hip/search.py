@@ -34,6 +34,10 @@
   likelihood (`soft_table`: 1 - e + e / n per reproduced move, e / n per missed one, n = the legal moves of the hypothetical
   state) and the replicas are drawn in proportion to importance weight times likelihood (hb_belief_select_soft;
   `belief_select_soft_ref` is its numpy restatement). No depth fallback; the results carry the candidates' effective sample size.
+* `belief_score` (hb_belief_score; `belief_score_ref` is its numpy restatement) scores any of these beliefs against the cards the
+  seat really holds: per slot the weight of the replicas that hold the true card, for the whole hand, and next to the card-counting
+  prior, in exact integers; `BeliefScore` forms the hit rates and cross-entropies. `score_belief=True` (`RolloutSearch`,
+  `SearchPlayer`; default False: nothing is computed) scores every search's replicas; `SearchPlayer.belief_stats()` gives the means.
 * `SearchPlayer` is an agent for `Evaluator.run`: the blueprint's move unless the search finds one that is better by more than
   `threshold` and, with `z` / `confirm_replicas`, by more than z standard errors of the paired difference.
 
@@ -348,6 +352,193 @@ def belief_select_soft_ref(src_rows, det_rows, weights, hyp_moves, n_legal, actu
         ow[i * R:(i + 1) * R] = 1
     out = (rows, ow, n_surv, L, np.where(L == 0, 2, 0).astype(np.uint8), ess)
     return out + (dict(lik=lik, q=q, W=W, T=T, target=target, pick=pick),) if details else out
+
+
+def belief_score(cfg, true_rows, det_rows, weights, seat, replicas, counts=False, out=None):
+    """hb_belief_score: true_rows [m, SW] int32 the real states, det_rows [m * R, SW] int32 and weights [m * R] (u32 bits in
+    int32) replicas of them from any of the samplers (replica r of root i = row i * R + r), seat (-1: each true row's current
+    player) -> `BeliefScore`: what the belief gives the cards the seat really holds, next to the card-counting prior, in exact
+    integers (include/hanabi_hip.h). counts=True also fills the [m, H, NC] per-card tally. `out`: an optional tuple of the
+    buffers (truth, hit, joint, wsum, n_live, prior[, counts]) to write into. GPU only."""
+    m, SW = true_rows.shape
+    R, dev = int(replicas), true_rows.device
+    H, NC, n = cfg.hand_size, cfg.colors * cfg.ranks, m * max(int(replicas), 0)
+    _bufs(dev, (true_rows, det_rows, weights), ((m, SW), torch.int32), ((n, SW), torch.int32), ((n,), torch.int32))
+    for t in (true_rows, det_rows, weights):
+        if not t.is_cuda or t.device != dev:
+            raise K.HbError("hb_belief_score reads tensors of one GPU (there is no CPU path)")
+    specs = (((m, H), torch.int8), ((m, H), torch.int64), ((m,), torch.int64), ((m,), torch.int64), ((m,), torch.int32),
+             ((m, H, NC), torch.int8)) + ((((m, H, NC), torch.int64),) if counts else ())
+    bufs = _bufs(dev, out, *specs)
+    truth, hit, joint, wsum, n_live, prior = bufs[:6]
+    tally = bufs[6] if counts else None
+    with torch.cuda.device(dev):
+        K.check(K.lib().hb_belief_score(C.byref(cfg), K.dptr(true_rows), K.dptr(det_rows), K.dptr(weights), m, int(seat), R,
+                                        K.dptr(truth), K.dptr(hit), K.dptr(joint), K.dptr(wsum), K.dptr(n_live), K.dptr(tally),
+                                        K.dptr(prior), K.current_stream()))
+    return BeliefScore(truth, hit, joint, wsum, n_live, prior, tally)
+
+
+def belief_score_ref(cfg, true_rows, det_rows, weights, seat, replicas):
+    """hb_belief_score restated in numpy, row by row and replica by replica in plain loops (nothing of the kernel's layout): arrays
+    shaped as belief_score's tensors (32-bit words of either sign) -> a dict of numpy arrays: truth int8 [m, H], hit int64
+    [m, H], joint, wsum int64 [m], n_live int32 [m], counts int64 [m, H, NC], prior int8 [m, H, NC]. Runs without a GPU;
+    `BeliefScore(**belief_score_ref(...))` gives the figures."""
+    import numpy as np
+
+    u32 = lambda x: (np.asarray(x).astype(np.int64) & _M32).astype(np.uint32)
+    rows, det = u32(true_rows), u32(det_rows)
+    (m, SW), R = rows.shape, int(replicas)
+    w = u32(weights).reshape(m, R)
+    assert det.shape == (m * R, SW)
+    P, H, Rk, NC = cfg.players, cfg.hand_size, cfg.ranks, cfg.colors * cfg.ranks
+    D = cfg.colors * sum(3 if r == 0 else 1 if r == Rk - 1 else 2 for r in range(Rk))
+    out = dict(truth=np.full((m, H), -1, np.int8), hit=np.zeros((m, H), np.int64), joint=np.zeros(m, np.int64),
+               wsum=np.zeros(m, np.int64), n_live=np.zeros(m, np.int32), counts=np.zeros((m, H, NC), np.int64),
+               prior=np.zeros((m, H, NC), np.int8))
+    for i in range(m):
+        w0, w1 = int(rows[i, 0]), int(rows[i, 1])
+        st = int(seat) if int(seat) >= 0 else (w0 >> 13) & 7
+        if (w0 >> 19) & 3 != 0 or st >= P:
+            continue
+        hand = int(rows[i, 10 + st])
+        know = int(rows[i, 10 + P + 2 * st]) | int(rows[i, 10 + P + 2 * st + 1]) << 32
+        n = min((w1 >> (15 + 3 * st)) & 7, H)
+        true = [(hand >> (5 * s)) & 31 for s in range(n)]
+        deck = np.ascontiguousarray(rows[i, 10 + 3 * P:], dtype="<u4").view(np.uint8)
+        pool = true + [int(deck[q]) for q in range(D - min(w0 & 63, D), D)]
+        for s in range(n):
+            out["truth"][i, s] = true[s]
+            kn = (know >> (12 * s)) & 0xFFF
+            for c in range(NC):
+                if (kn >> (c // Rk)) & 1 and (kn >> (5 + c % Rk)) & 1:
+                    out["prior"][i, s, c] = pool.count(c)
+        for r in range(R):
+            wr = int(w[i, r])
+            if wr == 0:
+                continue
+            out["wsum"][i] += wr
+            out["n_live"][i] += 1
+            word = int(det[i * R + r, 10 + st])
+            cards = [(word >> (5 * s)) & 31 for s in range(n)]
+            for s in range(n):
+                if cards[s] < NC:
+                    out["counts"][i, s, cards[s]] += wr
+            if all(c < NC and c == t for c, t in zip(cards, true)):
+                out["joint"][i] += wr
+        for s in range(n):
+            if true[s] < NC:
+                out["hit"][i, s] = out["counts"][i, s, true[s]]
+    return out
+
+
+def belief_figures(sums):
+    """The means of a `BeliefScore.sums()` tensor (or of a sum of several; None: nothing yet) as plain numbers: `cards` (the
+    scored (root, slot) pairs), `roots`, `hit_rate`, `prior_rate`, `joint_rate`, `cross_entropy`, `prior_cross_entropy` and
+    `by_slot`, the same five per-card figures as lists over the slot's age (slot 0 = the oldest card). A mean over nothing is 0.0.
+    One device-to-host copy."""
+    rows = [[0.0]] * len(BeliefScore.SUMS) if sums is None else sums.tolist()
+    mean = lambda total, count: total / count if count else 0.0
+    cards, hit, prior, ce, pce, roots, joint = rows
+    n = sum(cards)
+    names = ("hit_rate", "prior_rate", "cross_entropy", "prior_cross_entropy")
+    out = dict(cards=int(n), roots=int(roots[0]), joint_rate=mean(joint[0], roots[0]))
+    out.update({k: mean(sum(v), n) for k, v in zip(names, (hit, prior, ce, pce))})
+    slots = range(0 if sums is None else len(cards))
+    out["by_slot"] = dict(cards=[int(cards[s]) for s in slots],
+                          **{k: [mean(v[s], cards[s]) for s in slots] for k, v in zip(names, (hit, prior, ce, pce))})
+    return out
+
+
+def belief_stats_of(sums, split=False):
+    """SearchPlayer.belief_stats() of a `SearchPlayer.belief_sums()` tensor (or of a sum of several players'; None: zeros):
+    belief_figures over all roots and, with `split`, also over the `conditioned` and the `unconditioned` ones."""
+    out = belief_figures(None if sums is None else sums.sum(0))
+    if split:
+        for j, name in enumerate(("conditioned", "unconditioned")):
+            out[name] = belief_figures(None if sums is None else sums[j])
+    return out
+
+
+class BeliefScore:
+    """What a sampled belief gives the cards a seat really holds (hb_belief_score; `belief_score`, or `belief_score_ref`'s arrays).
+
+        truth  [m, H] int8       the card id in slot s of the true hand (-1: no such slot, or the root is not scored)
+        hit    [m, H] int64      the weight of the replicas that hold that card in that slot
+        joint  [m] int64         the weight of the replicas that hold the whole true hand
+        wsum   [m] int64         the weight of all replicas; n_live [m] int32 the replicas of weight != 0
+        prior  [m, H, NC] int8   card counting alone: the copies of card c the seat cannot see, where slot s's hints allow c
+        counts [m, H, NC] int64  the weight of the replicas that hold card c in slot s (None unless asked for)
+
+    Everything the kernel writes is an integer; the ratios are formed here, in float64, on the tensors' device. `scored` [m] bool:
+    the root is running (it has a slot 0) and wsum > 0; only scored roots, and of those only the slots that have a truth, enter
+    any figure. A sampled belief gives a card it never drew no mass at all, so the cross-entropy is taken of the mixture
+    p = (1 - l) * hit / wsum + l * prior[truth] / sum_c prior (see cross_entropy)."""
+
+    SUMS = ("cards", "hit", "prior", "ce", "prior_ce", "roots", "joint")
+
+    def __init__(self, truth, hit, joint, wsum, n_live, prior, counts=None):
+        t = torch.as_tensor
+        self.truth, self.hit, self.joint, self.wsum, self.n_live, self.prior = t(truth), t(hit), t(joint), t(wsum), t(n_live), t(prior)
+        self.counts = None if counts is None else t(counts)
+
+    @property
+    def scored(self):
+        return (self.truth[:, 0] >= 0) & (self.wsum > 0)
+
+    def sums(self, smoothing=None, where=None):
+        """The raw sums behind every figure, [len(SUMS), H] float64 on the tensors' device, one column per slot: `cards` (scored
+        slots with a truth), `hit` (sum of hit / wsum), `prior` (sum of prior[truth] / sum_c prior), `ce` and `prior_ce` (sums of
+        -log p, `smoothing` as in cross_entropy), and in column 0 `roots` (scored roots) and `joint` (sum of joint / wsum).
+        where: an optional [m] bool mask of the roots to count. No host synchronisation: sums of several calls add up, and
+        `belief_figures` turns the total into means."""
+        scored = self.scored if where is None else self.scored & where
+        has = scored.unsqueeze(1) & (self.truth >= 0)
+        NC = self.prior.shape[2]
+        ws = self.wsum.clamp(min=1).double().unsqueeze(1)
+        q = self.hit.double() / ws
+        at = self.prior.gather(2, self.truth.long().clamp(0, NC - 1).unsqueeze(2)).squeeze(2).double()
+        pr = torch.where(self.truth < NC, at, 0.0) / self.prior.sum(2).clamp(min=1).double()
+        lam = 1.0 / (self.n_live.double().unsqueeze(1) + 1.0) if smoothing is None else float(smoothing)
+        zero = torch.zeros((), dtype=torch.float64, device=q.device)
+        nll = lambda p: torch.where(has, -torch.log(p), zero).sum(0)
+        first = torch.zeros_like(q[0])
+        first[0] = 1.0
+        return torch.stack([has.sum(0).double(), torch.where(has, q, zero).sum(0), torch.where(has, pr, zero).sum(0),
+                            nll((1.0 - lam) * q + lam * pr), nll(pr), first * scored.sum(),
+                            first * torch.where(scored, self.joint.double() / ws.squeeze(1), zero).sum()])
+
+    def figures(self, smoothing=None, where=None):
+        """belief_figures(self.sums(...)): every figure at once."""
+        return belief_figures(self.sums(smoothing, where))
+
+    def hit_rate(self):
+        """The mean over the scored roots' slots of hit / wsum: the mass the belief puts on the true card."""
+        return self.figures()["hit_rate"]
+
+    def prior_rate(self):
+        """The same mean of prior[truth] / sum_c prior: the mass card counting alone puts on it."""
+        return self.figures()["prior_rate"]
+
+    def joint_rate(self):
+        """The mean over the scored roots of joint / wsum: the mass on the whole true hand."""
+        return self.figures()["joint_rate"]
+
+    def cross_entropy(self, smoothing=None):
+        """Minus the mean natural log of p = (1 - l) * hit / wsum + l * prior[truth] / sum_c prior over the scored roots' slots;
+        l = `smoothing`, or 1 / (n_live + 1) per root when None (one pseudo-replica drawn from the prior). The mixture is what
+        keeps the figure finite: a sampled belief gives no mass to a card it never drew. On states reached by play the true
+        card is in the pool and plausible, so prior[truth] >= 1 and every p > 0; on edited rows (a truth the hints exclude, or
+        smoothing=0 with a missed card) the result may be inf."""
+        return self.figures(smoothing)["cross_entropy"]
+
+    def prior_cross_entropy(self):
+        """cross_entropy at l = 1: the card-counting baseline's own figure."""
+        return self.figures()["prior_cross_entropy"]
+
+    def by_slot(self, smoothing=None):
+        """The per-card figures by the slot's age (slot 0 = the oldest card): belief_figures' `by_slot`."""
+        return self.figures(smoothing)["by_slot"]
 
 
 def running(rows):
@@ -745,14 +936,15 @@ class SearchResult:
     the partner's last move): `n_surv` [m] int32 and `fallback` [m] uint8 of hb_belief_select; None without. With a
     `PartnerHistory` (its last `depth` moves): `n_surv` [depth, m], `fallback` and `depth_used` [m] int32 of
     hb_belief_select_depth; `depth_used` is None when not computed. With the search's `epsilon` (the soft filter,
-    hb_belief_select_soft): `ess` [m] float32, the effective sample size of each root's weighted candidates; None without."""
+    hb_belief_select_soft): `ess` [m] float32, the effective sample size of each root's weighted candidates; None without.
+    With the search's `score_belief`: `belief`, the `BeliefScore` of the replicas searched against the roots' real hands."""
 
     def __init__(self, value, wsum, n_live, best, rollouts, turns, dead=0, replicas=0, diff=None, se=None, n_pair=None, cand=None,
-                 best_uid=None, n_surv=None, fallback=None, depth_used=None, ess=None):
+                 best_uid=None, n_surv=None, fallback=None, depth_used=None, ess=None, belief=None):
         self.value, self.wsum, self.n_live, self.best = value, wsum, n_live, best
         self.rollouts, self.turns, self.dead, self.replicas = int(rollouts), int(turns), int(dead), int(replicas)
         self.diff, self.se, self.n_pair, self.cand, self.best_uid = diff, se, n_pair, cand, best_uid
-        self.n_surv, self.fallback, self.depth_used, self.ess = n_surv, fallback, depth_used, ess
+        self.n_surv, self.fallback, self.depth_used, self.ess, self.belief = n_surv, fallback, depth_used, ess, belief
 
     def __repr__(self):
         return f"SearchResult(roots={self.value.shape[0]}, rollouts={self.rollouts}, turns={self.turns})"
@@ -801,10 +993,12 @@ class RolloutSearch:
     determinization is the same. history may also be a `PartnerHistory` of the roots (the partner's last `depth` moves, with its
     partner_seed and first_game_id): the replicas then come from `ConditionedDeterminizer.sample_history` and the result carries
     `depth_used`. epsilon (default None: the exact-match filter): with a history, the candidates are weighed by the likelihood of
-    an epsilon-greedy partner instead of filtered (`ConditionedDeterminizer`'s epsilon) and the result carries `ess`."""
+    an epsilon-greedy partner instead of filtered (`ConditionedDeterminizer`'s epsilon) and the result carries `ess`.
+    score_belief (default False: nothing is computed): the replicas of every search are scored against the roots' real hands
+    right after the determinization (hb_belief_score) and the result carries `belief`; the search itself is unchanged."""
 
     def __init__(self, game="Hanabi-Full", players=2, replicas=32, seed=1, device=None, config=None, check_every=8, first_game_id=0,
-                 oversample=8, epsilon=None):
+                 oversample=8, epsilon=None, score_belief=False):
         self.cfg = eval_config(game, players, config)
         self.players = self.cfg.players
         self.replicas = int(replicas)
@@ -826,6 +1020,9 @@ class RolloutSearch:
             if self.replicas * self.oversample > MAX_SOFT_CANDIDATES:
                 raise ValueError(f"the soft filter takes at most {MAX_SOFT_CANDIDATES} candidates per root, got replicas * oversample = "
                                  f"{self.replicas * self.oversample}")
+        if not isinstance(score_belief, bool):
+            raise TypeError(f"score_belief is a switch (True or False), got {score_belief!r}")
+        self.score_belief = score_belief
         self.n_counters = K.lib().hb_eval_counters(C.byref(self.cfg))
         self._sized = {}   # (m, C, replicas) -> the rollout env and buffers of that size, with the scratch of its blueprint
         self._uid = None   # [1, A] int32: every uid, on the device (built by the first run())
@@ -914,6 +1111,7 @@ class RolloutSearch:
                                        epsilon=self.epsilon)
                 n_surv, fallback = got[2:4]
                 ess = got[4] if self.epsilon is not None else None
+            belief = belief_score(self.cfg, r, b["det_rows"], b["weights"], cp, R) if self.score_belief else None
             # [m, C, R]: block c of root i holds the same R replicas. A slot without a candidate (an illegal action, in run()) is
             # never counted (done up front); its games move in step with the others on the root's filler move, so that no illegal
             # move reaches the env
@@ -936,7 +1134,7 @@ class RolloutSearch:
             value, wsum, n_live, best = search_reduce(scores, weights, slots)
             rollouts, dead, roots = counts.tolist()
             res = SearchResult(value, wsum, n_live, best, rollouts, turns, dead=dead, replicas=roots * R, n_surv=n_surv,
-                               fallback=fallback, depth_used=depth_used, ess=ess)
+                               fallback=fallback, depth_used=depth_used, ess=ess, belief=belief)
             if base_slot is not None:
                 res.diff, res.se, res.n_pair = search_compare(scores, weights, cand, base_slot)
         return res
@@ -1083,13 +1281,17 @@ class SearchPlayer:
     searched with the filter), `unconditioned` (live roots without), `survivors` / `candidates` (sums over the conditioned
     roots), `fallbacks` (conditioned roots without a survivor), `depth_used` (sum over the conditioned roots of the number of
     partner moves their replicas reproduce: 1 per root that did not fall back at depth 1; with depth > 1 `survivors` counts the
-    candidates that pass the filter of the depth used)."""
+    candidates that pass the filter of the depth used).
+
+    score_belief (default False: nothing is computed or allocated, and the moves played are the same bits either way): every
+    first-stage search scores its replicas against the real hands (RolloutSearch's score_belief, hb_belief_score) and the player
+    adds the sums up on the device; belief_stats() gives the means."""
 
     COUNTERS = ("moves", "deviations", "confirmed", "rejected", "conditioned", "unconditioned", "survivors", "candidates", "fallbacks",
                 "depth_used")
 
     def __init__(self, blueprint, seat, replicas=32, threshold=0.0, seed=1, check_every=8, z=None, confirm_replicas=0,
-                 condition=False, oversample=8, depth=1, epsilon=None):
+                 condition=False, oversample=8, depth=1, epsilon=None, score_belief=False):
         self.blueprint = list(blueprint)
         self.seat = int(seat)
         if not 0 <= self.seat < len(self.blueprint):
@@ -1123,6 +1325,9 @@ class SearchPlayer:
             if self.replicas * self.oversample > MAX_SOFT_CANDIDATES:
                 raise ValueError(f"the soft filter takes at most {MAX_SOFT_CANDIDATES} candidates per root, got replicas * oversample = "
                                  f"{self.replicas * self.oversample}")
+        if not isinstance(score_belief, bool):
+            raise TypeError(f"score_belief is a switch (True or False), got {score_belief!r}")
+        self.score_belief = score_belief
         self._history = None   # depth > 1: the PartnerHistory of the env of the last call
         self._search = None
         self.last_result = None   # the SearchResult of the last call's first stage
@@ -1138,6 +1343,19 @@ class SearchPlayer:
         self.dead_replicas = self.replicas_drawn = self.searches = self.rollouts = 0
         self._by_depth = None   # depth > 1: [4, depth] int64 on the device, see depth_stats()
         self._ess = None        # epsilon: [2] float64 on the device, sum of ess and count over the conditioned roots
+        self._belief = None     # score_belief: [2, len(BeliefScore.SUMS), H] float64 on the device (conditioned roots, the others)
+
+    def belief_stats(self):
+        """score_belief: the first stage's beliefs against the real hands since reset_stats(), over every live root searched:
+        belief_figures' dict (`cards`, `roots`, `hit_rate`, `prior_rate`, `joint_rate`, `cross_entropy`, `prior_cross_entropy`,
+        `by_slot`). With condition=True it also holds the same dict for the `conditioned` roots (fallback != 2) and for the
+        `unconditioned` ones. All zeros before the first call (and without score_belief)."""
+        return belief_stats_of(self._belief, self.condition)
+
+    def belief_sums(self):
+        """score_belief: the sums behind belief_stats(), [2 (conditioned roots, the others), len(BeliefScore.SUMS), H] float64 on
+        the device (None before the first call): several players' sums add up, and `belief_stats_of` gives the figures."""
+        return self._belief
 
     def depth_stats(self):
         """depth > 1: sums over the first stage's conditioned roots since reset_stats(), one figure per D = 1 .. depth:
@@ -1206,7 +1424,8 @@ class SearchPlayer:
             raise ValueError(f"condition=True is built for 2 players, the env has {env.cfg.players}")
         if self._search is None or self._search.cfg.players != env.cfg.players:
             self._search = RolloutSearch(config=env.cfg, replicas=self.replicas, seed=self.seed, device=env.device,
-                                         check_every=self.check_every, oversample=self.oversample, epsilon=self.epsilon)
+                                         check_every=self.check_every, oversample=self.oversample, epsilon=self.epsilon,
+                                         score_belief=self.score_belief)
         rows = env.export_state()
         staged = self.z is not None or self.confirm_replicas > 0
         history = None
@@ -1219,6 +1438,10 @@ class SearchPlayer:
         res = self._search.run(rows, env.legal, self.blueprint, draw, seat=self.seat,
                                baseline=actions_out if self.z is not None else None, history=history)
         self.last_result = res
+        if res.belief is not None:   # (None: the switch is off, or no root was running)
+            filtered = res.fallback != 2 if self.condition and res.fallback is not None else torch.zeros_like(res.belief.scored)
+            sums = torch.stack([res.belief.sums(where=filtered), res.belief.sums(where=~filtered)])
+            self._belief = sums if self._belief is None else self._belief + sums
         live = running(rows)
         bp = actions_out.long().clamp(0, env.num_actions - 1).view(-1, 1)
         best = res.best.long().clamp(min=0).view(-1, 1)

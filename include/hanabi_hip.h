@@ -968,7 +968,23 @@ int hb_train_tally(const hb_config* cfg, int64_t n_games, int32_t seat, const in
  * integer scan per chunk on a running base, ballot and find-first; no atomics, no LDS, a pure function of the inputs.
  * 1 <= n_cand <= 4096 (weights below 2^28 and q <= 2^24 keep T below 2^64), replicas >= 1 (n_cand < replicas is allowed),
  * 1 <= depth <= 8, m * max(n_cand, replicas) * SW < 2^31.
- * All ten check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                      */
+ * hb_belief_score: a belief scored against the cards the seat really holds. true_rows_dev [m, SW] the real states, det_rows_dev
+ * [m * replicas, SW] / weight_dev [m * replicas] u32 replicas of them (replica r of root i = row i * replicas + r) from any of the
+ * samplers above, seat as hb_belief_determinize's (-1: each true row's current player). H = hand_size, NC = colors * ranks. Per
+ * root i whose true row is running and whose seat is < players, n = that seat's hand size in the TRUE row (word 1), slots s < n:
+ *   truth_dev [m, H] int8 = the 5-bit field of slot s of true word 10 + seat (the card id colour * ranks + rank);
+ *   counts_dev [m, H, NC] int64 (may be NULL: not written) = sum_r w_r [slot s of replica r's word 10 + seat == c];
+ *   hit_dev [m, H] int64 = sum_r w_r [slot s of replica r == truth[i, s] < NC] (= counts[i, s, truth]; computed either way);
+ *   joint_dev [m] int64 = sum_r w_r [every slot s < n of replica r equals the true one, and every one of those is < NC];
+ *   wsum_dev [m] int64 = sum_r w_r; n_live_dev [m] int32 = replicas with w_r != 0;
+ *   prior_dev [m, H, NC] int8 = the card-counting baseline from the true row alone: the copies of c in the seat's pool (its n hand
+ *   slots plus the undealt deck bytes, as hb_belief_determinize reads them) if slot s's knowledge bits allow c's colour and its
+ *   rank, else 0.
+ * Slots s >= n: truth -1, everything else 0. A root that is not running, or whose seat is >= players: truth -1 and zeros everywhere.
+ * A replica of weight 0 counts nothing (it is an unchanged copy of the true hand); a replica slot holding 31 or an id >= NC matches
+ * nothing. Integers only (every ratio is the host's), 64-bit sums: no order, bit-equal to hanabi_hip.search.belief_score_ref.
+ * 1 <= replicas <= 2^20 (wsum < 2^52), m < 2^31. One wavefront per root; no LDS, no atomics.
+ * All eleven check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                   */
 int hb_belief_determinize(const hb_config* cfg, const uint32_t* src_rows_dev, int64_t m, int32_t seat, int32_t replicas, uint64_t seed,
                           uint64_t draw, int64_t first_row_id, uint32_t* out_rows_dev, uint32_t* weight_dev, void* stream);
 int hb_search_reduce(const int8_t* score_dev, const uint32_t* weight_dev, const int8_t* legal_dev, int64_t m, int32_t n_actions,
@@ -999,6 +1015,9 @@ int hb_belief_history_step(const hb_config* cfg, int64_t m, int32_t depth, int32
                            const uint8_t* reset_dev, const uint32_t* cur_rows_dev, const uint32_t* prev_rows_dev,
                            uint32_t* hist_rows_dev, int32_t* hist_moves_dev, uint8_t* hist_alive_dev, uint8_t* hist_valid_dev,
                            void* stream);
+int hb_belief_score(const hb_config* cfg, const uint32_t* true_rows_dev, const uint32_t* det_rows_dev, const uint32_t* weight_dev,
+                    int64_t m, int32_t seat, int32_t replicas, int8_t* truth_dev, int64_t* hit_dev, int64_t* joint_dev,
+                    int64_t* wsum_dev, int32_t* n_live_dev, int64_t* counts_dev, int8_t* prior_dev, void* stream);
 
 /* ---- One host call per step: hb_chain_run (csrc/chain.hip, round 3) ------------------------------------------------------
  * The session that drives DQNAgent (rlax_rainbow.py:277-339: explore / add_experience / update once per env step) issues ~25
