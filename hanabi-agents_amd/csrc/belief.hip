@@ -36,6 +36,11 @@
 // valid flags) advanced by one turn in place: own move out of the alive masks, reset of re-dealt games, push of a new entry. One
 // launch; rows move as contiguous 16-byte items, the byte fields one game per lane (see the kernel).
 //
+// hb_belief_carry: the hand samples of my previous turn carried to my present one (range tracking, sampled): the card I played
+// leaves the sample, the others keep their slots if the pool and the hints since still allow them, the new card and the deck are
+// the determinizer's own draw, and the weight counts the copies of the card the partner drew. One wavefront per output row, like
+// hb_belief_determinize, with which it shares the slot draw and the deck shuffle. No LDS, barrier or atomic.
+//
 // hb_belief_score: any of these beliefs scored against the cards the seat really holds: per slot the weight of the replicas that
 // hold the true card (and, on request, of every card), the weight of those that hold the whole hand, and the card-counting prior
 // read from the true row alone. One wavefront per root, 64-bit integer sums, no float arithmetic; no LDS, barrier or atomic.
@@ -60,6 +65,52 @@ struct DetArgs {
 
 __device__ __forceinline__ uint32_t lane_read(uint32_t v, int l) {
   return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), l));
+}
+
+// One hand slot of the sequential importance sampler: `cand` marks this lane's pool element as free and plausible for the slot.
+// Returns n = the number of candidates (0: none, nothing is taken); otherwise the k-th candidate in pool order, k = (u * n) >> 32,
+// is marked in `taken` and its lane returned in idx.
+__device__ __forceinline__ uint32_t draw_slot(bool cand, uint32_t u, int lane, unsigned long long& taken, int& idx) {
+  const unsigned long long mask = __ballot(cand);
+  const uint32_t n = static_cast<uint32_t>(__popcll(mask));
+  idx = -1;
+  if (n == 0) return 0u;
+  const uint32_t k = static_cast<uint32_t>((static_cast<uint64_t>(u) * n) >> 32);
+  const uint32_t before = static_cast<uint32_t>(__popcll(mask & ((1ull << lane) - 1ull)));
+  idx = __ffsll(static_cast<unsigned long long>(__ballot(cand && before == k))) - 1;
+  taken |= 1ull << idx;
+  return n;
+}
+
+// The redrawn row: the pool elements not in `taken` go onto the undealt deck positions by the rank of a distinct random key
+// (element l: (v_l & ~63) | l), lane hand_lane's word becomes new_hand, every other word stays the source's (wj).
+__device__ __forceinline__ void store_redrawn(uint32_t wj, uint32_t card, uint32_t v, bool in_pool, unsigned long long taken, int lane,
+                                              int W_DECK, int deck_pos, int D, int SW, int hand_lane, uint32_t new_hand, uint32_t* dst) {
+  const unsigned long long rest = __ballot(in_pool && !((taken >> lane) & 1ull));
+  const uint32_t key = (v & ~63u) | static_cast<uint32_t>(lane);
+  int rank = 0;
+  for (unsigned long long todo = rest; todo; todo &= todo - 1) {
+    const uint32_t ki = lane_read(key, __ffsll(todo) - 1);
+    rank += ki < key ? 1 : 0;
+  }
+  const int dest = deck_pos + rank;   // (meaningful in the lanes of `rest`)
+  const int j = lane - W_DECK;   // deck word of this lane (bytes 4j .. 4j + 3), if 0 <= j < ceil(D / 4)
+  uint32_t neww = wj;
+  if (j >= 0 && 4 * j < D) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int p = 4 * j + b;
+      if (p >= deck_pos && p < D) neww &= ~(255u << (8 * b));
+    }
+  }
+  for (unsigned long long todo = rest; todo; todo &= todo - 1) {
+    const int l = __ffsll(todo) - 1;
+    const int d = static_cast<int>(lane_read(static_cast<uint32_t>(dest), l));
+    const uint32_t c = lane_read(card, l);
+    if ((d >> 2) == j) neww |= c << (8 * (d & 3));
+  }
+  if (lane == hand_lane) neww = new_hand;
+  if (lane < SW) dst[lane] = neww;
 }
 
 __global__ void __launch_bounds__(256) belief_determinize_kernel(DetArgs a) {
@@ -105,16 +156,12 @@ __global__ void __launch_bounds__(256) belief_determinize_kernel(DetArgs a) {
   for (int s = 0; s < n_hand; ++s) {
     const uint32_t kn = static_cast<uint32_t>(know >> (12 * s)) & 0xFFFu;
     const bool cand = card_ok && !((taken >> lane) & 1ull) && ((kn >> col) & 1u) && ((kn >> (5u + rk)) & 1u);
-    const unsigned long long mask = __ballot(cand);
-    const uint32_t n = static_cast<uint32_t>(__popcll(mask));
+    int idx;
+    const uint32_t n = draw_slot(cand, lane_read(rnd[0], s), lane, taken, idx);
     if (n == 0) {
       dead = true;
       break;
     }
-    const uint32_t k = static_cast<uint32_t>((static_cast<uint64_t>(lane_read(rnd[0], s)) * n) >> 32);
-    const uint32_t before = static_cast<uint32_t>(__popcll(mask & ((1ull << lane) - 1ull)));
-    const int idx = __ffsll(static_cast<unsigned long long>(__ballot(cand && before == k))) - 1;
-    taken |= 1ull << idx;
     weight *= n;
     new_hand = (new_hand & ~(31u << (5 * s))) | (lane_read(card, idx) << (5 * s));
   }
@@ -123,35 +170,115 @@ __global__ void __launch_bounds__(256) belief_determinize_kernel(DetArgs a) {
     if (lane == 0) a.weight[o] = 0u;
     return;
   }
+  store_redrawn(wj, card, rnd[1], in_pool, taken, lane, W_DECK, deck_pos, a.D, a.SW, 10 + seat, new_hand, dst);
+  if (lane == 0) a.weight[o] = weight;
+}
 
-  // ---- the rest of the pool onto the undealt deck positions: rank of a distinct random key ------------------------------------
-  const unsigned long long rest = __ballot(in_pool && !((taken >> lane) & 1ull));
-  const uint32_t key = (rnd[1] & ~63u) | static_cast<uint32_t>(lane);
-  int rank = 0;
-  for (unsigned long long todo = rest; todo; todo &= todo - 1) {
-    const uint32_t ki = lane_read(key, __ffsll(todo) - 1);
-    rank += ki < key ? 1 : 0;
-  }
-  const int dest = deck_pos + rank;   // (meaningful in the lanes of `rest`)
+struct CarryArgs {
+  const uint32_t* cur;
+  const uint32_t* old_rows;
+  const uint32_t* old_weight;
+  const int32_t* own_slot;
+  const int32_t* revealed;
+  const int32_t* drew;
+  uint32_t* out;
+  uint32_t* weight;
+  long long n_out, first_row;
+  unsigned long long seed, draw;
+  int K, seat, P, C, R, H, D, SW;
+};
 
-  // ---- the row: word 10 + seat = the new hand, the deck words' undealt bytes = the shuffled cards ------------------------------
-  const int j = lane - W_DECK;   // deck word of this lane (bytes 4j .. 4j + 3), if 0 <= j < ceil(D / 4)
-  uint32_t neww = wj;
-  if (j >= 0 && 4 * j < a.D) {
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int p = 4 * j + b;
-      if (p >= deck_pos && p < a.D) neww &= ~(255u << (8 * b));
+// hb_belief_carry: particle (i, k) of my previous turn carried to my present one (the rule is in include/hanabi_hip.h). One
+// wavefront per output row, laid out like belief_determinize_kernel: lane j < SW holds word j of cur row i, lane l < npool pool
+// element l. The kept cards take their pool elements by ballot and find-first, the new slots and the deck are the determinizer's
+// own steps with its Philox words. Every decision is wave-uniform; no LDS, no atomics.
+__global__ void __launch_bounds__(256) belief_carry_kernel(CarryArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long long o = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);   // output row of this wavefront
+  if (o >= a.n_out) return;
+  const long long i = o / a.K;
+  const uint32_t wj = lane < a.SW ? a.cur[i * a.SW + lane] : 0u;
+  uint32_t* const dst = a.out + o * a.SW;
+  const uint32_t w0 = lane_read(wj, 0), w1 = lane_read(wj, 1);
+  const int seat = a.seat;
+  const uint32_t old_hand = a.old_rows[o * a.SW + 10 + seat];
+  const int slot = a.own_slot[i], drw = a.drew[i];
+  const uint32_t rev = static_cast<uint32_t>(a.revealed[i]);
+  const int W_DECK = 10 + 3 * a.P;
+  const uint32_t hand = lane_read(wj, 10 + seat);
+  const uint64_t know = (static_cast<uint64_t>(lane_read(wj, 10 + a.P + 2 * seat + 1)) << 32) | lane_read(wj, 10 + a.P + 2 * seat);
+  const int n_hand = min(static_cast<int>((w1 >> (15 + 3 * seat)) & 7u), a.H);
+  const int deck_size = min(static_cast<int>(w0 & 63u), a.D);
+  const int deck_pos = a.D - deck_size;
+  const int npool = n_hand + deck_size;
+
+  // ---- steps 1 and 2: usable at all; the card I played leaves the old hand, the others are kept oldest first ------------------
+  bool dead = a.old_weight[o] == 0u || ((w0 >> 19) & 3u) != 0 || static_cast<int>((w0 >> 13) & 7u) != seat;
+  if (slot >= 0) dead = dead || slot >= a.H || ((old_hand >> (5 * min(slot, 4))) & 31u) != rev;
+  uint32_t kept = 0;
+  int n_kept = 0;
+  for (int s = 0; s < a.H; ++s) {
+    const uint32_t f = (old_hand >> (5 * s)) & 31u;
+    if (s != slot && f != 31u) {
+      kept |= f << (5 * n_kept);
+      ++n_kept;
     }
   }
-  for (unsigned long long todo = rest; todo; todo &= todo - 1) {
-    const int l = __ffsll(todo) - 1;
-    const int d = static_cast<int>(lane_read(static_cast<uint32_t>(dest), l));
-    const uint32_t c = lane_read(card, l);
-    if ((d >> 2) == j) neww |= c << (8 * (d & 3));
+  dead = dead || n_kept > n_hand;
+
+  // ---- step 3: the pool element of this lane, as in belief_determinize_kernel ---------------------------------------------------
+  const int q = deck_pos + lane - n_hand;
+  const uint32_t wq = static_cast<uint32_t>(__shfl(static_cast<int>(wj), (W_DECK + (q >> 2)) & 63));
+  const uint32_t card = lane < n_hand ? (hand >> (5 * lane)) & 31u : (wq >> (8 * (q & 3))) & 255u;
+  const bool in_pool = lane < npool;
+  const uint32_t col = card / static_cast<uint32_t>(a.R), rk = card - col * static_cast<uint32_t>(a.R);
+  const bool card_ok = in_pool && col < static_cast<uint32_t>(a.C);
+
+  unsigned long long taken = 0;
+  uint32_t weight = 1u, new_hand = hand;
+  // ---- step 4: kept slot s takes the first free pool element of its card, if the slot's knowledge now allows that card ---------
+  for (int s = 0; s < n_kept && !dead; ++s) {
+    const uint32_t c = (kept >> (5 * s)) & 31u;
+    const uint32_t kn = static_cast<uint32_t>(know >> (12 * s)) & 0xFFFu;
+    const uint32_t cc = c / static_cast<uint32_t>(a.R), cr = c - cc * static_cast<uint32_t>(a.R);
+    const bool allowed = cc < static_cast<uint32_t>(a.C) && ((kn >> cc) & 1u) && ((kn >> (5u + cr)) & 1u);
+    const unsigned long long mask = __ballot(in_pool && !((taken >> lane) & 1ull) && card == c);
+    if (!allowed || mask == 0) {
+      dead = true;
+      break;
+    }
+    taken |= 1ull << (__ffsll(mask) - 1);
+    new_hand = (new_hand & ~(31u << (5 * s))) | (c << (5 * s));
   }
-  if (lane == 10 + seat) neww = new_hand;
-  if (lane < a.SW) dst[lane] = neww;
+  // ---- step 5: the partner's visible draw: its copies still in the hypothesis's pool, plus the one the partner took ------------
+  if (!dead && drw >= 0)
+    weight += static_cast<uint32_t>(__popcll(__ballot(in_pool && !((taken >> lane) & 1ull) && card == static_cast<uint32_t>(drw))));
+
+  // ---- step 6: the new slots, the determinizer's step with the determinizer's random words -------------------------------------
+  const unsigned long long row_id = static_cast<unsigned long long>(a.first_row + o);
+  uint32_t rnd[4];
+  hb::philox4x32_10(128u + static_cast<uint32_t>(lane), static_cast<uint32_t>(a.draw), static_cast<uint32_t>(row_id),
+                    static_cast<uint32_t>(row_id >> 32), static_cast<uint32_t>(a.seed),
+                    static_cast<uint32_t>(a.seed >> 32) ^ static_cast<uint32_t>(a.draw >> 32), rnd);
+  for (int s = n_kept; s < n_hand && !dead; ++s) {
+    const uint32_t kn = static_cast<uint32_t>(know >> (12 * s)) & 0xFFFu;
+    const bool cand = card_ok && !((taken >> lane) & 1ull) && ((kn >> col) & 1u) && ((kn >> (5u + rk)) & 1u);
+    int idx;
+    const uint32_t n = draw_slot(cand, lane_read(rnd[0], s), lane, taken, idx);
+    if (n == 0) {
+      dead = true;
+      break;
+    }
+    weight *= n;
+    new_hand = (new_hand & ~(31u << (5 * s))) | (lane_read(card, idx) << (5 * s));
+  }
+  if (dead) {
+    if (lane < a.SW) dst[lane] = wj;
+    if (lane == 0) a.weight[o] = 0u;
+    return;
+  }
+  // ---- steps 7 and 8 ---------------------------------------------------------------------------------------------------------------
+  store_redrawn(wj, card, rnd[1], in_pool, taken, lane, W_DECK, deck_pos, a.D, a.SW, 10 + seat, new_hand, dst);
   if (lane == 0) a.weight[o] = weight;
 }
 
@@ -907,6 +1034,39 @@ extern "C" int hb_belief_determinize(const hb_config* cfg, const uint32_t* src_r
   a.SW = hb_state_words(cfg);
   const unsigned blocks = static_cast<unsigned>((a.n_out + 3) / 4);   // four wavefronts = four output rows per workgroup
   hipLaunchKernelGGL(belief_determinize_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}
+
+extern "C" int hb_belief_carry(const hb_config* cfg, const uint32_t* cur_rows_dev, const uint32_t* old_rows_dev,
+                               const uint32_t* old_weight_dev, const int32_t* own_slot_dev, const int32_t* revealed_dev,
+                               const int32_t* drew_dev, int64_t m, int32_t seat, int32_t n_particles, uint64_t seed, uint64_t draw,
+                               int64_t first_row_id, uint32_t* out_rows_dev, uint32_t* out_weight_dev, void* stream) {
+  if (!cfg) return hb::fail(HB_ERR_INVALID, "null config");
+  if (int rc = hb_config_validate(cfg)) return rc;
+  if (m < 0) return hb::fail(HB_ERR_INVALID, "m must be >= 0");
+  if (n_particles < 1) return hb::fail(HB_ERR_INVALID, "n_particles must be >= 1, got %d", n_particles);
+  if (seat < 0 || seat >= cfg->players)
+    return hb::fail(HB_ERR_INVALID, "seat %d out of range 0..%d (the observer, who is to act)", seat, cfg->players - 1);
+  if (!cur_rows_dev || !old_rows_dev || !old_weight_dev || !own_slot_dev || !revealed_dev || !drew_dev || !out_rows_dev || !out_weight_dev)
+    return hb::fail(HB_ERR_INVALID, "null argument");
+  if (m > (static_cast<int64_t>(1) << 31) / n_particles - 1)
+    return hb::fail(HB_ERR_INVALID, "m * n_particles must stay below 2^31 output rows: split the call (first_row_id)");
+  if (m == 0) return HB_OK;
+  if (int rc = have_device()) return rc;
+  CarryArgs a{};
+  a.cur = cur_rows_dev; a.old_rows = old_rows_dev; a.old_weight = old_weight_dev;
+  a.own_slot = own_slot_dev; a.revealed = revealed_dev; a.drew = drew_dev;
+  a.out = out_rows_dev; a.weight = out_weight_dev;
+  a.n_out = m * n_particles;
+  a.first_row = first_row_id;
+  a.seed = seed; a.draw = draw;
+  a.K = n_particles; a.seat = seat;
+  a.P = cfg->players; a.C = cfg->colors; a.R = cfg->ranks; a.H = cfg->hand_size;
+  a.D = hb_deck_size(cfg);
+  a.SW = hb_state_words(cfg);
+  const unsigned blocks = static_cast<unsigned>((a.n_out + 3) / 4);   // four wavefronts = four output rows per workgroup
+  hipLaunchKernelGGL(belief_carry_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   HB_HIP(hipGetLastError());
   return HB_OK;
 }

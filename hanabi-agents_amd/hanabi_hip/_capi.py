@@ -217,6 +217,7 @@ SIGNATURES = {
                                         _P, _P, _P]),
     "hb_belief_history_step": (C.c_int, [_CFG, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hb_belief_score": (C.c_int, [_CFG, _P, _P, _P, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "hb_belief_carry": (C.c_int, [_CFG, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _U64, _U64, _I64, _P, _P, _P]),
     "hb_relu_bwd_colsum": (C.c_int, [_P, _P, _I64, _I32, _I64, _I64, _P, _P]),
     "hb_replay_insert": (C.c_int, [_P] * 12 + [_I64, _I32, _I32, _I64, _I64, _P]),
     "hb_obl_insert": (C.c_int, [_P] * 12 + [_I64, _I32, _I32, _I32, _I64, _I64, _P]),

@@ -38,6 +38,10 @@
   seat really holds: per slot the weight of the replicas that hold the true card, for the whole hand, and next to the card-counting
   prior, in exact integers; `BeliefScore` forms the hit rates and cross-entropies. `score_belief=True` (`RolloutSearch`,
   `SearchPlayer`; default False: nothing is computed) scores every search's replicas; `SearchPlayer.belief_stats()` gives the means.
+* `TrackedBelief` (`SearchPlayer(condition=True, track=True)`, 2 players) tracks the belief across turns instead of rebuilding it:
+  the hand samples of my last turn are carried to this one (hb_belief_carry; `belief_carry`, `belief_carry_ref` its numpy
+  restatement), weighed by the one move the partner has made since and resampled (hb_belief_select_soft); a root whose samples run
+  out starts over from the conditioned belief above.
 * `SearchPlayer` is an agent for `Evaluator.run`: the blueprint's move unless the search finds one that is better by more than
   `threshold` and, with `z` / `confirm_replicas`, by more than z standard errors of the paired difference.
 
@@ -352,6 +356,125 @@ def belief_select_soft_ref(src_rows, det_rows, weights, hyp_moves, n_legal, actu
         ow[i * R:(i + 1) * R] = 1
     out = (rows, ow, n_surv, L, np.where(L == 0, 2, 0).astype(np.uint8), ess)
     return out + (dict(lik=lik, q=q, W=W, T=T, target=target, pick=pick),) if details else out
+
+
+def belief_carry(cfg, cur_rows, old_rows, old_weights, own_slot, revealed, drew, seat, n_particles, seed, draw, first_row_id=0,
+                 out=None):
+    """hb_belief_carry: the hand samples of my previous turn carried to my present one (include/hanabi_hip.h has the rule).
+    cur_rows [m, SW] int32 the states now (`seat`, the observer, to act), old_rows [m * K, SW] int32 / old_weights [m * K] (u32
+    bits in int32) the K = n_particles particles of each root at my previous turn (only the observer's hand word is read, and
+    whether the weight is 0), own_slot [m] int32 the slot I played or discarded then (-1: a hint), revealed [m] int32 the card
+    that turned face up (-1: none), drew [m] int32 the card the partner has visibly drawn since (-1: none) -> (rows [m * K, SW]
+    int32, weights [m * K] int32). `out`: an optional pair of these two buffers to write into. GPU only."""
+    cur = torch.as_tensor(cur_rows)
+    if cur.dim() != 2:
+        raise ValueError(f"cur_rows has shape [m, state_words], got {tuple(cur.shape)}")
+    m, SW = cur.shape
+    Kn, dev = int(n_particles), cur.device
+    if Kn < 1:
+        raise ValueError(f"n_particles must be >= 1, got {n_particles}")
+    if not 0 <= int(seat) < cfg.players:
+        raise ValueError(f"seat {seat} out of range for {cfg.players} players (the observer, who is to act)")
+    n = m * Kn
+    _bufs(dev, (cur, old_rows, old_weights, own_slot, revealed, drew), ((m, SW), torch.int32), ((n, SW), torch.int32), ((n,), torch.int32),
+          ((m,), torch.int32), ((m,), torch.int32), ((m,), torch.int32))
+    for t in (cur, old_rows, old_weights, own_slot, revealed, drew):
+        if not t.is_cuda or t.device != dev:
+            raise K.HbError("hb_belief_carry reads tensors of one GPU (there is no CPU path)")
+    rows, w = _bufs(dev, out, ((n, SW), torch.int32), ((n,), torch.int32))
+    with torch.cuda.device(dev):
+        K.check(K.lib().hb_belief_carry(C.byref(cfg), K.dptr(cur), K.dptr(old_rows), K.dptr(old_weights), K.dptr(own_slot),
+                                        K.dptr(revealed), K.dptr(drew), m, int(seat), Kn, int(seed) & _M64, int(draw) & _M64,
+                                        int(first_row_id), K.dptr(rows), K.dptr(w), K.current_stream()))
+    return rows, w
+
+
+def belief_carry_ref(cfg, cur_rows, old_rows, old_weights, own_slot, revealed, drew, seat, n_particles, seed, draw, first_row_id=0,
+                     draw_weight=True, details=False):
+    """hb_belief_carry restated in numpy, particle by particle in plain loops over Python lists (nothing of the kernel's layout):
+    arrays shaped as belief_carry's tensors (32-bit words of either sign) -> (rows uint32 [m * K, SW], weights uint32 [m * K]).
+    draw_weight=False is the deliberately wrong variant with g = 1 (step 5 left out) that the tests hold against the right one.
+    details=True appends a list with one dict per particle: `dead` (the step that killed it, or 0), `kept`, `g`, `ns`. Runs
+    without a GPU."""
+    import numpy as np
+
+    u32 = lambda x: (np.asarray(x).astype(np.int64) & _M32).astype(np.uint32)
+    cur, old = u32(cur_rows), u32(old_rows)
+    (m, SW), Kn, st = cur.shape, int(n_particles), int(seat)
+    ow = u32(old_weights)
+    slot_a, rev_a, drew_a = (np.asarray(x).astype(np.int64) for x in (own_slot, revealed, drew))
+    assert old.shape == (m * Kn, SW) and ow.shape == (m * Kn,) and slot_a.shape == rev_a.shape == drew_a.shape == (m,)
+    P, H, Rk, Cn = cfg.players, cfg.hand_size, cfg.ranks, cfg.colors
+    assert 0 <= st < P
+    D = Cn * sum(3 if r == 0 else 1 if r == Rk - 1 else 2 for r in range(Rk))
+    seed, draw = int(seed) & _M64, int(draw) & _M64
+    rows, w, info = np.empty((m * Kn, SW), np.uint32), np.zeros(m * Kn, np.uint32), []
+
+    def allows(kn, c):
+        return c // Rk < Cn and bool((kn >> (c // Rk)) & 1) and bool((kn >> (5 + c % Rk)) & 1)
+
+    for o in range(m * Kn):
+        i = o // Kn
+        rows[o] = cur[i]
+        note = dict(dead=0, kept=[], g=1, ns=[])
+        info.append(note)
+        w0, w1 = int(cur[i, 0]), int(cur[i, 1])
+        if ow[o] == 0 or (w0 >> 19) & 3 != 0 or (w0 >> 13) & 7 != st:   # 1. not usable
+            note["dead"] = 1
+            continue
+        old_hand, slot = int(old[o, 10 + st]), int(slot_a[i])
+        fields = [(old_hand >> (5 * s)) & 31 for s in range(H)]
+        if slot >= 0 and (slot >= H or fields[slot] != int(rev_a[i])):   # 2. the card I played is not the one that was seen
+            note["dead"] = 2
+            continue
+        kept = note["kept"] = [f for s, f in enumerate(fields) if s != slot and f != 31]
+        n_hand = min((w1 >> (15 + 3 * st)) & 7, H)
+        if len(kept) > n_hand:
+            note["dead"] = 2
+            continue
+        hand = int(cur[i, 10 + st])
+        know = int(cur[i, 10 + P + 2 * st]) | int(cur[i, 10 + P + 2 * st + 1]) << 32
+        deck_pos = D - min(w0 & 63, D)
+        deck = np.ascontiguousarray(cur[i, 10 + 3 * P:], dtype="<u4").view(np.uint8)
+        pool = [(hand >> (5 * l)) & 31 for l in range(n_hand)] + [int(deck[q]) for q in range(deck_pos, D)]   # 3.
+        free = [True] * len(pool)
+        new_hand = hand
+        for s, c in enumerate(kept):   # 4. the kept cards, where they now sit
+            where = [l for l in range(len(pool)) if free[l] and pool[l] == c]
+            if not where or not allows((know >> (12 * s)) & 0xFFF, c):
+                note["dead"] = 4
+                break
+            free[where[0]] = False
+            new_hand = (new_hand & ~(31 << (5 * s))) | (c << (5 * s))
+        if note["dead"]:
+            continue
+        g = 1
+        if draw_weight and int(drew_a[i]) >= 0:   # 5. the partner's draw
+            g += sum(1 for l in range(len(pool)) if free[l] and pool[l] == int(drew_a[i]))
+        note["g"] = g
+        rid = (int(first_row_id) + o) & _M64
+        rnd = _philox_np(128 + np.arange(64), draw & _M32, rid & _M32, rid >> 32, seed & _M32, ((seed >> 32) ^ (draw >> 32)) & _M32)
+        weight = g
+        for s in range(len(kept), n_hand):   # 6. the new slots: the determinizer's step
+            kn = (know >> (12 * s)) & 0xFFF
+            cand = [l for l in range(len(pool)) if free[l] and allows(kn, pool[l])]
+            note["ns"].append(len(cand))
+            if not cand:
+                note["dead"] = 6
+                break
+            pick = cand[(int(rnd[0][s]) * len(cand)) >> 32]
+            free[pick] = False
+            weight *= len(cand)
+            new_hand = (new_hand & ~(31 << (5 * s))) | (pool[pick] << (5 * s))
+        if note["dead"]:
+            continue
+        rest = sorted((l for l in range(len(pool)) if free[l]), key=lambda l: (int(rnd[1][l]) & ~63) | l)   # 7. the deck
+        rows[o, 10 + st] = new_hand
+        bytes_out = rows[o, 10 + 3 * P:].view(np.uint8)
+        for j, l in enumerate(rest):
+            bytes_out[deck_pos + j] = pool[l]
+        w[o] = weight & _M32
+    return (rows, w, info) if details else (rows, w)
 
 
 def belief_score(cfg, true_rows, det_rows, weights, seat, replicas, counts=False, out=None):
@@ -791,6 +914,27 @@ class ConditionedDeterminizer:
             encode_rows(self.cfg, b["hyp_rows"][k], out=(obs[k, :m], legal[k, :m]))
         return obs[:, :m], legal[:, :m]
 
+    def _slab_moves(self, b, partner, m, Kn, dev, partner_seed, partner_draw, moves, nleg):
+        """The partner's eval_moves with (partner_seed, partner_draw) on the Kn slabs of b["hyp_rows"] -> moves [Kn, m] int32 and,
+        where nleg [Kn, m] int32 is given, the number of legal moves it was shown in each. The stateless path where the partner
+        allows it (_slab_views), else one import and observe of the scratch env per slab (its first_game_id set by the caller)."""
+        env = b["env"]
+        vec = partner.requires_vectorized_observation()
+        slabs = self._slab_views(b, partner, m, Kn, dev)
+        if slabs is not None and nleg is not None:
+            torch.sum(slabs[1], dim=-1, dtype=torch.int32, out=nleg)
+        for k in range(Kn):
+            if slabs is not None:
+                partner.eval_moves((None, (slabs[0][k], slabs[1][k])), int(partner_seed), int(partner_draw), moves[k],
+                                   scratch=self._scratch.setdefault(partner, {}))
+                continue
+            env.import_state(b["hyp_rows"][k])
+            if vec or nleg is not None:   # import_state moves the rows only: the seat's observation and legal mask are encoded here
+                env.observe()
+            if nleg is not None:
+                torch.sum(env.legal, dim=1, dtype=torch.int32, out=nleg[k])
+            _ask(partner, env, int(partner_seed), int(partner_draw), moves[k], self._scratch)
+
     @torch.no_grad()
     def sample(self, rows, prev_rows, partner, seat, replicas, oversample, seed, draw, partner_seed, partner_draw, first_game_id,
                valid=None, first_row_id=0, out=None, epsilon=None):
@@ -826,21 +970,7 @@ class ConditionedDeterminizer:
                             out=(b["cand_rows"], b["cand_w"]))
             belief_splice(self.cfg, prev, b["cand_rows"], int(seat), Kn, out=b["hyp_rows"])
             env.first_game_id = int(first_game_id)   # (the scratch env never deals: its game ids key the partner's draws only)
-            vec = partner.requires_vectorized_observation()
-            slabs = self._slab_views(b, partner, m, Kn, dev)
-            if slabs is not None and nleg is not None:
-                torch.sum(slabs[1], dim=-1, dtype=torch.int32, out=nleg[0])
-            for k in range(Kn):
-                if slabs is not None:
-                    partner.eval_moves((None, (slabs[0][k], slabs[1][k])), int(partner_seed), int(partner_draw), b["hyp_moves"][k],
-                                       scratch=self._scratch.setdefault(partner, {}))
-                    continue
-                env.import_state(b["hyp_rows"][k])
-                if vec or nleg is not None:   # import_state moves the rows only: the seat's observation and legal mask are encoded here
-                    env.observe()
-                if nleg is not None:
-                    torch.sum(env.legal, dim=1, dtype=torch.int32, out=nleg[0, k])
-                _ask(partner, env, int(partner_seed), int(partner_draw), b["hyp_moves"][k], self._scratch)
+            self._slab_moves(b, partner, m, Kn, dev, partner_seed, partner_draw, b["hyp_moves"], None if nleg is None else nleg[0])
             if epsilon is not None:
                 res = belief_select_soft(self.cfg, r, b["cand_rows"], b["cand_w"], b["hyp_moves"].view(1, Kn, m), nleg,
                                          last_move_uid(self.cfg, r).view(1, m), usable.to(torch.uint8).view(1, m), table, R, seed, draw,
@@ -893,24 +1023,10 @@ class ConditionedDeterminizer:
             self.det.sample(r, seat=int(seat), replicas=Kn, seed=seed, draw=draw, first_row_id=first_row_id,
                             out=(b["cand_rows"], b["cand_w"]))
             env.first_game_id = int(first_game_id)
-            vec = partner.requires_vectorized_observation()
             for d in range(min(D, history.filled)):
                 prev = torch.where((chain[d] != 0).view(m, 1), history.prev_rows[d], r).contiguous()
                 belief_splice_alive(self.cfg, prev, history.alive[d].contiguous(), b["cand_rows"], int(seat), Kn, out=b["hyp_rows"])
-                slabs = self._slab_views(b, partner, m, Kn, dev)
-                if slabs is not None and nleg is not None:
-                    torch.sum(slabs[1], dim=-1, dtype=torch.int32, out=nleg[d])
-                for k in range(Kn):
-                    if slabs is not None:
-                        partner.eval_moves((None, (slabs[0][k], slabs[1][k])), int(partner_seed), int(history.draws[d]), hyp[d, k],
-                                           scratch=self._scratch.setdefault(partner, {}))
-                        continue
-                    env.import_state(b["hyp_rows"][k])
-                    if vec or nleg is not None:
-                        env.observe()
-                    if nleg is not None:
-                        torch.sum(env.legal, dim=1, dtype=torch.int32, out=nleg[d, k])
-                    _ask(partner, env, int(partner_seed), int(history.draws[d]), hyp[d, k], self._scratch)
+                self._slab_moves(b, partner, m, Kn, dev, partner_seed, history.draws[d], hyp[d], None if nleg is None else nleg[d])
             if epsilon is not None:
                 res = belief_select_soft(self.cfg, r, b["cand_rows"], b["cand_w"], hyp, nleg, history.moves.contiguous(), chain, table, R,
                                          seed, draw, first_row_id=first_row_id,
@@ -923,6 +1039,184 @@ class ConditionedDeterminizer:
         if out is not None:
             return res
         return res[0], res[1].long() & 0xFFFFFFFF, res[2], res[3], res[4]
+
+
+def exact_table(n_actions, device=None):
+    """soft_table's layout for a partner that never leaves its policy: [2, A + 1] float64, row 0 all 1 (the move is the policy's),
+    row 1 all 0 (it is not), column 0 zero. hb_belief_select_soft with this table is the exact filter on weighted candidates."""
+    A = int(n_actions)
+    if A < 1:
+        raise ValueError(f"n_actions must be >= 1, got {n_actions}")
+    t = torch.tensor([[0.0] + [1.0] * A, [0.0] * (A + 1)], dtype=torch.float64)
+    return t if device is None else t.to(device)
+
+
+class TrackedRows:
+    """What `TrackedBelief.step` hands to RolloutSearch as `history`: rows [m * K, SW] int32 / weights [m * K] int32, the K
+    equally weighted particles of each root (weight 0: dead), of which a search of R replicas takes particles start .. start + R
+    - 1; and per root n_surv [m] int32, fallback [m] uint8, depth_used [m] int32, ess [m] float32 (as SearchResult's), tracked /
+    restarted [m] bool and carried_live [m] int32 (the live particles after the carry)."""
+
+    def __init__(self, rows, weights, n_particles, n_surv, fallback, depth_used, ess, tracked, restarted, carried_live, start=0):
+        self.rows, self.weights, self.n_particles, self.start = rows, weights, int(n_particles), int(start)
+        self.n_surv, self.fallback, self.depth_used, self.ess = n_surv, fallback, depth_used, ess
+        self.tracked, self.restarted, self.carried_live = tracked, restarted, carried_live
+
+    def shifted(self, by):
+        """The same particles, read from `by` places further on (a confirming stage: particles the first stage did not see)."""
+        return TrackedRows(self.rows, self.weights, self.n_particles, self.n_surv, self.fallback, self.depth_used, self.ess,
+                           self.tracked, self.restarted, self.carried_live, start=self.start + int(by))
+
+    def take(self, m, R, out):
+        """Particles start .. start + R - 1 of each of the m roots -> out = (rows [m * R, SW], weights [m * R])."""
+        Kn, SW = self.n_particles, self.rows.shape[1]
+        if self.rows.shape[0] != m * Kn:
+            raise ValueError(f"the tracked belief holds {self.rows.shape[0]} rows, the search has {m} roots of {Kn} particles")
+        if self.start + R > Kn:
+            raise ValueError(f"the tracked belief holds {Kn} particles per root, particles {self.start}..{self.start + R - 1} were asked for")
+        out[0].view(m, R, SW).copy_(self.rows.view(m, Kn, SW)[:, self.start:self.start + R])
+        out[1].view(m, R).copy_(self.weights.view(m, Kn)[:, self.start:self.start + R])
+
+
+class TrackedBelief:
+    """The search belief tracked across turns, 2 players ("Tracking the belief"): per root the K = replicas *
+    oversample hand samples of the observer's last turn are kept, carried to the present turn (hb_belief_carry: the card I played
+    leaves, the others stay if the pool and the hints since allow them, the new card and the deck are drawn afresh, the weight
+    counts the copies of the card the partner drew), spliced into the state the partner moved from (hb_belief_splice), weighed
+    by the likelihood of the ONE move the partner has made since (its eval_moves on the K slabs, `ConditionedDeterminizer`'s slab
+    code) and resampled to K equally weighted particles (hb_belief_select_soft with replicas = K). The first `replicas` of them
+    are the search's replicas: the draws are exchangeable.
+
+    A root STARTS OVER when it has no particle set yet, when its previous turn is not usable, or when its resampling total is 0
+    (no carried particle explains what was seen): it takes K rows from `ConditionedDeterminizer.sample_history` (a PartnerHistory
+    given) or `.sample` (none), with the caller's epsilon, K candidates. That path runs only when some root needs it (one host
+    synchronisation per step decides). A restart is normal — a first move, a partner that explores — and only counted."""
+
+    def __init__(self, game="Hanabi-Full", players=2, config=None, replicas=32, oversample=8, cdet=None):
+        self.cdet = cdet if cdet is not None else ConditionedDeterminizer(game, players, config)
+        self.cfg, self.state_words = self.cdet.cfg, self.cdet.state_words
+        if self.cfg.players != 2:
+            raise ValueError(f"track=True is built for 2 players, got {self.cfg.players}")
+        self.replicas, self.oversample = int(replicas), int(oversample)
+        if self.replicas < 1 or self.oversample < 1:
+            raise ValueError(f"replicas and oversample must be >= 1, got {replicas} and {oversample}")
+        self.n_particles = self.replicas * self.oversample
+        if self.n_particles > MAX_SOFT_CANDIDATES:
+            raise ValueError(f"the soft filter takes at most {MAX_SOFT_CANDIDATES} candidates per root, got replicas * oversample = "
+                             f"{self.n_particles}")
+        self.num_actions = K.lib().hb_num_actions(C.byref(self.cfg))
+        self.rows = self.weights = self.have = None   # [m * K, SW] int32, [m * K] int32, [m] bool: the particle sets
+        self._tables, self._nleg = {}, None
+
+    def clear(self):
+        """Forget every particle set: the next step starts every root over."""
+        if self.have is not None:
+            self.have.zero_()
+
+    def observed(self, rows, then_rows, then_moves, prev_rows, seat):
+        """What has become public between my last turn and now, on the device, no host synchronisation -> (own_slot, revealed,
+        drew) [m] int32 as hb_belief_carry reads them. own_slot: the slot of then_moves where that is a discard or a play;
+        revealed: the card word 2 of prev_rows (then_rows stepped with my move) names, where it records a discard or a play of
+        mine; drew: the partner's newest hand slot in `rows`, where word 2 of `rows` records a discard or a play of the partner's
+        and its hand is as large as in prev_rows."""
+        H, Rk, st, pt = self.cfg.hand_size, self.cfg.ranks, int(seat), 1 - int(seat)
+        mv = then_moves.long()
+        own_slot = torch.where((mv >= 0) & (mv < 2 * H), mv % H, -1)
+        w2 = prev_rows[:, 2].long() & 0xFFFFFFFF
+        mine = ((w2 & 1) != 0) & (((w2 >> 1) & 7) == st) & (((w2 >> 4) & 3) < 2)
+        revealed = torch.where(mine & (own_slot >= 0), ((w2 >> 12) & 7) * Rk + ((w2 >> 15) & 7), -1)
+        c2 = rows[:, 2].long() & 0xFFFFFFFF
+        size = lambda r: (r[:, 1].long() >> (15 + 3 * pt)) & 7
+        n_now = size(rows)
+        took = ((c2 & 1) != 0) & (((c2 >> 1) & 7) == pt) & (((c2 >> 4) & 3) < 2) & (n_now == size(prev_rows)) & (n_now >= 1)
+        newest = ((rows[:, 10 + pt].long() & 0xFFFFFFFF) >> (5 * (n_now - 1).clamp(min=0))) & 31
+        drew = torch.where(took, newest, -1)
+        return own_slot.int().contiguous(), revealed.int().contiguous(), drew.int().contiguous()
+
+    def _table(self, epsilon, dev):
+        key = (None if epsilon is None else float(epsilon), dev)
+        if key not in self._tables:
+            self._tables[key] = (exact_table if epsilon is None else lambda A, device: soft_table(epsilon, A, device=device))(
+                self.num_actions, device=dev)
+        return self._tables[key]
+
+    @torch.no_grad()
+    def step(self, rows, then_rows, then_moves, prev_rows, valid, partner, seat, seed, draw, partner_seed, partner_draw, first_game_id,
+             epsilon=None, history=None, first_row_id=0):
+        """One turn. rows [m, SW] the states now (`seat` to act); then_rows [m, SW] / then_moves [m] my last turn and the moves I
+        played there (None: there is none, every root starts over); prev_rows [m, SW] / valid [m] the states the partner moved
+        from and where that is usable (SearchPlayer._previous); partner: the agent that moved, called with (partner_seed,
+        partner_draw) on games first_game_id + i; (seed, draw, first_row_id) key the carry's and the resampling's draws; epsilon:
+        the partner read as epsilon-greedy (None: the exact filter, `exact_table`); history: the PartnerHistory a root that starts
+        over is conditioned on (None: prev_rows alone). -> `TrackedRows`; the particle sets are replaced."""
+        r = _rows(rows, self.state_words)
+        m, Kn, SW, dev = r.shape[0], self.n_particles, self.state_words, r.device
+        if not 0 <= int(seat) < 2:
+            raise ValueError(f"seat {seat} out of range for 2 players")
+        if not hasattr(partner, "eval_moves"):
+            raise TypeError(f"{type(partner).__name__} has no eval_moves()")
+        prev, _, _, _, valid = _history((prev_rows, 0, 0, 0, valid), m, SW, dev)
+        if self.rows is None or self.rows.shape[0] != m * Kn or self.rows.device != dev:
+            self.rows = torch.zeros((m * Kn, SW), dtype=torch.int32, device=dev)
+            self.weights = torch.zeros(m * Kn, dtype=torch.int32, device=dev)
+            self.have = torch.zeros(m, dtype=torch.bool, device=dev)
+            self._next = (torch.empty_like(self.rows), torch.empty_like(self.weights))
+            self._nleg = torch.ones((1, Kn, m), dtype=torch.int32, device=dev)
+        cd = self.cdet
+        b = cd._setup(m, Kn, dev)
+        with torch.cuda.device(dev):
+            live = running(r)
+            usable = live & self.have if valid is None else live & self.have & (valid != 0)
+            if then_rows is None:
+                usable = torch.zeros_like(usable)
+                own_slot = revealed = drew = torch.full((m,), -1, dtype=torch.int32, device=dev)
+            else:
+                then = _rows(then_rows, SW, dev)
+                own_slot, revealed, drew = self.observed(r, then, torch.as_tensor(then_moves).to(dev).view(m), prev, seat)
+            old_w = torch.where(usable.view(m, 1), self.weights.view(m, Kn), 0).view(-1)
+            belief_carry(self.cfg, r, self.rows, old_w, own_slot, revealed, drew, seat, Kn, seed, draw, first_row_id=first_row_id,
+                         out=(b["cand_rows"], b["cand_w"]))
+            carried_live = (b["cand_w"].view(m, Kn) != 0).sum(1).int()
+            # a root that cannot be carried is never weighed: its slab rows only have to be states the partner can be run on
+            prev = torch.where(usable.view(m, 1), prev, r).contiguous()
+            belief_splice(self.cfg, prev, b["cand_rows"], int(seat), Kn, out=b["hyp_rows"])
+            b["env"].first_game_id = int(first_game_id)
+            cd._slab_moves(b, partner, m, Kn, dev, partner_seed, partner_draw, b["hyp_moves"], self._nleg[0])
+            n_surv, used, fallback, ess = _bufs(dev, None, ((1, m), torch.int32), ((m,), torch.int32), ((m,), torch.uint8),
+                                                ((m,), torch.float32))
+            belief_select_soft(self.cfg, r, b["cand_rows"], b["cand_w"], b["hyp_moves"].view(1, Kn, m), self._nleg,
+                               last_move_uid(self.cfg, r).view(1, m), usable.to(torch.uint8).view(1, m), self._table(epsilon, dev), Kn,
+                               seed, draw, first_row_id=first_row_id, out=self._next + (n_surv, used, fallback, ess))
+            new_rows, new_w = self._next
+            tracked = usable & (new_w.view(m, Kn)[:, 0] != 0)   # (a resampling total of 0 leaves every particle dead)
+            restarted = live & ~tracked
+            n_surv, used = n_surv[0], tracked.int()
+            fallback = torch.where(tracked, 0, 2).to(torch.uint8)
+            if bool(restarted.any().item()):
+                if history is not None:
+                    got = cd.sample_history(r, history, partner, seat, Kn, 1, seed, draw, partner_seed, first_game_id,
+                                            first_row_id=first_row_id, epsilon=epsilon)
+                    surv_d, used2, fb2 = got[2], got[3].int(), got[4]
+                    surv2 = torch.where(used2 > 0, surv_d.gather(0, (used2.long() - 1).clamp(min=0).view(1, m)).view(m), 0)
+                    ess2 = got[5] if epsilon is not None else None
+                else:
+                    got = cd.sample(r, prev_rows, partner, seat, Kn, 1, seed, draw, partner_seed, partner_draw, first_game_id,
+                                    valid=valid, first_row_id=first_row_id, epsilon=epsilon)
+                    surv2, fb2 = got[2], got[3]
+                    used2 = (fb2 == 0).int()
+                    ess2 = got[4] if epsilon is not None else None
+                pick = restarted.view(m, 1)
+                new_rows.view(m, Kn * SW).copy_(torch.where(pick, got[0].view(m, Kn * SW), new_rows.view(m, Kn * SW)))
+                new_w.view(m, Kn).copy_(torch.where(pick, got[1].view(m, Kn).int(), new_w.view(m, Kn)))
+                n_surv, used = torch.where(restarted, surv2, n_surv), torch.where(restarted, used2, used)
+                fallback = torch.where(restarted, fb2, fallback)
+                if ess2 is not None:
+                    ess = torch.where(restarted, ess2, ess)
+            self._next = (self.rows, self.weights)
+            self.rows, self.weights = new_rows, new_w
+            self.have = live.clone()
+        return TrackedRows(self.rows, self.weights, Kn, n_surv, fallback, used, ess, tracked, restarted,
+                           torch.where(tracked, carried_live, 0))
 
 
 class SearchResult:
@@ -1094,6 +1388,9 @@ class RolloutSearch:
             if history is None:
                 self.det.sample(r, seat=cp, replicas=R, seed=self.seed, draw=draw, first_row_id=first_row_id,
                                 out=(b["det_rows"], b["weights"]))
+            elif isinstance(history, TrackedRows):
+                history.take(m, R, (b["det_rows"], b["weights"]))
+                n_surv, fallback, depth_used, ess = history.n_surv, history.fallback, history.depth_used, history.ess
             elif isinstance(history, PartnerHistory):
                 if self.cdet is None:
                     self.cdet = ConditionedDeterminizer(config=self.cfg)
@@ -1150,7 +1447,7 @@ class RolloutSearch:
         r = roots[0]
         dev = r.device
         m, A = r.shape[0], self.num_actions
-        if history is not None and not isinstance(history, PartnerHistory):
+        if history is not None and not isinstance(history, (PartnerHistory, TrackedRows)):
             history = _history(history, m, self.det.state_words, dev)
         lg = torch.as_tensor(legal).to(device=dev, dtype=torch.int8).contiguous()
         if lg.shape != (m, A):
@@ -1180,7 +1477,7 @@ class RolloutSearch:
         roots = self._roots(rows, blueprint, None)
         dev = roots[0].device
         m = roots[0].shape[0]
-        if history is not None and not isinstance(history, PartnerHistory):
+        if history is not None and not isinstance(history, (PartnerHistory, TrackedRows)):
             history = _history(history, m, self.det.state_words, dev)
         R = self.replicas if replicas is None else int(replicas)
         if R < 1:
@@ -1227,6 +1524,8 @@ class RolloutSearch:
         is_legal = lambda u: (u >= 0) & (u < A) & lgb.gather(1, u.long().clamp(0, A - 1).view(m, 1)).view(m)
         ok = running(r) & (ch != bl) & is_legal(bl) & is_legal(ch)
         cand = torch.where(ok.view(m, 1), torch.stack([bl, ch], 1), -1).int().contiguous()
+        if isinstance(history, TrackedRows):   # the particles behind run()'s
+            history = history.shifted(self.replicas)
         return self.run_candidates(r, cand, lgb.int().argmax(1).int(), blueprint, draw, replicas=replicas,
                                    first_row_id=m * self.replicas * (1 if history is None else self.oversample),
                                    first_game_id=self.first_game_id + m * A * self.replicas,
@@ -1283,15 +1582,28 @@ class SearchPlayer:
     partner moves their replicas reproduce: 1 per root that did not fall back at depth 1; with depth > 1 `survivors` counts the
     candidates that pass the filter of the depth used).
 
+    track=True (default False: nothing is allocated and the player is the one above bit for bit; needs condition=True): the
+    belief is tracked across turns instead of rebuilt at each (`TrackedBelief`, hb_belief_carry): the
+    replicas * oversample hand samples of my last turn are carried, weighed by the one move the partner has made since and
+    resampled; the first `replicas` of them are searched, the next `confirm_replicas` confirm (so replicas + confirm_replicas <=
+    replicas * oversample). A root without particles, without a usable previous turn or without one particle that explains what
+    was seen starts over from the belief above (depth, epsilon, replicas * oversample candidates). TRACK_COUNTERS: `tracked` (live
+    roots that carried), `restarts` (live roots that started over; tracked + restarts = conditioned + unconditioned = moves),
+    `carried_live` (live particles after the carry, summed over the tracked roots). `conditioned` then counts the tracked roots
+    and the restarted ones whose belief was filtered, `survivors` the particles (or candidates) that reproduce the partner's move,
+    `depth_used` 1 per tracked root; depth_stats() gains `carried_ess`, the mean effective sample size of the tracked roots'
+    weighed particles, and its per-depth sums are not kept. belief_stats() also splits by `tracked` / `restarted`.
+
     score_belief (default False: nothing is computed or allocated, and the moves played are the same bits either way): every
     first-stage search scores its replicas against the real hands (RolloutSearch's score_belief, hb_belief_score) and the player
     adds the sums up on the device; belief_stats() gives the means."""
 
     COUNTERS = ("moves", "deviations", "confirmed", "rejected", "conditioned", "unconditioned", "survivors", "candidates", "fallbacks",
                 "depth_used")
+    TRACK_COUNTERS = ("tracked", "restarts", "carried_live")
 
     def __init__(self, blueprint, seat, replicas=32, threshold=0.0, seed=1, check_every=8, z=None, confirm_replicas=0,
-                 condition=False, oversample=8, depth=1, epsilon=None, score_belief=False):
+                 condition=False, oversample=8, depth=1, epsilon=None, score_belief=False, track=False):
         self.blueprint = list(blueprint)
         self.seat = int(seat)
         if not 0 <= self.seat < len(self.blueprint):
@@ -1328,6 +1640,19 @@ class SearchPlayer:
         if not isinstance(score_belief, bool):
             raise TypeError(f"score_belief is a switch (True or False), got {score_belief!r}")
         self.score_belief = score_belief
+        if not isinstance(track, bool):
+            raise TypeError(f"track is a switch (True or False), got {track!r}")
+        if track:
+            if not self.condition:
+                raise ValueError("track=True needs condition=True")
+            if self.replicas * self.oversample > MAX_SOFT_CANDIDATES:
+                raise ValueError(f"the soft filter takes at most {MAX_SOFT_CANDIDATES} candidates per root, got replicas * oversample = "
+                                 f"{self.replicas * self.oversample}")
+            if self.replicas + self.confirm_replicas > self.replicas * self.oversample:
+                raise ValueError(f"track=True searches and confirms on particles of one set: replicas + confirm_replicas = "
+                                 f"{self.replicas + self.confirm_replicas} exceeds replicas * oversample = {self.replicas * self.oversample}")
+        self.track = track
+        self._tracked = None   # track: the TrackedBelief of the env of the last call
         self._history = None   # depth > 1: the PartnerHistory of the env of the last call
         self._search = None
         self.last_result = None   # the SearchResult of the last call's first stage
@@ -1344,13 +1669,20 @@ class SearchPlayer:
         self._by_depth = None   # depth > 1: [4, depth] int64 on the device, see depth_stats()
         self._ess = None        # epsilon: [2] float64 on the device, sum of ess and count over the conditioned roots
         self._belief = None     # score_belief: [2, len(BeliefScore.SUMS), H] float64 on the device (conditioned roots, the others)
+        self._track_stats = None    # track: [len(TRACK_COUNTERS)] int64 on the device
+        self._track_ess = None      # track: [2] float64 on the device, sum of ess and count over the tracked roots
+        self._belief_track = None   # track and score_belief: the sums of _belief, split (tracked roots, restarted roots)
 
     def belief_stats(self):
         """score_belief: the first stage's beliefs against the real hands since reset_stats(), over every live root searched:
         belief_figures' dict (`cards`, `roots`, `hit_rate`, `prior_rate`, `joint_rate`, `cross_entropy`, `prior_cross_entropy`,
         `by_slot`). With condition=True it also holds the same dict for the `conditioned` roots (fallback != 2) and for the
         `unconditioned` ones. All zeros before the first call (and without score_belief)."""
-        return belief_stats_of(self._belief, self.condition)
+        out = belief_stats_of(self._belief, self.condition)
+        if self.track:   # the same figures over the roots that carried their particles and over those that started over
+            for j, name in enumerate(("tracked", "restarted")):
+                out[name] = belief_figures(None if self._belief_track is None else self._belief_track[j])
+        return out
 
     def belief_sums(self):
         """score_belief: the sums behind belief_stats(), [2 (conditioned roots, the others), len(BeliefScore.SUMS), H] float64 on
@@ -1367,6 +1699,9 @@ class SearchPlayer:
         if self.epsilon is not None:   # the mean effective sample size of the conditioned roots' candidates (0.0: none yet)
             total, count = (0.0, 0.0) if self._ess is None else self._ess.tolist()
             out["ess"] = total / count if count else 0.0
+        if self.track:   # the mean effective sample size of the tracked roots' carried, weighed particles
+            total, count = (0.0, 0.0) if self._track_ess is None else self._track_ess.tolist()
+            out["carried_ess"] = total / count if count else 0.0
         return out
 
     def _previous(self, env, rows, draw):
@@ -1404,6 +1739,18 @@ class SearchPlayer:
         h.push(prev, last_move_uid(env.cfg, rows), int(draw) - 1, valid, seat=self.seat)
         return h
 
+    def _carry(self, env, rows, seed, draw, prev, valid, stack):
+        """track: this call's TrackedRows. The particle sets of the call remembered from draw - 2 are carried; a remembered call
+        that is not this env's at draw - 2 forgets them first (every root then starts over)."""
+        mem, tb = self._memory, self._tracked
+        if tb is None or tb.cfg.players != env.cfg.players or (tb.rows is not None and tb.rows.device != rows.device):
+            tb = self._tracked = TrackedBelief(config=eval_config(None, None, env.cfg), replicas=self.replicas, oversample=self.oversample)
+        same = mem is not None and mem[0]() is env and mem[1] == int(draw) - 2 and mem[2].shape == rows.shape
+        if not same:
+            tb.clear()
+        return tb.step(rows, mem[2] if same else None, mem[3] if same else None, prev, valid, self.blueprint[1 - self.seat], self.seat,
+                       self.seed, draw, int(seed), int(draw) - 1, env.first_game_id, epsilon=self.epsilon, history=stack)
+
     def _significant(self, diff, se, z):
         """diff > z * se, never with a standard error that is not finite (0 * inf must not pass) or a NaN."""
         return torch.isfinite(se) & (diff > z * se)
@@ -1435,6 +1782,8 @@ class SearchPlayer:
                 history = (prev, int(seed), int(draw) - 1, env.first_game_id, valid)
             else:
                 history = self._stack(env, rows, seed, draw, prev, valid)
+            if self.track:
+                history = self._carry(env, rows, seed, draw, prev, valid, history if self.depth > 1 else None)
         res = self._search.run(rows, env.legal, self.blueprint, draw, seat=self.seat,
                                baseline=actions_out if self.z is not None else None, history=history)
         self.last_result = res
@@ -1442,6 +1791,9 @@ class SearchPlayer:
             filtered = res.fallback != 2 if self.condition and res.fallback is not None else torch.zeros_like(res.belief.scored)
             sums = torch.stack([res.belief.sums(where=filtered), res.belief.sums(where=~filtered)])
             self._belief = sums if self._belief is None else self._belief + sums
+            if self.track:
+                split = torch.stack([res.belief.sums(where=history.tracked), res.belief.sums(where=history.restarted)])
+                self._belief_track = split if self._belief_track is None else self._belief_track + split
         live = running(rows)
         bp = actions_out.long().clamp(0, env.num_actions - 1).view(-1, 1)
         best = res.best.long().clamp(min=0).view(-1, 1)
@@ -1467,10 +1819,17 @@ class SearchPlayer:
             self._memory = (weakref.ref(env), int(draw), rows, actions_out.clone())
             if res.fallback is not None:   # (None: no root was running)
                 filtered = live & (res.fallback != 2)
-                if res.ess is not None:
-                    ess = torch.stack([(res.ess.double() * filtered).sum(), filtered.sum().double()])
+                if res.ess is not None and self.epsilon is not None:
+                    soft = filtered & history.restarted if self.track else filtered
+                    ess = torch.stack([(res.ess.double() * soft).sum(), soft.sum().double()])
                     self._ess = ess if self._ess is None else self._ess + ess
-                if self.depth == 1:
+                if self.track:   # (per root already: the carried particles' figures, or those of the belief it started over with)
+                    n_surv, used = res.n_surv, res.depth_used.long()
+                    t_ess = torch.stack([(res.ess.double() * history.tracked).sum(), history.tracked.sum().double()])
+                    self._track_ess = t_ess if self._track_ess is None else self._track_ess + t_ess
+                    t_counts = torch.stack([history.tracked.sum(), history.restarted.sum(), history.carried_live.sum()]).long()
+                    self._track_stats = t_counts if self._track_stats is None else self._track_stats + t_counts
+                elif self.depth == 1:
                     n_surv, used = res.n_surv, (res.fallback == 0).long()
                 else:   # the candidates that pass the filter of the depth used, root by root
                     used = res.depth_used.long()
@@ -1496,3 +1855,5 @@ class SearchPlayer:
 
 for _j, _name in enumerate(SearchPlayer.COUNTERS):   # the device counters as read-only ints: 0 before the first call
     setattr(SearchPlayer, _name, property(lambda self, j=_j: 0 if self._stats is None else int(self._stats[j].item())))
+for _j, _name in enumerate(SearchPlayer.TRACK_COUNTERS):   # track=True's (0 without)
+    setattr(SearchPlayer, _name, property(lambda self, j=_j: 0 if self._track_stats is None else int(self._track_stats[j].item())))

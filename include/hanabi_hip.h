@@ -984,7 +984,37 @@ int hb_train_tally(const hb_config* cfg, int64_t n_games, int32_t seat, const in
  * A replica of weight 0 counts nothing (it is an unchanged copy of the true hand); a replica slot holding 31 or an id >= NC matches
  * nothing. Integers only (every ratio is the host's), 64-bit sums: no order, bit-equal to hanabi_hip.search.belief_score_ref.
  * 1 <= replicas <= 2^20 (wsum < 2^52), m < 2^31. One wavefront per root; no LDS, no atomics.
- * All eleven check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                   */
+ * hb_belief_carry: range tracking, sampled: the hand samples ("particles") of my previous turn carried to my present one. cur_rows_dev
+ * [m, SW] the real states now, in which `seat` (0 .. players - 1, the observer) is to act; old_rows_dev [m * K, SW] / old_weight_dev
+ * [m * K] u32 the K = n_particles particles of each root at my previous turn (particle (i, k) = row i * K + k; ONLY word 10 + seat, the
+ * observer's hand then, is read, and of the weight only whether it is 0); own_slot_dev [m] int32 the slot I played or discarded at
+ * that turn (< 0: a hint), revealed_dev [m] int32 the card id that move turned face up (-1: none), drew_dev [m] int32 the card id
+ * the partner has visibly drawn since (< 0: none). Per particle (i, k) -> out_rows_dev [m * K, SW], out_weight_dev [m * K] u32:
+ *   1. Not usable: the particle is dead if old_weight == 0, if cur row i is not running, or if its current player is not `seat`. A
+ *      dead particle has weight 0 and its row is an unchanged copy of cur row i, as in hb_belief_determinize.
+ *   2. Card played: if own_slot >= 0, the old hand's 5-bit field in that slot must equal `revealed` (own_slot >= hand_size: no such
+ *      slot), else dead; it is removed. The remaining fields that hold a card (!= 31), oldest first, are kept[0 .. k). More kept
+ *      cards than the current hand has slots (word 1 of cur row i): dead.
+ *   3. Pool: hb_belief_determinize's, built from cur row i: the observer's current hand slots, then the undealt deck positions
+ *      ascending.
+ *   4. Kept slots: for s < k, slot s takes the first pool element not yet taken whose card equals kept[s]; the CURRENT knowledge
+ *      bits of slot s must allow that card's colour and rank (an id >= colors * ranks is never allowed). No such element, or not
+ *      allowed: dead. No weight factor.
+ *   5. Weight from the partner's draw: g = 1 + the number of pool elements not taken whose card equals `drew`, counted after step 4
+ *      and before step 6; g = 1 when drew < 0.
+ *   6. New slots: every remaining slot s = k .. hand size - 1 (normally one) takes hb_belief_determinize's step exactly: candidates
+ *      (not taken, plausible for slot s), n_s, the (u_s * n_s) >> 32-th of them; n_s == 0: dead.
+ *   7. Deck: the rest of the pool goes onto the undealt deck positions by hb_belief_determinize's keyed shuffle.
+ *   8. out_weight = g * prod n_s (u32; < 2^32 on any real deck). The row is cur row i with ONLY word 10 + seat and the undealt deck
+ *      bytes changed.
+ * The input particles are taken as EQUALLY weighted, whatever non-zero weight they carry: that is what hb_belief_select_soft hands
+ * out, and what hb_belief_determinize hands out on states reached by play (there its weights are constant per root). Then the
+ * weighted output estimates the uniform distribution over the physical assignments of what I cannot see, given the old sample
+ * and everything made public since ("Tracking the belief", has the derivation of g). Randomness:
+ * hb_belief_determinize's own Philox words (same key, counter 128 + j, row id = first_row_id + output row): a split call gives the
+ * same rows. One wavefront per output row, four per workgroup, everything in registers; no LDS, no atomics, a pure function of the
+ * inputs. n_particles >= 1, m * n_particles < 2^31.
+ * All twelve check their arguments before any launch; m == 0 is a no-op; without a device: HB_ERR_NO_DEVICE.                   */
 int hb_belief_determinize(const hb_config* cfg, const uint32_t* src_rows_dev, int64_t m, int32_t seat, int32_t replicas, uint64_t seed,
                           uint64_t draw, int64_t first_row_id, uint32_t* out_rows_dev, uint32_t* weight_dev, void* stream);
 int hb_search_reduce(const int8_t* score_dev, const uint32_t* weight_dev, const int8_t* legal_dev, int64_t m, int32_t n_actions,
@@ -1018,6 +1048,10 @@ int hb_belief_history_step(const hb_config* cfg, int64_t m, int32_t depth, int32
 int hb_belief_score(const hb_config* cfg, const uint32_t* true_rows_dev, const uint32_t* det_rows_dev, const uint32_t* weight_dev,
                     int64_t m, int32_t seat, int32_t replicas, int8_t* truth_dev, int64_t* hit_dev, int64_t* joint_dev,
                     int64_t* wsum_dev, int32_t* n_live_dev, int64_t* counts_dev, int8_t* prior_dev, void* stream);
+int hb_belief_carry(const hb_config* cfg, const uint32_t* cur_rows_dev, const uint32_t* old_rows_dev, const uint32_t* old_weight_dev,
+                    const int32_t* own_slot_dev, const int32_t* revealed_dev, const int32_t* drew_dev, int64_t m, int32_t seat,
+                    int32_t n_particles, uint64_t seed, uint64_t draw, int64_t first_row_id, uint32_t* out_rows_dev,
+                    uint32_t* out_weight_dev, void* stream);
 
 /* ---- One host call per step: hb_chain_run (csrc/chain.hip, round 3) ------------------------------------------------------
  * The session that drives DQNAgent (rlax_rainbow.py:277-339: explore / add_experience / update once per env step) issues ~25

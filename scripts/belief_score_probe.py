@@ -5,8 +5,15 @@ sections 11f "Scoring a belief" and 11g) on one MI355X, and what scoring costs.
            score_belief=True, replicas=32, oversample=8, seed=9): with that threshold no configuration ever leaves the blueprint,
            so all of them search the same roots of the same games and the comparison is paired (the script checks it: same
            scores, same roots, same cards, same prior figures). Configurations: the V0 belief; condition=True at depth 1, 2, 4;
-           the same three with epsilon=0.1. Per configuration: hit rate, joint rate, cross-entropy, the card-counting prior's
-           figures, by slot, and the conditioned / unconditioned split.
+           the same three with epsilon=0.1; track=True (the belief tracked across turns, hb_belief_carry) over depth 1 and 4 and
+           over depth 1 with epsilon=0.1. Per configuration: hit rate, joint rate, cross-entropy, the card-counting prior's
+           figures, by slot, and the conditioned / unconditioned split; with track=True also the tracked / restarted split, the
+           restart share, the mean live particles after the carry and the mean effective sample size.
+  track    the cost of one tracked turn (TrackedBelief.step: carry, splice, one partner pass over the 256 slabs, resampling)
+           against one depth=4 turn (ConditionedDeterminizer.sample_history: 256 candidates, four partner passes, one filter) on
+           the same 1 024 roots 24 moves into [Piers, Piers] games, event-timed over whole turns, rotating through enough
+           particle sets to exceed the 256 MB Infinity Cache; and hb_belief_carry alone, call by call (one launch between two
+           events: an upper bound).
   kernel   hb_belief_score alone, event-timed call by call at m=1024, R=32 and m=32768, R=1 (with and without the per-card tally):
            median of CALLS calls after a warm-up, once on one set of buffers (cache-resident) and once rotating through enough
            sets to exceed the 256 MB Infinity Cache. One launch between two events is mostly launch overhead: upper bounds.
@@ -16,7 +23,7 @@ sections 11f "Scoring a belief" and 11g) on one MI355X, and what scoring costs.
   resources (--resources-only: this part alone, needs no GPU) the compiler's resource line of belief_score_kernel.
 
 Writes one JSON file.
-Usage: belief_score_probe.py [--out profiles/search/belief_score_probe.json] [--games 1024] [--parts beliefs,kernel,obl]
+Usage: belief_score_probe.py [--out profiles/search/belief_score_probe.json] [--games 1024] [--parts beliefs,kernel,obl,track]
        [--resources-only]   (parts that are not run keep what the file holds)"""
 import argparse
 import json
@@ -32,6 +39,8 @@ for p in (ROOT, os.path.join(ROOT, "hanabi-agents_amd"), os.path.dirname(os.path
 
 CONFIGS = [("v0", {})] + [(f"depth{d}{'_eps0.1' if eps else ''}", dict(condition=True, depth=d, **({"epsilon": eps} if eps else {})))
                           for eps in (None, 0.1) for d in (1, 2, 4)]
+CONFIGS += [("track_depth1", dict(condition=True, depth=1, track=True)), ("track_depth4", dict(condition=True, depth=4, track=True)),
+            ("track_depth1_eps0.1", dict(condition=True, depth=1, track=True, epsilon=0.1))]
 CALLS, WARM_CALLS = 40, 10
 N, STEPS, REPS, WARM = 32768, 200, 3, 80
 CACHE_BYTES = 256 << 20
@@ -59,6 +68,17 @@ def beliefs(games):
         st = belief_stats_of(players[0].belief_sums() + players[1].belief_sums(), split=bool(kw))
         rows[label] = dict(kw, mean=r.mean, moves=tot("moves"), deviations=tot("deviations"), conditioned=tot("conditioned"),
                            fallbacks=tot("fallbacks"), dead_replicas=tot("dead_replicas"), seconds=seconds, belief=st)
+        if kw.get("track"):
+            both = [p.belief_stats() for p in players]
+            merge = lambda k, name, count: sum(b[k][name] * b[k][count] for b in both) / max(sum(b[k][count] for b in both), 1)
+            ess = [p.depth_stats()["carried_ess"] for p in players]
+            rows[label].update(
+                tracked=tot("tracked"), restarts=tot("restarts"), restart_share=tot("restarts") / max(tot("moves"), 1),
+                mean_carried_live=tot("carried_live") / max(tot("tracked"), 1), particles=32 * 8,
+                carried_ess=sum(e * p.tracked for e, p in zip(ess, players)) / max(tot("tracked"), 1),
+                split={k: dict(roots=sum(b[k]["roots"] for b in both), hit_rate=merge(k, "hit_rate", "cards"),
+                               joint_rate=merge(k, "joint_rate", "roots"), cross_entropy=merge(k, "cross_entropy", "cards"))
+                       for k in ("tracked", "restarted")})
         print(json.dumps({label: rows[label]}), flush=True)
         del players
         torch.cuda.empty_cache()
@@ -115,6 +135,90 @@ def kernel():
         torch.cuda.empty_cache()
     out["note"] = ("one launch between two events: launch overhead and the events' own resolution are in every figure, so these are "
                    "host-bound upper bounds on the kernel's time, not kernel times")
+    return out
+
+
+def track():
+    import torch
+
+    import hanabi_hip
+    from hanabi_agents.rule_based import RulebasedAgent, predefined_rules as PR
+    from hanabi_hip import ConditionedDeterminizer, PartnerHistory, TrackedBelief, belief_carry, last_move_uid
+
+    m, R, ov, depth, seed, pseed = 1024, 32, 8, 4, 9, 7
+    Kn = R * ov
+    piers = [RulebasedAgent(PR.piers_rules, seed=1), RulebasedAgent(PR.piers_rules, seed=2)]
+    env = hanabi_hip.HanabiEnv("Hanabi-Full", 2, n_games=m, seed=3, auto_reset=False, packed=True)
+    act = torch.zeros(m, dtype=torch.int32, device="cuda")
+    tb = TrackedBelief("Hanabi-Full", 2, replicas=R, oversample=ov)
+    hist = PartnerHistory(env.cfg, m, depth, "cuda", partner_seed=pseed, first_game_id=env.first_game_id)
+    ones, then, last = torch.ones(m, dtype=torch.uint8, device="cuda"), None, None
+    for turn in range(25):   # seat 0 observes on even turns; the last of them is the one timed
+        rows, draw = env.export_state().clone(), turn + 1
+        if turn % 2 == 0:
+            if then is not None:
+                hist.own_move(then[1])
+                hist.push(then[2], last_move_uid(env.cfg, rows), draw - 1, ones, seat=0)
+                last = dict(rows=rows, then_rows=then[0], then_moves=then[1], prev_rows=then[2], draw=draw,
+                            old=(tb.rows.clone(), tb.weights.clone(), tb.have.clone()))
+            tb.step(rows, *(then if then is not None else (None, None, rows)), None if then is not None else ones * 0, piers[1], 0, seed, draw,
+                    pseed, draw - 1, env.first_game_id)
+            piers[0].eval_moves(env, pseed, draw, act)
+            then = [rows, act.clone(), None]
+        else:
+            piers[1].eval_moves(env, pseed, draw, act)
+            then[2] = rows
+        env.step(act)
+    per_set = sum(t.numel() * t.element_size() for t in last["old"][:2])
+    n_sets = -(-CACHE_BYTES * 5 // 4 // per_set)
+    sets = [tuple(t.clone() for t in last["old"]) for _ in range(n_sets)]
+    cdet = ConditionedDeterminizer(config=env.cfg)
+    a = last
+
+    def tracked_turn(k):
+        tb.rows, tb.weights, tb.have = (t for t in sets[k % n_sets])   # (step swaps its buffers: the set comes back as scratch)
+        tb._next = (torch.empty_like(tb.rows), torch.empty_like(tb.weights)) if k < 2 else tb._next
+        return tb.step(a["rows"], a["then_rows"], a["then_moves"], a["prev_rows"], ones, piers[1], 0, seed, a["draw"], pseed, a["draw"] - 1,
+                       env.first_game_id)
+
+    def depth_turn(k):
+        return cdet.sample_history(a["rows"], hist, piers[1], 0, R, ov, seed, a["draw"], pseed, env.first_game_id)
+
+    out = dict(m=m, particles=Kn, depth=depth, turns_timed=10, particle_bytes_per_set=per_set, sets_rotated=n_sets)
+    for name, fn in (("tracked_turn_ms", tracked_turn), ("depth4_turn_ms", depth_turn)):
+        for k in range(2):
+            got = fn(k)
+        if name == "tracked_turn_ms":
+            out.update(tracked_roots=int(got.tracked.sum()), restarted_roots=int(got.restarted.sum()),
+                       mean_carried_live=float(got.carried_live.sum()) / max(int(got.tracked.sum()), 1))
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(10)]
+        torch.cuda.synchronize()
+        for k, (e0, e1) in enumerate(ev):
+            sets[(k + 2) % n_sets] = tuple(t.clone() for t in last["old"]) if name == "tracked_turn_ms" else sets[(k + 2) % n_sets]
+            e0.record()
+            fn(k + 2)
+            e1.record()
+        torch.cuda.synchronize()
+        ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+        out[name] = dict(median=round(statistics.median(ms), 3), min=round(ms[0], 3), max=round(ms[-1], 3))
+    slot, rev, drew = tb.observed(a["rows"], a["then_rows"], a["then_moves"], a["prev_rows"], 0)
+    sets = [tuple(t.clone() for t in last["old"]) for _ in range(n_sets)]
+    bufs = (torch.empty_like(last["old"][0]), torch.empty_like(last["old"][1]))
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(CALLS)]
+    for k in range(WARM_CALLS):
+        belief_carry(env.cfg, a["rows"], sets[k % n_sets][0], sets[k % n_sets][1], slot, rev, drew, 0, Kn, seed, a["draw"], out=bufs)
+    torch.cuda.synchronize()
+    for k, (e0, e1) in enumerate(ev):
+        e0.record()
+        belief_carry(env.cfg, a["rows"], sets[k % n_sets][0], sets[k % n_sets][1], slot, rev, drew, 0, Kn, seed, a["draw"], out=bufs)
+        e1.record()
+    torch.cuda.synchronize()
+    us = sorted(e0.elapsed_time(e1) * 1000 for e0, e1 in ev)
+    out["carry_kernel_us_upper_bound"] = dict(median=round(statistics.median(us), 2), min=round(us[0], 2), max=round(us[-1], 2),
+                                              rows_per_call=m * Kn)
+    out["note"] = ("whole turns between two events (dozens of launches each; the restart decision's one synchronisation is inside the "
+                   "tracked turn); the single-kernel figure is one launch between two events: a host-bound upper bound")
+    print(json.dumps(out), flush=True)
     return out
 
 
@@ -182,6 +286,7 @@ def main():
         from obl_probe import kernel_resources
 
         out["resources"] = kernel_resources("belief.hip", only="belief_score")
+        out["resources"].update(kernel_resources("belief.hip", only="belief_carry"))
         print(json.dumps(out["resources"]), flush=True)
         return save()
     import torch
@@ -190,7 +295,7 @@ def main():
         raise SystemExit("belief_score_probe.py measures on the GPU: none found")
     out["device"] = torch.cuda.get_device_name(0)
     for part in args.parts.split(","):
-        out[part] = {"beliefs": lambda: beliefs(args.games), "kernel": kernel, "obl": obl}[part]()
+        out[part] = {"beliefs": lambda: beliefs(args.games), "kernel": kernel, "obl": obl, "track": track}[part]()
         save()
 
 
