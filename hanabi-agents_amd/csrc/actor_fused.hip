@@ -78,6 +78,23 @@ struct FusedArgs {
   unsigned long long* stamps;   // diagnostic builds only (-DHB_STAMPS): 16 u64 per wavefront
 };
 
+// HB_ENV_KARGS(env): the env arguments of actor_env_fused_kernel (its second parameter) as a reference `env`, read from the
+// kernel-argument segment only WHERE THE MACRO STANDS: read through the parameter, the compiler loads them at the kernel's start and
+// carries ~30 scalar registers through both layers, which spills scalars into a reserved vector register (233 VGPRs instead of 232:
+// no room left for the learner's kernels beside this one). The opaque pointer keeps the loads behind it. Explicit kernel arguments
+// are laid out in declaration order at their natural alignment.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) unsigned char KargByte;
+typedef const __attribute__((address_space(4))) hb::EnvArgs KargEnv;
+constexpr size_t ENV_KARG_OFF = (sizeof(FusedArgs) + alignof(hb::EnvArgs) - 1) / alignof(hb::EnvArgs) * alignof(hb::EnvArgs);
+#define HB_ENV_KARGS(NAME)                                            \
+  auto NAME##_kargs_ = __builtin_amdgcn_kernarg_segment_ptr();        \
+  asm volatile("" : "+s"(NAME##_kargs_));                             \
+  KargEnv& NAME = *(KargEnv*)((KargByte*)NAME##_kargs_ + ENV_KARG_OFF)
+#else
+#define HB_ENV_KARGS(NAME) const hb::EnvArgs NAME{}   // (host pass: never run)
+#endif
+
 // In-kernel phase stamps (cdna_hip_programming.md section 7): compiled in only with -DHB_STAMPS, into the separate diagnostic
 // library (make stamps); the shipped kernel contains none of this.
 #ifdef HB_STAMPS
@@ -503,6 +520,23 @@ __device__ __forceinline__ void actor_fused_body(const FusedArgs& a) {
     if (p + 1 < n_pass) __syncthreads();
     if (p < 2) HB_FSTAMP(9 + 3 * p);
   }
+  // ---- env tail, deck-pool refill, part 1 (see part 2 below): wavefronts 2..7 request the refill flags and the deal counters of the
+  // workgroup's 128 games (lane l: games row0 + l and row0 + 64 + l) as soon as they leave the last pass, so that the latency sits
+  // under the merge and the q drain. Nothing at or past the batch's end is read.
+  [[maybe_unused]] uint32_t rf_flag[2] = {0u, 0u}, rf_ep[2] = {0u, 0u};
+  if constexpr (!std::is_void_v<K>) {
+    if (wave >= 2) {
+      HB_ENV_KARGS(env);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const long long g = row0 + 64 * h + lane;
+        if (g < env.n) {
+          rf_flag[h] = env.refill[g];
+          rf_ep[h] = env.state[g * K::SW + 6];
+        }
+      }
+    }
+  }
   if (a.legal) {
     // ---- action selection for the workgroup's 128 rows, one lane per row. The q values were stored by all eight wavefronts:
     // every wavefront drains its stores (they are complete once L2 has them), the barrier orders that before the reads, and the
@@ -542,27 +576,43 @@ __device__ __forceinline__ void actor_fused_body(const FusedArgs& a) {
     }
   }
   if constexpr (!std::is_void_v<K>) {
+    // ---- env tail, deck-pool refill, part 2: while wavefronts 0 and 1 select the moves, wavefronts 2..7 regenerate the pool decks
+    // of the workgroup's own games whose flag is set (raised by an earlier launch's re-deal: about two per workgroup and step) and
+    // clear the flags, which is all refill_kernel does, so the fused step needs no refill launch after it. Flagged games are dealt
+    // out over the six wavefronts by the rank of their flag (every wavefront sees all 128 flags), so exactly one wavefront writes
+    // a deck and clears its flag. A deck consumed by this launch's env tail (below) is flagged there and regenerated by the next
+    // launch: the game it belongs to has three lives and cannot end before the third step after its deal. Only this workgroup
+    // touches these pool rows and flags; the barrier below orders the writes here before the env tail's reads and writes.
+    static_assert(K::LIFE >= 2, "a deck flagged by one launch is regenerated by the next: a game must outlive the step after its deal");
+    if (wave >= 2) {
+      HB_ENV_KARGS(env);
+      int turn = wave - 2;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        unsigned long long todo = __ballot(rf_flag[h] != 0u);
+        while (todo) {
+          const int src = __ffsll(static_cast<long long>(todo)) - 1;
+          todo &= todo - 1;
+          if (turn == 0) {
+            const long long g = row0 + 64 * h + src;
+            hb::refill_deck<K>(env, g, lane, [&] {
+              return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(rf_ep[h]), src));
+            });
+            if (lane == 0) env.refill[g] = 0;
+            turn = 6;
+          }
+          --turn;
+        }
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the pool writes are out before the barrier
+    }
     // ---- env tail: games [row0, row0 + 128) take their moves from LDS; wavefront w steps games row0 + EG w + [0, EG). The
     // barrier also orders every read of `legal` and of the bit rows (done above) before the env's writes of the same rows.
     constexpr int ENV_WORDS = hb::env_lds_words<K, EG>();
     static_assert((FM / EG) * ENV_WORDS * 4 <= H_BYTES && FM / EG <= FNT / 64, "env tail: the LDS slices must fit in H");
     __syncthreads();
     if (wave < FM / EG) {
-      // The env arguments (the kernel's second parameter) are read from the kernel-argument segment only HERE: read through the
-      // parameter, the compiler loads them at the kernel's start and carries ~30 scalar registers through both layers, which
-      // spills scalars into a reserved vector register (233 VGPRs instead of 232: no room left for the learner's kernels beside
-      // this one). The opaque pointer keeps the loads in the tail. Explicit kernel arguments are laid out in declaration order
-      // at their natural alignment.
-#if defined(__HIP_DEVICE_COMPILE__)
-      typedef const __attribute__((address_space(4))) unsigned char KargByte;
-      typedef const __attribute__((address_space(4))) hb::EnvArgs KargEnv;
-      auto kargs = __builtin_amdgcn_kernarg_segment_ptr();
-      asm volatile("" : "+s"(kargs));
-      constexpr size_t ENV_OFF = (sizeof(FusedArgs) + alignof(hb::EnvArgs) - 1) / alignof(hb::EnvArgs) * alignof(hb::EnvArgs);
-      KargEnv& env = *(KargEnv*)((KargByte*)kargs + ENV_OFF);
-#else
-      const hb::EnvArgs env{};   // (host pass: never run)
-#endif
+      HB_ENV_KARGS(env);
       const long long g0 = row0 + EG * wave;
       const int uid = lane < EG ? reinterpret_cast<const int*>(lds + H_BYTES)[EG * wave + lane] : 0;
       hb::env_wave_step<K, EG>(env, g0, lane, reinterpret_cast<uint32_t*>(lds) + wave * ENV_WORDS, uid, g0 / EG);

@@ -541,7 +541,7 @@ int hb_env_step_select_packed(hb_env* e, const float* q_dev, const int8_t* sel_l
 }
 
 // hb_actor_fused_act followed by hb_env_step_packed as ONE launch: every workgroup of the policy kernel steps its own 128 games with
-// the moves it has just selected. Around the launch everything hb_env_step_packed does: pool join, refill cadence, counters, events.
+// the moves it has just selected. Around the launch what hb_env_step_packed does (pool join, counters, events) but no refill launch.
 int hb_actor_fused_act_step(hb_env* e, const uint32_t* obs_bits_dev, const int8_t* legal_dev, int64_t n_rows, int32_t obs_len,
                             const void* w1f_dev, const float* b1f_dev, const void* w2f_dev, const float* b2f_dev, const float* support_dev,
                             int32_t hidden, int32_t n_actions, int32_t n_atoms, float* q_dev, float epsilon, uint64_t seed, uint64_t draw,
@@ -567,7 +567,11 @@ int hb_actor_fused_act_step(hb_env* e, const uint32_t* obs_bits_dev, const int8_
                                           n_actions, n_atoms, q_dev, epsilon, seed, draw, first_game_id, actions_dev, dtype, a, *e->var,
                                           stream))
     return rc;
-  return refill_async(e, stream);
+  // No refill launch: the kernel's idle wavefronts have regenerated every pool deck flagged before this step (actor_fused.hip, env
+  // tail), so the only flags left standing are the ones this step's re-deals raised: one step old. The cadence counter says so, and a
+  // plain entry point called next still refills before any of those games can end (refill_period <= max_life steps after the deal).
+  e->since_refill = 1;
+  return HB_OK;
 }
 
 int hb_actor_fused_step_supported(const hb_env* e) { return e && !e->shuffled && hb::actor_env_fused_supported(*e->var) ? 1 : 0; }

@@ -922,11 +922,40 @@ __global__ __launch_bounds__(256) void env_kernel_shuf(const EnvArgs a) {
   env_wave_step<K, G, true>(a, g0, lane, lds + wave * env_lds_words<K, G>(), uid_in, wslot);
 }
 
-// Deck pool refill: regenerates next_deck[g] for every game whose flag is set. One wavefront scans 64 games
-// and shuffles the flagged ones one at a time with all lanes: lane j draws Philox4x32-10(j, episode, game id;
-// seed), key = 26 random bits | j (all distinct); its rank among the D keys comes from D v_readlane
-// broadcasts + compare + add-carry; card j of the canonical deck lands at position rank. `episode` is the
-// game's deal counter (state word 6), so deck(g, e) is a pure function of (seed, global game id, e).
+// One entry of the deck pool, written by all 64 lanes of the calling wavefront: next_deck[g] = the caller's deck of game g when
+// decks were set, else deck(g, episode): lane j draws Philox4x32-10(j, episode, game id; seed), key = 26 random bits | j (all
+// distinct); its rank among the D keys comes from D v_readlane broadcasts + compare + add-carry; card j of the canonical deck
+// lands at position rank. `episode_of()` is the game's deal counter (state word 6; asked for only when it is needed), so
+// deck(g, e) is a pure function of (seed, global game id, e). The one copy of the shuffle: refill_kernel and the one-kernel
+// actor's idle wavefronts (actor_fused.hip) both call it.
+template <class K, class EpisodeFn>
+__device__ __forceinline__ void refill_deck(const EnvArgs& a, long long g, int lane, EpisodeFn&& episode_of) {
+  uint8_t* dst = a.next_deck + g * NEXT_DECK_BYTES;
+  if (a.decks) {
+    if (lane < K::D) dst[lane] = a.decks[g * K::D + lane];
+  } else {
+    const uint32_t episode = episode_of();
+    const unsigned long long gid = static_cast<unsigned long long>(a.first_gid + g);
+    uint32_t out[4];
+    philox4x32_10(static_cast<uint32_t>(lane), episode, static_cast<uint32_t>(gid), static_cast<uint32_t>(gid >> 32),
+                  static_cast<uint32_t>(a.seed), static_cast<uint32_t>(a.seed >> 32), out);
+    const uint32_t key = (out[0] & ~63u) | static_cast<uint32_t>(lane);
+    int rank = 0;
+    static_for<K::D>([&](auto I) {
+      constexpr int i = decltype(I)::value;
+      const uint32_t ki = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(key), i));
+      rank += ki < key ? 1 : 0;
+    });
+    if (lane < K::D) {
+      const int col = lane / K::CPC, k = lane - col * K::CPC;
+      const int rk = k < 3 ? 0 : 1 + (k - 3) / 2;
+      dst[rank] = static_cast<uint8_t>(col * K::R + rk);
+    }
+  }
+}
+
+// Deck pool refill: regenerates next_deck[g] for every game whose flag is set. One wavefront scans 16 games
+// and shuffles the flagged ones one at a time with all lanes (refill_deck).
 template <class K>
 __global__ __launch_bounds__(256) void refill_kernel(const EnvArgs a) {
   constexpr int GR = 16;  // games scanned per wavefront: few enough that a wave rarely shuffles more than one deck
@@ -940,28 +969,7 @@ __global__ __launch_bounds__(256) void refill_kernel(const EnvArgs a) {
     const int src = __ffsll(static_cast<long long>(todo)) - 1;
     todo &= todo - 1;
     const long long g = g0 + src;
-    uint8_t* dst = a.next_deck + g * NEXT_DECK_BYTES;
-    if (a.decks) {
-      if (lane < K::D) dst[lane] = a.decks[g * K::D + lane];
-    } else {
-      const uint32_t episode = a.state[g * K::SW + 6];
-      const unsigned long long gid = static_cast<unsigned long long>(a.first_gid + g);
-      uint32_t out[4];
-      philox4x32_10(static_cast<uint32_t>(lane), episode, static_cast<uint32_t>(gid), static_cast<uint32_t>(gid >> 32),
-                    static_cast<uint32_t>(a.seed), static_cast<uint32_t>(a.seed >> 32), out);
-      const uint32_t key = (out[0] & ~63u) | static_cast<uint32_t>(lane);
-      int rank = 0;
-      static_for<K::D>([&](auto I) {
-        constexpr int i = decltype(I)::value;
-        const uint32_t ki = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(key), i));
-        rank += ki < key ? 1 : 0;
-      });
-      if (lane < K::D) {
-        const int col = lane / K::CPC, k = lane - col * K::CPC;
-        const int rk = k < 3 ? 0 : 1 + (k - 3) / 2;
-        dst[rank] = static_cast<uint8_t>(col * K::R + rk);
-      }
-    }
+    refill_deck<K>(a, g, lane, [&] { return a.state[g * K::SW + 6]; });
   }
   if (mine) a.refill[gi] = 0;
 }

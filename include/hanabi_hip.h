@@ -725,8 +725,9 @@ int hb_actor_fused_act_dt(const uint32_t* obs_bits_dev, const int8_t* legal_dev,
                           uint64_t seed, uint64_t draw, int64_t first_game_id, int32_t* actions_dev, int32_t dtype, void* stream);
 /* hb_actor_fused_act_dt followed by hb_env_step_packed(env, actions_dev, obs_bits_out_dev, NULL, legal_out_dev, ...) as ONE launch:
  * each workgroup of the policy kernel steps its own 128 games with the moves it has just selected, bit for bit what the two calls
- * compute. Around the launch it does what hb_env_step_packed does (deck-pool join and refill cadence, illegal-move and episode
- * counters, hb_env_set_profile_events timing). The observation / legal inputs may be the output buffers themselves (in place).
+ * compute. Around the launch it does what hb_env_step_packed does (deck-pool join, illegal-move and episode counters,
+ * hb_env_set_profile_events timing), except that no refill launch follows: the kernel regenerates the flagged pool decks itself,
+ * whatever the refill period and placement. The observation / legal inputs may be the output buffers themselves (in place).
  * n_rows must be the env's game count. Compiled for Hanabi-Full with 2 and 5 players (hb_actor_fused_step_supported); other
  * configurations: HB_ERR_INVALID.                                                                                           */
 int hb_actor_fused_act_step(hb_env* env, const uint32_t* obs_bits_dev, const int8_t* legal_dev, int64_t n_rows, int32_t obs_len,
