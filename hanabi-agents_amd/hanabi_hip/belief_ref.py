@@ -1,0 +1,218 @@
+"""The belief kernels restated in numpy (csrc/belief.hip, include/hanabi_hip.h): what the tests and the probe scripts hold
+hb_belief_select_soft, hb_belief_carry and hb_belief_score against, the same arithmetic written without anything of the kernels'
+layout. Nothing here runs on a GPU, and nothing in the package's own code paths calls it.
+"""
+
+_M32, _M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+
+
+def _philox_np(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on numpy arrays (broadcast) -> the four output words as uint64 arrays below 2^32."""
+    import numpy as np
+
+    c0, c1, c2, c3 = (np.asarray(x, np.uint64) & np.uint64(_M32) for x in np.broadcast_arrays(c0, c1, c2, c3))
+    k0, k1 = int(k0) & _M32, int(k1) & _M32
+    lo, sh = np.uint64(_M32), np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ np.uint64(k0), p1 & lo, (p0 >> sh) ^ c3 ^ np.uint64(k1), p0 & lo
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0, c1, c2, c3
+
+
+def belief_select_soft_ref(src_rows, det_rows, weights, hyp_moves, n_legal, actual, valid, p_table, replicas, seed, draw,
+                           first_row_id=0, details=False):
+    """hb_belief_select_soft restated in numpy, the same arithmetic in the same order (include/hanabi_hip.h): arrays shaped as
+    belief_select_soft's tensors (32-bit words of either sign) -> (rows uint32 [m * R, SW], weights uint32 [m * R], n_surv int32
+    [D, m], depth_used int32 [m], fallback uint8 [m], ess float32 [m]). details=True appends a dict of the intermediate figures:
+    lik float64 [m, K], q and W uint64 [m, K], T uint64 [m], target uint64 [m, R] and pick int64 [m, R] (-1: dead)."""
+    import numpy as np
+
+    u32 = lambda x: (np.asarray(x).astype(np.int64) & _M32).astype(np.uint32)
+    src, det = u32(src_rows), u32(det_rows)
+    (m, SW), R = src.shape, int(replicas)
+    hyp, nl, act = np.asarray(hyp_moves).astype(np.int64), np.asarray(n_legal).astype(np.int64), np.asarray(actual).astype(np.int64)
+    D, Kn = hyp.shape[0], hyp.shape[1]
+    assert hyp.shape == nl.shape == (D, Kn, m) and act.shape == (D, m) and det.shape == (m * Kn, SW)
+    w = u32(weights).reshape(m, Kn).astype(np.uint64)
+    table = np.asarray(p_table, np.float64)
+    A = table.shape[1] - 1
+    run = ((src[:, 0] >> np.uint32(19)) & np.uint32(3)) == 0
+    usable = np.ones((D, m), bool) if valid is None else np.asarray(valid).reshape(D, m) != 0
+    chain = np.cumprod(usable & run[None], axis=0).astype(bool)   # [D, m]: entry d is one of the root's L leading valid ones
+    L = chain.sum(0).astype(np.int32)
+    live = w != 0
+    lik, on = np.where(live, 1.0, 0.0), live.copy()
+    n_surv = np.zeros((D, m), np.int32)
+    for d in range(D):
+        match, n = hyp[d].T == act[d][:, None], nl[d].T   # [m, K]
+        factor = np.where((n >= 1) & (n <= A), table[np.where(match, 0, 1), np.clip(n, 0, A)], 0.0)
+        lik = np.where(chain[d][:, None] & live, lik * factor, lik)
+        on = on & match & chain[d][:, None]
+        n_surv[d] = on.sum(1)
+    mx = lik.max(1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(mx[:, None] > 0, np.floor(lik / mx[:, None] * 16777216.0), 0.0).astype(np.uint64)
+    W = w * q
+    T = W.sum(1, dtype=np.uint64)
+    Wf = W.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ess = np.where(T > 0, T.astype(np.float64) * T.astype(np.float64) / (Wf * Wf).sum(1), 0.0).astype(np.float32)
+    rid = [(int(first_row_id) + i) & _M64 for i in range(m)]
+    x = _philox_np(0x10000 + np.arange(R, dtype=np.uint64)[None], int(draw) & _M32, np.array([v & _M32 for v in rid], np.uint64)[:, None],
+                   np.array([v >> 32 for v in rid], np.uint64)[:, None], int(seed) & _M32, ((int(seed) >> 32) ^ (int(draw) >> 32)) & _M32)
+    u = (x[0] << np.uint64(32)) | x[1]   # [m, R]
+    target, pick = np.zeros((m, R), np.uint64), np.full((m, R), -1, np.int64)
+    rows, ow = np.empty((m * R, SW), np.uint32), np.zeros(m * R, np.uint32)
+    prefix = np.cumsum(W, axis=1, dtype=np.uint64)
+    for i in range(m):
+        if T[i] == 0:
+            rows[i * R:(i + 1) * R] = src[i]
+            continue
+        target[i] = np.array([(int(v) * int(T[i])) >> 64 for v in u[i]], np.uint64)
+        pick[i] = np.searchsorted(prefix[i], target[i], side="right")   # the first k whose inclusive prefix exceeds the target
+        rows[i * R:(i + 1) * R] = det[i * Kn + pick[i]]
+        ow[i * R:(i + 1) * R] = 1
+    out = (rows, ow, n_surv, L, np.where(L == 0, 2, 0).astype(np.uint8), ess)
+    return out + (dict(lik=lik, q=q, W=W, T=T, target=target, pick=pick),) if details else out
+
+
+def belief_carry_ref(cfg, cur_rows, old_rows, old_weights, own_slot, revealed, drew, seat, n_particles, seed, draw, first_row_id=0,
+                     draw_weight=True, details=False):
+    """hb_belief_carry restated in numpy, particle by particle in plain loops over Python lists (nothing of the kernel's layout):
+    arrays shaped as belief_carry's tensors (32-bit words of either sign) -> (rows uint32 [m * K, SW], weights uint32 [m * K]).
+    draw_weight=False is the deliberately wrong variant with g = 1 (step 5 left out) that the tests hold against the right one.
+    details=True appends a list with one dict per particle: `dead` (the step that killed it, or 0), `kept`, `g`, `ns`. Runs
+    without a GPU."""
+    import numpy as np
+
+    u32 = lambda x: (np.asarray(x).astype(np.int64) & _M32).astype(np.uint32)
+    cur, old = u32(cur_rows), u32(old_rows)
+    (m, SW), Kn, st = cur.shape, int(n_particles), int(seat)
+    ow = u32(old_weights)
+    slot_a, rev_a, drew_a = (np.asarray(x).astype(np.int64) for x in (own_slot, revealed, drew))
+    assert old.shape == (m * Kn, SW) and ow.shape == (m * Kn,) and slot_a.shape == rev_a.shape == drew_a.shape == (m,)
+    P, H, Rk, Cn = cfg.players, cfg.hand_size, cfg.ranks, cfg.colors
+    assert 0 <= st < P
+    D = Cn * sum(3 if r == 0 else 1 if r == Rk - 1 else 2 for r in range(Rk))
+    seed, draw = int(seed) & _M64, int(draw) & _M64
+    rows, w, info = np.empty((m * Kn, SW), np.uint32), np.zeros(m * Kn, np.uint32), []
+
+    def allows(kn, c):
+        return c // Rk < Cn and bool((kn >> (c // Rk)) & 1) and bool((kn >> (5 + c % Rk)) & 1)
+
+    for o in range(m * Kn):
+        i = o // Kn
+        rows[o] = cur[i]
+        note = dict(dead=0, kept=[], g=1, ns=[])
+        info.append(note)
+        w0, w1 = int(cur[i, 0]), int(cur[i, 1])
+        if ow[o] == 0 or (w0 >> 19) & 3 != 0 or (w0 >> 13) & 7 != st:   # 1. not usable
+            note["dead"] = 1
+            continue
+        old_hand, slot = int(old[o, 10 + st]), int(slot_a[i])
+        fields = [(old_hand >> (5 * s)) & 31 for s in range(H)]
+        if slot >= 0 and (slot >= H or fields[slot] != int(rev_a[i])):   # 2. the card I played is not the one that was seen
+            note["dead"] = 2
+            continue
+        kept = note["kept"] = [f for s, f in enumerate(fields) if s != slot and f != 31]
+        n_hand = min((w1 >> (15 + 3 * st)) & 7, H)
+        if len(kept) > n_hand:
+            note["dead"] = 2
+            continue
+        hand = int(cur[i, 10 + st])
+        know = int(cur[i, 10 + P + 2 * st]) | int(cur[i, 10 + P + 2 * st + 1]) << 32
+        deck_pos = D - min(w0 & 63, D)
+        deck = np.ascontiguousarray(cur[i, 10 + 3 * P:], dtype="<u4").view(np.uint8)
+        pool = [(hand >> (5 * l)) & 31 for l in range(n_hand)] + [int(deck[q]) for q in range(deck_pos, D)]   # 3.
+        free = [True] * len(pool)
+        new_hand = hand
+        for s, c in enumerate(kept):   # 4. the kept cards, where they now sit
+            where = [l for l in range(len(pool)) if free[l] and pool[l] == c]
+            if not where or not allows((know >> (12 * s)) & 0xFFF, c):
+                note["dead"] = 4
+                break
+            free[where[0]] = False
+            new_hand = (new_hand & ~(31 << (5 * s))) | (c << (5 * s))
+        if note["dead"]:
+            continue
+        g = 1
+        if draw_weight and int(drew_a[i]) >= 0:   # 5. the partner's draw
+            g += sum(1 for l in range(len(pool)) if free[l] and pool[l] == int(drew_a[i]))
+        note["g"] = g
+        rid = (int(first_row_id) + o) & _M64
+        rnd = _philox_np(128 + np.arange(64), draw & _M32, rid & _M32, rid >> 32, seed & _M32, ((seed >> 32) ^ (draw >> 32)) & _M32)
+        weight = g
+        for s in range(len(kept), n_hand):   # 6. the new slots: the determinizer's step
+            kn = (know >> (12 * s)) & 0xFFF
+            cand = [l for l in range(len(pool)) if free[l] and allows(kn, pool[l])]
+            note["ns"].append(len(cand))
+            if not cand:
+                note["dead"] = 6
+                break
+            pick = cand[(int(rnd[0][s]) * len(cand)) >> 32]
+            free[pick] = False
+            weight *= len(cand)
+            new_hand = (new_hand & ~(31 << (5 * s))) | (pool[pick] << (5 * s))
+        if note["dead"]:
+            continue
+        rest = sorted((l for l in range(len(pool)) if free[l]), key=lambda l: (int(rnd[1][l]) & ~63) | l)   # 7. the deck
+        rows[o, 10 + st] = new_hand
+        bytes_out = rows[o, 10 + 3 * P:].view(np.uint8)
+        for j, l in enumerate(rest):
+            bytes_out[deck_pos + j] = pool[l]
+        w[o] = weight & _M32
+    return (rows, w, info) if details else (rows, w)
+
+
+def belief_score_ref(cfg, true_rows, det_rows, weights, seat, replicas):
+    """hb_belief_score restated in numpy, row by row and replica by replica in plain loops (nothing of the kernel's layout): arrays
+    shaped as belief_score's tensors (32-bit words of either sign) -> a dict of numpy arrays: truth int8 [m, H], hit int64
+    [m, H], joint, wsum int64 [m], n_live int32 [m], counts int64 [m, H, NC], prior int8 [m, H, NC]. Runs without a GPU;
+    `BeliefScore(**belief_score_ref(...))` gives the figures."""
+    import numpy as np
+
+    u32 = lambda x: (np.asarray(x).astype(np.int64) & _M32).astype(np.uint32)
+    rows, det = u32(true_rows), u32(det_rows)
+    (m, SW), R = rows.shape, int(replicas)
+    w = u32(weights).reshape(m, R)
+    assert det.shape == (m * R, SW)
+    P, H, Rk, NC = cfg.players, cfg.hand_size, cfg.ranks, cfg.colors * cfg.ranks
+    D = cfg.colors * sum(3 if r == 0 else 1 if r == Rk - 1 else 2 for r in range(Rk))
+    out = dict(truth=np.full((m, H), -1, np.int8), hit=np.zeros((m, H), np.int64), joint=np.zeros(m, np.int64),
+               wsum=np.zeros(m, np.int64), n_live=np.zeros(m, np.int32), counts=np.zeros((m, H, NC), np.int64),
+               prior=np.zeros((m, H, NC), np.int8))
+    for i in range(m):
+        w0, w1 = int(rows[i, 0]), int(rows[i, 1])
+        st = int(seat) if int(seat) >= 0 else (w0 >> 13) & 7
+        if (w0 >> 19) & 3 != 0 or st >= P:
+            continue
+        hand = int(rows[i, 10 + st])
+        know = int(rows[i, 10 + P + 2 * st]) | int(rows[i, 10 + P + 2 * st + 1]) << 32
+        n = min((w1 >> (15 + 3 * st)) & 7, H)
+        true = [(hand >> (5 * s)) & 31 for s in range(n)]
+        deck = np.ascontiguousarray(rows[i, 10 + 3 * P:], dtype="<u4").view(np.uint8)
+        pool = true + [int(deck[q]) for q in range(D - min(w0 & 63, D), D)]
+        for s in range(n):
+            out["truth"][i, s] = true[s]
+            kn = (know >> (12 * s)) & 0xFFF
+            for c in range(NC):
+                if (kn >> (c // Rk)) & 1 and (kn >> (5 + c % Rk)) & 1:
+                    out["prior"][i, s, c] = pool.count(c)
+        for r in range(R):
+            wr = int(w[i, r])
+            if wr == 0:
+                continue
+            out["wsum"][i] += wr
+            out["n_live"][i] += 1
+            word = int(det[i * R + r, 10 + st])
+            cards = [(word >> (5 * s)) & 31 for s in range(n)]
+            for s in range(n):
+                if cards[s] < NC:
+                    out["counts"][i, s, cards[s]] += wr
+            if all(c < NC and c == t for c, t in zip(cards, true)):
+                out["joint"][i] += wr
+        for s in range(n):
+            if true[s] < NC:
+                out["hit"][i, s] = out["counts"][i, s, true[s]]
+    return out

@@ -230,16 +230,16 @@ class OffBeliefSession(SelfPlaySession):
             rows, h, partner=self.belief_policy[1 - seat], seat=seat, replicas=1, oversample=self.oversample, seed=self.belief_seed,
             draw=t, partner_seed=self.belief_seed, first_game_id=env.first_game_id, first_row_id=env.first_game_id,
             out=(self._det_rows, self._det_w), epsilon=self.belief_epsilon)
-        n_surv, used, fb = got[2:5]
+        used, fb = got.depth_used, got.fallback
         self.belief_forwards += min(h.depth, h.filled) * self.oversample
-        self.last_belief = (n_surv, used, fb)
+        self.last_belief = (got.n_surv, used, fb)
         # fallback 0 and 1 are running rows by construction (hb_belief_select_depth: a finished row has no usable entry)
         # (the soft filter: fallback is 0 with a usable move and 2 without, never 1)
         cond = fb == 0
         if self.belief_epsilon is not None:
-            self._ess += (got[5].double() * cond).sum()
-        surv = n_surv.gather(0, (used.long() - 1).clamp(min=0).view(1, -1)).view(-1)
-        self._level += torch.stack([cond.sum(), (fb == 1).sum(), (running(rows) & (fb == 2)).sum(), (surv * cond).sum(), used.sum()])
+            self._ess += (got.ess.double() * cond).sum()
+        self._level += torch.stack([cond.sum(), (fb == 1).sum(), (running(rows) & (fb == 2)).sum(), (got.survivors() * cond).sum(),
+                                    used.sum()])
 
     def _score(self, rows, seat):
         """score_belief: the fictitious states in _det_rows / _det_w against the real `rows`, one replica per game."""

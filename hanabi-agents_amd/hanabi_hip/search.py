@@ -19,36 +19,37 @@
   `RolloutSearch.confirm` re-measures {blueprint move, challenger} of every root on fresh replicas: screen, then confirm.
   There is one rollout path: `run` is `run_candidates` with every legal action as the candidate of slot = uid, and both go
   through one cache of rollout envs and buffers keyed (m, C, replicas).
-* `ConditionedDeterminizer.sample` conditions that belief on the partner's last move: `replicas * oversample` candidates, the
-  state the partner moved from with each candidate hand spliced in (hb_belief_splice), the partner's `eval_moves` on those with
-  the real turn's Philox keys, and the first `replicas` candidates under which it makes the move it made (hb_belief_select).
-  `history=` hands it to run / run_candidates / confirm; `SearchPlayer(condition=True)` keeps the history itself (2 players).
-* `ConditionedDeterminizer.sample_history` conditions it on the partner's last `depth` moves, kept in a `PartnerHistory`: the
-  same candidates carried back to every earlier state the partner moved from (hb_belief_splice_alive: the cards of that older
-  hand I still hold are a prefix of the candidate's hand, the others are public), the partner's `eval_moves` on each, and one
-  hb_belief_select_depth. `SearchPlayer(condition=True, depth=L)` keeps the stack itself. `PartnerHistory.advance` is one turn
-  of that bookkeeping (own move, re-dealt games, push) in one kernel call (hb_belief_history_step): what a training env, whose
-  games end and are dealt anew at different steps, keeps its histories with (hanabi_hip.obl, off-belief learning level 2+).
+* `ConditionedDeterminizer.sample_history` conditions that belief on the partner's last `depth` moves, kept in a
+  `PartnerHistory`: `replicas * oversample` candidates, carried back to every state the partner moved from
+  (hb_belief_splice_alive: the cards of that older hand I still hold are a prefix of the candidate's hand, the others are
+  public), the partner's `eval_moves` on each with the real turn's Philox keys, and one hb_belief_select_depth: the first
+  `replicas` candidates under which it makes the moves it made. It is the one conditioned-sampling path, and `BeliefSample` its
+  one result; `.sample` (the last move alone) is the same path on a `LastMove`, the history of one entry, and so is the tuple
+  `history=` that run / run_candidates / confirm take. `SearchPlayer(condition=True[, depth=L])` keeps the history itself (2
+  players). `PartnerHistory.advance` is one turn of that bookkeeping (own move, re-dealt games, push) in one kernel call
+  (hb_belief_history_step): what a training env, whose games end and are dealt anew at different steps, keeps its histories
+  with (hanabi_hip.obl, off-belief learning level 2+).
 * `epsilon=e` (to `ConditionedDeterminizer.sample` / `sample_history`, `RolloutSearch`, `SearchPlayer(condition=True)`; default
   None: the exact-match filters above, unchanged) reads the partner as epsilon-greedy on its policy: every candidate keeps a
   likelihood (`soft_table`: 1 - e + e / n per reproduced move, e / n per missed one, n = the legal moves of the hypothetical
-  state) and the replicas are drawn in proportion to importance weight times likelihood (hb_belief_select_soft;
-  `belief_select_soft_ref` is its numpy restatement). No depth fallback; the results carry the candidates' effective sample size.
-* `belief_score` (hb_belief_score; `belief_score_ref` is its numpy restatement) scores any of these beliefs against the cards the
-  seat really holds: per slot the weight of the replicas that hold the true card, for the whole hand, and next to the card-counting
-  prior, in exact integers; `BeliefScore` forms the hit rates and cross-entropies. `score_belief=True` (`RolloutSearch`,
+  state) and the replicas are drawn in proportion to importance weight times likelihood (hb_belief_select_soft). No depth
+  fallback; the results carry the candidates' effective sample size.
+* `belief_score` (hb_belief_score) scores any of these beliefs against the cards the seat really holds: per slot the weight of
+  the replicas that hold the true card, for the whole hand, and next to the card-counting prior, in exact integers; `BeliefScore` forms the hit rates and cross-entropies. `score_belief=True` (`RolloutSearch`,
   `SearchPlayer`; default False: nothing is computed) scores every search's replicas; `SearchPlayer.belief_stats()` gives the means.
 * `TrackedBelief` (`SearchPlayer(condition=True, track=True)`, 2 players) tracks the belief across turns instead of rebuilding it:
-  the hand samples of my last turn are carried to this one (hb_belief_carry; `belief_carry`, `belief_carry_ref` its numpy
-  restatement), weighed by the one move the partner has made since and resampled (hb_belief_select_soft); a root whose samples run
-  out starts over from the conditioned belief above.
+  the hand samples of my last turn are carried to this one (hb_belief_carry; `belief_carry`), weighed by the one move the
+  partner has made since and resampled (hb_belief_select_soft); a root whose samples run out starts over from the conditioned
+  belief above.
 * `SearchPlayer` is an agent for `Evaluator.run`: the blueprint's move unless the search finds one that is better by more than
   `threshold` and, with `z` / `confirm_replicas`, by more than z standard errors of the paired difference.
+* The kernels' numpy restatements (`belief_select_soft_ref`, `belief_carry_ref`, `belief_score_ref`) live in hanabi_hip.belief_ref.
 
 Colour-shuffled envs are refused: the rollout env's game ids would draw other permutations than the source's.
 """
 import ctypes as C
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -78,6 +79,18 @@ def _bufs(dev, given, *specs):
         assert t.shape == tuple(shape) and t.dtype == dtype and t.is_contiguous(), \
             f"expected a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}"
     return tuple(given)
+
+
+def _reads(dev, tensors, *specs, one_gpu=None):
+    """_bufs' check of the tensors a belief kernel reads; the last may be None (an optional mask) and is then left out. one_gpu:
+    the name of a kernel whose wrapper also refuses a tensor that is not on the GPU `dev`."""
+    if tensors[-1] is None:
+        tensors, specs = tensors[:-1], specs[:-1]
+    _bufs(dev, tensors, *specs)
+    if one_gpu is not None:
+        for t in tensors:
+            if not t.is_cuda or t.device != dev:
+                raise K.HbError(f"{one_gpu} reads tensors of one GPU (there is no CPU path)")
 
 
 def _ask(agent, env, seed, draw, out, scratch):
@@ -162,7 +175,7 @@ def belief_splice(cfg, prev_rows, det_rows, seat, n_cand, out=None):
     row taken from candidate (i, k)."""
     m, SW = prev_rows.shape
     Kn, dev = int(n_cand), prev_rows.device
-    _bufs(dev, (prev_rows, det_rows), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32))
+    _reads(dev, (prev_rows, det_rows), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32))
     out, = _bufs(dev, None if out is None else (out,), ((max(Kn, 0), m, SW), torch.int32))
     with torch.cuda.device(dev):
         K.check(K.lib().hb_belief_splice(C.byref(cfg), K.dptr(prev_rows), K.dptr(det_rows), m, int(seat), Kn, K.dptr(out),
@@ -176,10 +189,8 @@ def belief_select(cfg, src_rows, det_rows, weights, hyp_moves, actual, valid, re
     [m * R] int32, n_surv [m] int32, fallback [m] uint8). `out`: an optional tuple of these four buffers to write into."""
     m, SW = src_rows.shape
     Kn, R, dev = hyp_moves.shape[0], int(replicas), src_rows.device
-    _bufs(dev, (src_rows, det_rows, weights, hyp_moves, actual), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32),
-          ((m * Kn,), torch.int32), ((Kn, m), torch.int32), ((m,), torch.int32))
-    if valid is not None:
-        _bufs(dev, (valid,), ((m,), torch.uint8))
+    _reads(dev, (src_rows, det_rows, weights, hyp_moves, actual, valid), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32),
+           ((m * Kn,), torch.int32), ((Kn, m), torch.int32), ((m,), torch.int32), ((m,), torch.uint8))
     n = m * max(R, 0)
     rows, w, n_surv, fallback = _bufs(dev, out, ((n, SW), torch.int32), ((n,), torch.int32), ((m,), torch.int32), ((m,), torch.uint8))
     with torch.cuda.device(dev):
@@ -196,9 +207,7 @@ def belief_splice_alive(cfg, prev_rows, alive, det_rows, seat, n_cand, out=None)
     taken from candidate (i, k)'s hand, in order."""
     m, SW = prev_rows.shape
     Kn, dev = int(n_cand), prev_rows.device
-    _bufs(dev, (prev_rows, det_rows), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32))
-    if alive is not None:
-        _bufs(dev, (alive,), ((m,), torch.uint8))
+    _reads(dev, (prev_rows, det_rows, alive), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32), ((m,), torch.uint8))
     out, = _bufs(dev, None if out is None else (out,), ((max(Kn, 0), m, SW), torch.int32))
     with torch.cuda.device(dev):
         K.check(K.lib().hb_belief_splice_alive(C.byref(cfg), K.dptr(prev_rows), K.dptr(alive), K.dptr(det_rows), m, int(seat), Kn,
@@ -215,10 +224,8 @@ def belief_select_depth(cfg, src_rows, det_rows, weights, hyp_moves, actual, val
     if hyp_moves.dim() != 3:
         raise ValueError(f"hyp_moves has shape [depth, K, m], got {tuple(hyp_moves.shape)}")
     D, Kn, R, dev = hyp_moves.shape[0], hyp_moves.shape[1], int(replicas), src_rows.device
-    _bufs(dev, (src_rows, det_rows, weights, hyp_moves, actual), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32),
-          ((m * Kn,), torch.int32), ((D, Kn, m), torch.int32), ((D, m), torch.int32))
-    if valid is not None:
-        _bufs(dev, (valid,), ((D, m), torch.uint8))
+    _reads(dev, (src_rows, det_rows, weights, hyp_moves, actual, valid), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32),
+           ((m * Kn,), torch.int32), ((D, Kn, m), torch.int32), ((D, m), torch.int32), ((D, m), torch.uint8))
     n = m * max(R, 0)
     rows, w, n_surv, depth_used, fallback = _bufs(dev, out, ((n, SW), torch.int32), ((n,), torch.int32), ((D, m), torch.int32),
                                                   ((m,), torch.int32), ((m,), torch.uint8))
@@ -265,14 +272,9 @@ def belief_select_soft(cfg, src_rows, det_rows, weights, hyp_moves, n_legal, act
     if not 1 <= Kn <= MAX_SOFT_CANDIDATES:
         raise ValueError(f"the soft filter takes 1..{MAX_SOFT_CANDIDATES} candidates per root, got {Kn}")
     A = K.lib().hb_num_actions(C.byref(cfg))
-    _bufs(dev, (src_rows, det_rows, weights, hyp_moves, n_legal, actual, p_table), ((m, SW), torch.int32), ((m * Kn, SW), torch.int32),
-          ((m * Kn,), torch.int32), ((D, Kn, m), torch.int32), ((D, Kn, m), torch.int32), ((D, m), torch.int32),
-          ((2, A + 1), torch.float64))
-    if valid is not None:
-        _bufs(dev, (valid,), ((D, m), torch.uint8))
-    for t in (src_rows, det_rows, weights, hyp_moves, n_legal, actual, p_table) + (() if valid is None else (valid,)):
-        if not t.is_cuda or t.device != dev:
-            raise K.HbError("hb_belief_select_soft reads tensors of one GPU (there is no CPU path)")
+    _reads(dev, (src_rows, det_rows, weights, hyp_moves, n_legal, actual, p_table, valid), ((m, SW), torch.int32),
+           ((m * Kn, SW), torch.int32), ((m * Kn,), torch.int32), ((D, Kn, m), torch.int32), ((D, Kn, m), torch.int32),
+           ((D, m), torch.int32), ((2, A + 1), torch.float64), ((D, m), torch.uint8), one_gpu="hb_belief_select_soft")
     n = m * max(R, 0)
     rows, w, n_surv, depth_used, fallback, ess = _bufs(dev, out, ((n, SW), torch.int32), ((n,), torch.int32), ((D, m), torch.int32),
                                                        ((m,), torch.int32), ((m,), torch.uint8), ((m,), torch.float32))
@@ -284,78 +286,7 @@ def belief_select_soft(cfg, src_rows, det_rows, weights, hyp_moves, n_legal, act
     return rows, w, n_surv, depth_used, fallback, ess
 
 
-_M32, _M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
-
-
-def _philox_np(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10 on numpy arrays (broadcast) -> the four output words as uint64 arrays below 2^32."""
-    import numpy as np
-
-    c0, c1, c2, c3 = (np.asarray(x, np.uint64) & np.uint64(_M32) for x in np.broadcast_arrays(c0, c1, c2, c3))
-    k0, k1 = int(k0) & _M32, int(k1) & _M32
-    lo, sh = np.uint64(_M32), np.uint64(32)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ np.uint64(k0), p1 & lo, (p0 >> sh) ^ c3 ^ np.uint64(k1), p0 & lo
-        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
-    return c0, c1, c2, c3
-
-
-def belief_select_soft_ref(src_rows, det_rows, weights, hyp_moves, n_legal, actual, valid, p_table, replicas, seed, draw,
-                           first_row_id=0, details=False):
-    """hb_belief_select_soft restated in numpy, the same arithmetic in the same order (include/hanabi_hip.h): arrays shaped as
-    belief_select_soft's tensors (32-bit words of either sign) -> (rows uint32 [m * R, SW], weights uint32 [m * R], n_surv int32
-    [D, m], depth_used int32 [m], fallback uint8 [m], ess float32 [m]). details=True appends a dict of the intermediate figures:
-    lik float64 [m, K], q and W uint64 [m, K], T uint64 [m], target uint64 [m, R] and pick int64 [m, R] (-1: dead)."""
-    import numpy as np
-
-    u32 = lambda x: (np.asarray(x).astype(np.int64) & _M32).astype(np.uint32)
-    src, det = u32(src_rows), u32(det_rows)
-    (m, SW), R = src.shape, int(replicas)
-    hyp, nl, act = np.asarray(hyp_moves).astype(np.int64), np.asarray(n_legal).astype(np.int64), np.asarray(actual).astype(np.int64)
-    D, Kn = hyp.shape[0], hyp.shape[1]
-    assert hyp.shape == nl.shape == (D, Kn, m) and act.shape == (D, m) and det.shape == (m * Kn, SW)
-    w = u32(weights).reshape(m, Kn).astype(np.uint64)
-    table = np.asarray(p_table, np.float64)
-    A = table.shape[1] - 1
-    run = ((src[:, 0] >> np.uint32(19)) & np.uint32(3)) == 0
-    usable = np.ones((D, m), bool) if valid is None else np.asarray(valid).reshape(D, m) != 0
-    chain = np.cumprod(usable & run[None], axis=0).astype(bool)   # [D, m]: entry d is one of the root's L leading valid ones
-    L = chain.sum(0).astype(np.int32)
-    live = w != 0
-    lik, on = np.where(live, 1.0, 0.0), live.copy()
-    n_surv = np.zeros((D, m), np.int32)
-    for d in range(D):
-        match, n = hyp[d].T == act[d][:, None], nl[d].T   # [m, K]
-        factor = np.where((n >= 1) & (n <= A), table[np.where(match, 0, 1), np.clip(n, 0, A)], 0.0)
-        lik = np.where(chain[d][:, None] & live, lik * factor, lik)
-        on = on & match & chain[d][:, None]
-        n_surv[d] = on.sum(1)
-    mx = lik.max(1)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        q = np.where(mx[:, None] > 0, np.floor(lik / mx[:, None] * 16777216.0), 0.0).astype(np.uint64)
-    W = w * q
-    T = W.sum(1, dtype=np.uint64)
-    Wf = W.astype(np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        ess = np.where(T > 0, T.astype(np.float64) * T.astype(np.float64) / (Wf * Wf).sum(1), 0.0).astype(np.float32)
-    rid = [(int(first_row_id) + i) & _M64 for i in range(m)]
-    x = _philox_np(0x10000 + np.arange(R, dtype=np.uint64)[None], int(draw) & _M32, np.array([v & _M32 for v in rid], np.uint64)[:, None],
-                   np.array([v >> 32 for v in rid], np.uint64)[:, None], int(seed) & _M32, ((int(seed) >> 32) ^ (int(draw) >> 32)) & _M32)
-    u = (x[0] << np.uint64(32)) | x[1]   # [m, R]
-    target, pick = np.zeros((m, R), np.uint64), np.full((m, R), -1, np.int64)
-    rows, ow = np.empty((m * R, SW), np.uint32), np.zeros(m * R, np.uint32)
-    prefix = np.cumsum(W, axis=1, dtype=np.uint64)
-    for i in range(m):
-        if T[i] == 0:
-            rows[i * R:(i + 1) * R] = src[i]
-            continue
-        target[i] = np.array([(int(v) * int(T[i])) >> 64 for v in u[i]], np.uint64)
-        pick[i] = np.searchsorted(prefix[i], target[i], side="right")   # the first k whose inclusive prefix exceeds the target
-        rows[i * R:(i + 1) * R] = det[i * Kn + pick[i]]
-        ow[i * R:(i + 1) * R] = 1
-    out = (rows, ow, n_surv, L, np.where(L == 0, 2, 0).astype(np.uint8), ess)
-    return out + (dict(lik=lik, q=q, W=W, T=T, target=target, pick=pick),) if details else out
+_M64 = 0xFFFFFFFFFFFFFFFF
 
 
 def belief_carry(cfg, cur_rows, old_rows, old_weights, own_slot, revealed, drew, seat, n_particles, seed, draw, first_row_id=0,
@@ -376,105 +307,14 @@ def belief_carry(cfg, cur_rows, old_rows, old_weights, own_slot, revealed, drew,
     if not 0 <= int(seat) < cfg.players:
         raise ValueError(f"seat {seat} out of range for {cfg.players} players (the observer, who is to act)")
     n = m * Kn
-    _bufs(dev, (cur, old_rows, old_weights, own_slot, revealed, drew), ((m, SW), torch.int32), ((n, SW), torch.int32), ((n,), torch.int32),
-          ((m,), torch.int32), ((m,), torch.int32), ((m,), torch.int32))
-    for t in (cur, old_rows, old_weights, own_slot, revealed, drew):
-        if not t.is_cuda or t.device != dev:
-            raise K.HbError("hb_belief_carry reads tensors of one GPU (there is no CPU path)")
+    _reads(dev, (cur, old_rows, old_weights, own_slot, revealed, drew), ((m, SW), torch.int32), ((n, SW), torch.int32), ((n,), torch.int32),
+           ((m,), torch.int32), ((m,), torch.int32), ((m,), torch.int32), one_gpu="hb_belief_carry")
     rows, w = _bufs(dev, out, ((n, SW), torch.int32), ((n,), torch.int32))
     with torch.cuda.device(dev):
         K.check(K.lib().hb_belief_carry(C.byref(cfg), K.dptr(cur), K.dptr(old_rows), K.dptr(old_weights), K.dptr(own_slot),
                                         K.dptr(revealed), K.dptr(drew), m, int(seat), Kn, int(seed) & _M64, int(draw) & _M64,
                                         int(first_row_id), K.dptr(rows), K.dptr(w), K.current_stream()))
     return rows, w
-
-
-def belief_carry_ref(cfg, cur_rows, old_rows, old_weights, own_slot, revealed, drew, seat, n_particles, seed, draw, first_row_id=0,
-                     draw_weight=True, details=False):
-    """hb_belief_carry restated in numpy, particle by particle in plain loops over Python lists (nothing of the kernel's layout):
-    arrays shaped as belief_carry's tensors (32-bit words of either sign) -> (rows uint32 [m * K, SW], weights uint32 [m * K]).
-    draw_weight=False is the deliberately wrong variant with g = 1 (step 5 left out) that the tests hold against the right one.
-    details=True appends a list with one dict per particle: `dead` (the step that killed it, or 0), `kept`, `g`, `ns`. Runs
-    without a GPU."""
-    import numpy as np
-
-    u32 = lambda x: (np.asarray(x).astype(np.int64) & _M32).astype(np.uint32)
-    cur, old = u32(cur_rows), u32(old_rows)
-    (m, SW), Kn, st = cur.shape, int(n_particles), int(seat)
-    ow = u32(old_weights)
-    slot_a, rev_a, drew_a = (np.asarray(x).astype(np.int64) for x in (own_slot, revealed, drew))
-    assert old.shape == (m * Kn, SW) and ow.shape == (m * Kn,) and slot_a.shape == rev_a.shape == drew_a.shape == (m,)
-    P, H, Rk, Cn = cfg.players, cfg.hand_size, cfg.ranks, cfg.colors
-    assert 0 <= st < P
-    D = Cn * sum(3 if r == 0 else 1 if r == Rk - 1 else 2 for r in range(Rk))
-    seed, draw = int(seed) & _M64, int(draw) & _M64
-    rows, w, info = np.empty((m * Kn, SW), np.uint32), np.zeros(m * Kn, np.uint32), []
-
-    def allows(kn, c):
-        return c // Rk < Cn and bool((kn >> (c // Rk)) & 1) and bool((kn >> (5 + c % Rk)) & 1)
-
-    for o in range(m * Kn):
-        i = o // Kn
-        rows[o] = cur[i]
-        note = dict(dead=0, kept=[], g=1, ns=[])
-        info.append(note)
-        w0, w1 = int(cur[i, 0]), int(cur[i, 1])
-        if ow[o] == 0 or (w0 >> 19) & 3 != 0 or (w0 >> 13) & 7 != st:   # 1. not usable
-            note["dead"] = 1
-            continue
-        old_hand, slot = int(old[o, 10 + st]), int(slot_a[i])
-        fields = [(old_hand >> (5 * s)) & 31 for s in range(H)]
-        if slot >= 0 and (slot >= H or fields[slot] != int(rev_a[i])):   # 2. the card I played is not the one that was seen
-            note["dead"] = 2
-            continue
-        kept = note["kept"] = [f for s, f in enumerate(fields) if s != slot and f != 31]
-        n_hand = min((w1 >> (15 + 3 * st)) & 7, H)
-        if len(kept) > n_hand:
-            note["dead"] = 2
-            continue
-        hand = int(cur[i, 10 + st])
-        know = int(cur[i, 10 + P + 2 * st]) | int(cur[i, 10 + P + 2 * st + 1]) << 32
-        deck_pos = D - min(w0 & 63, D)
-        deck = np.ascontiguousarray(cur[i, 10 + 3 * P:], dtype="<u4").view(np.uint8)
-        pool = [(hand >> (5 * l)) & 31 for l in range(n_hand)] + [int(deck[q]) for q in range(deck_pos, D)]   # 3.
-        free = [True] * len(pool)
-        new_hand = hand
-        for s, c in enumerate(kept):   # 4. the kept cards, where they now sit
-            where = [l for l in range(len(pool)) if free[l] and pool[l] == c]
-            if not where or not allows((know >> (12 * s)) & 0xFFF, c):
-                note["dead"] = 4
-                break
-            free[where[0]] = False
-            new_hand = (new_hand & ~(31 << (5 * s))) | (c << (5 * s))
-        if note["dead"]:
-            continue
-        g = 1
-        if draw_weight and int(drew_a[i]) >= 0:   # 5. the partner's draw
-            g += sum(1 for l in range(len(pool)) if free[l] and pool[l] == int(drew_a[i]))
-        note["g"] = g
-        rid = (int(first_row_id) + o) & _M64
-        rnd = _philox_np(128 + np.arange(64), draw & _M32, rid & _M32, rid >> 32, seed & _M32, ((seed >> 32) ^ (draw >> 32)) & _M32)
-        weight = g
-        for s in range(len(kept), n_hand):   # 6. the new slots: the determinizer's step
-            kn = (know >> (12 * s)) & 0xFFF
-            cand = [l for l in range(len(pool)) if free[l] and allows(kn, pool[l])]
-            note["ns"].append(len(cand))
-            if not cand:
-                note["dead"] = 6
-                break
-            pick = cand[(int(rnd[0][s]) * len(cand)) >> 32]
-            free[pick] = False
-            weight *= len(cand)
-            new_hand = (new_hand & ~(31 << (5 * s))) | (pool[pick] << (5 * s))
-        if note["dead"]:
-            continue
-        rest = sorted((l for l in range(len(pool)) if free[l]), key=lambda l: (int(rnd[1][l]) & ~63) | l)   # 7. the deck
-        rows[o, 10 + st] = new_hand
-        bytes_out = rows[o, 10 + 3 * P:].view(np.uint8)
-        for j, l in enumerate(rest):
-            bytes_out[deck_pos + j] = pool[l]
-        w[o] = weight & _M32
-    return (rows, w, info) if details else (rows, w)
 
 
 def belief_score(cfg, true_rows, det_rows, weights, seat, replicas, counts=False, out=None):
@@ -486,10 +326,8 @@ def belief_score(cfg, true_rows, det_rows, weights, seat, replicas, counts=False
     m, SW = true_rows.shape
     R, dev = int(replicas), true_rows.device
     H, NC, n = cfg.hand_size, cfg.colors * cfg.ranks, m * max(int(replicas), 0)
-    _bufs(dev, (true_rows, det_rows, weights), ((m, SW), torch.int32), ((n, SW), torch.int32), ((n,), torch.int32))
-    for t in (true_rows, det_rows, weights):
-        if not t.is_cuda or t.device != dev:
-            raise K.HbError("hb_belief_score reads tensors of one GPU (there is no CPU path)")
+    _reads(dev, (true_rows, det_rows, weights), ((m, SW), torch.int32), ((n, SW), torch.int32), ((n,), torch.int32),
+           one_gpu="hb_belief_score")
     specs = (((m, H), torch.int8), ((m, H), torch.int64), ((m,), torch.int64), ((m,), torch.int64), ((m,), torch.int32),
              ((m, H, NC), torch.int8)) + ((((m, H, NC), torch.int64),) if counts else ())
     bufs = _bufs(dev, out, *specs)
@@ -500,59 +338,6 @@ def belief_score(cfg, true_rows, det_rows, weights, seat, replicas, counts=False
                                         K.dptr(truth), K.dptr(hit), K.dptr(joint), K.dptr(wsum), K.dptr(n_live), K.dptr(tally),
                                         K.dptr(prior), K.current_stream()))
     return BeliefScore(truth, hit, joint, wsum, n_live, prior, tally)
-
-
-def belief_score_ref(cfg, true_rows, det_rows, weights, seat, replicas):
-    """hb_belief_score restated in numpy, row by row and replica by replica in plain loops (nothing of the kernel's layout): arrays
-    shaped as belief_score's tensors (32-bit words of either sign) -> a dict of numpy arrays: truth int8 [m, H], hit int64
-    [m, H], joint, wsum int64 [m], n_live int32 [m], counts int64 [m, H, NC], prior int8 [m, H, NC]. Runs without a GPU;
-    `BeliefScore(**belief_score_ref(...))` gives the figures."""
-    import numpy as np
-
-    u32 = lambda x: (np.asarray(x).astype(np.int64) & _M32).astype(np.uint32)
-    rows, det = u32(true_rows), u32(det_rows)
-    (m, SW), R = rows.shape, int(replicas)
-    w = u32(weights).reshape(m, R)
-    assert det.shape == (m * R, SW)
-    P, H, Rk, NC = cfg.players, cfg.hand_size, cfg.ranks, cfg.colors * cfg.ranks
-    D = cfg.colors * sum(3 if r == 0 else 1 if r == Rk - 1 else 2 for r in range(Rk))
-    out = dict(truth=np.full((m, H), -1, np.int8), hit=np.zeros((m, H), np.int64), joint=np.zeros(m, np.int64),
-               wsum=np.zeros(m, np.int64), n_live=np.zeros(m, np.int32), counts=np.zeros((m, H, NC), np.int64),
-               prior=np.zeros((m, H, NC), np.int8))
-    for i in range(m):
-        w0, w1 = int(rows[i, 0]), int(rows[i, 1])
-        st = int(seat) if int(seat) >= 0 else (w0 >> 13) & 7
-        if (w0 >> 19) & 3 != 0 or st >= P:
-            continue
-        hand = int(rows[i, 10 + st])
-        know = int(rows[i, 10 + P + 2 * st]) | int(rows[i, 10 + P + 2 * st + 1]) << 32
-        n = min((w1 >> (15 + 3 * st)) & 7, H)
-        true = [(hand >> (5 * s)) & 31 for s in range(n)]
-        deck = np.ascontiguousarray(rows[i, 10 + 3 * P:], dtype="<u4").view(np.uint8)
-        pool = true + [int(deck[q]) for q in range(D - min(w0 & 63, D), D)]
-        for s in range(n):
-            out["truth"][i, s] = true[s]
-            kn = (know >> (12 * s)) & 0xFFF
-            for c in range(NC):
-                if (kn >> (c // Rk)) & 1 and (kn >> (5 + c % Rk)) & 1:
-                    out["prior"][i, s, c] = pool.count(c)
-        for r in range(R):
-            wr = int(w[i, r])
-            if wr == 0:
-                continue
-            out["wsum"][i] += wr
-            out["n_live"][i] += 1
-            word = int(det[i * R + r, 10 + st])
-            cards = [(word >> (5 * s)) & 31 for s in range(n)]
-            for s in range(n):
-                if cards[s] < NC:
-                    out["counts"][i, s, cards[s]] += wr
-            if all(c < NC and c == t for c, t in zip(cards, true)):
-                out["joint"][i] += wr
-        for s in range(n):
-            if true[s] < NC:
-                out["hit"][i, s] = out["counts"][i, s, true[s]]
-    return out
 
 
 def belief_figures(sums):
@@ -689,21 +474,49 @@ def last_move_uid(cfg, rows):
     return torch.where((w2 & 1) != 0, uid, -1).to(torch.int32)
 
 
+class LastMove:
+    """The history (prev_rows, partner_seed, partner_draw, first_game_id[, valid]) as a history of one entry: it presents what
+    `ConditionedDeterminizer.sample_history` reads from a `PartnerHistory`, for the partner's last move alone.
+
+        prev_rows [1, m, SW] int32   the states the partner moved from
+        valid     [1, m] uint8       0: no usable previous state; None: every root has one
+        draws     [partner_draw]     the Philox draw of that turn; depth = filled = 1
+        alive     None               every card I held then I hold now: the splice takes a null mask
+        moves     None               the move is the last one the sampled rows record: last_move_uid(cfg, rows), at call time
+
+    prev_rows [m, words] and valid [m] (or None) are checked and moved to `device`. Unpacks as the tuple it was made from."""
+
+    depth = filled = 1
+    alive = moves = None
+
+    def __init__(self, prev_rows, partner_seed, partner_draw, first_game_id, valid=None, *, m, words, device):
+        prev = torch.as_tensor(prev_rows)
+        if prev.dim() != 2 or tuple(prev.shape) != (m, words):
+            raise ValueError(f"history's previous rows have shape ({m}, {words}), got {tuple(prev.shape)}")
+        self.m, self.state_words = m, words
+        self.prev_rows = prev.to(device=device, dtype=torch.int32).contiguous().view(1, m, words)
+        self.valid = None
+        if valid is not None:
+            valid = torch.as_tensor(valid)
+            if tuple(valid.shape) != (m,):
+                raise ValueError(f"history's valid mask has shape ({m},), got {tuple(valid.shape)}")
+            self.valid = (valid.to(device) != 0).to(torch.uint8).contiguous().view(1, m)
+        self.partner_seed, self.partner_draw, self.first_game_id = int(partner_seed), int(partner_draw), int(first_game_id)
+        self.draws = [self.partner_draw]
+
+    def __iter__(self):
+        return iter((self.prev_rows[0], self.partner_seed, self.partner_draw, self.first_game_id,
+                     None if self.valid is None else self.valid[0]))
+
+    def __getitem__(self, i):
+        return tuple(self)[i]
+
+
 def _history(history, m, words, dev):
-    """(prev_rows, partner_seed, partner_draw, first_game_id[, valid]) checked -> the same with tensors on the device."""
+    """(prev_rows, partner_seed, partner_draw, first_game_id[, valid]) checked -> the `LastMove` of it, tensors on the device."""
     if not isinstance(history, (tuple, list)) or len(history) not in (4, 5):
         raise ValueError("history is (prev_rows, partner_seed, partner_draw, first_game_id[, valid])")
-    prev = torch.as_tensor(history[0])
-    if prev.dim() != 2 or tuple(prev.shape) != (m, words):
-        raise ValueError(f"history's previous rows have shape ({m}, {words}), got {tuple(prev.shape)}")
-    prev = prev.to(device=dev, dtype=torch.int32).contiguous()
-    valid = None
-    if len(history) == 5 and history[4] is not None:
-        valid = torch.as_tensor(history[4])
-        if tuple(valid.shape) != (m,):
-            raise ValueError(f"history's valid mask has shape ({m},), got {tuple(valid.shape)}")
-        valid = (valid.to(dev) != 0).to(torch.uint8).contiguous()
-    return prev, int(history[1]), int(history[2]), int(history[3]), valid
+    return LastMove(*history, m=m, words=words, device=dev)
 
 
 class PartnerHistory:
@@ -841,11 +654,36 @@ class PartnerHistory:
             self.push(prev, last_move_uid(self.cfg, cur), draw, valid, seat=seat)
 
 
+class BeliefSample(NamedTuple):
+    """What `ConditionedDeterminizer.sample` and `.sample_history` return, for a history of depth D:
+
+        rows       [m * replicas, SW] int32   replica r of root i = row i * replicas + r
+        weights    [m * replicas] int64       (the caller's int32 buffer with `out`); 0 marks a dead replica
+        n_surv     [D, m] int32               the candidates that reproduce the partner's last d + 1 moves
+        depth_used [m] int32                  the moves the replicas of the root reproduce (epsilon: the usable moves)
+        fallback   [m] uint8                  0: filtered, 1: no survivor at any depth, 2: no usable entry (the unconditioned belief)
+        ess        [m] float32                epsilon: the effective sample size of the weighted candidates; None without"""
+
+    rows: torch.Tensor
+    weights: torch.Tensor
+    n_surv: torch.Tensor
+    depth_used: torch.Tensor
+    fallback: torch.Tensor
+    ess: Optional[torch.Tensor]
+
+    def survivors(self):
+        """[m] int32: n_surv at the depth used, the candidates that pass the filter the replicas come from; 0 where
+        depth_used is 0."""
+        used = self.depth_used.long()
+        return torch.where(used > 0, self.n_surv.gather(0, (used - 1).clamp(min=0).view(1, -1)).view(-1), 0)
+
+
 class ConditionedDeterminizer:
-    """The V0 belief conditioned on the partner's last move: candidates from `Determinizer`, the previous
-    state with each candidate hand spliced in (hb_belief_splice), the partner's move in each of them (its `eval_moves` on an
-    m-game scratch env, one slab of candidates at a time), and the first `replicas` candidates under which that move is the one
-    the partner made (hb_belief_select). The scratch env and the buffers are kept per (m, K).
+    """The V0 belief conditioned on the partner's last moves: candidates from `Determinizer`, each
+    previous state with each candidate hand spliced in (hb_belief_splice_alive), the partner's move in each of them (its
+    `eval_moves` on an m-game scratch env, one slab of candidates at a time), and the first `replicas` candidates under which
+    those moves are the ones the partner made (hb_belief_select_depth). There is one path, `sample_history`; `sample` is that
+    path on the `LastMove`. The scratch env and the buffers are kept per (m, K).
 
     stateless (default True; an attribute that may be switched between calls): a partner that declares `obs_only_eval = True`
     (DQNAgent: its eval_moves reads only the observation and legal mask it is handed) gets them from ONE hb_encode_rows call over
@@ -856,7 +694,7 @@ class ConditionedDeterminizer:
     epsilon-greedy on `partner`'s policy. Every candidate keeps a likelihood (soft_table: 1 - eps + eps / n per reproduced move,
     eps / n per missed one, n = the legal moves of the hypothetical state, recorded per slab from the legal mask the partner is
     shown) and the replicas are drawn in proportion to importance weight times likelihood (hb_belief_select_soft): no depth
-    fallback, every replica weighs 1, and the result carries the candidates' effective sample size `ess` at the end."""
+    fallback, every replica weighs 1, and the result carries the candidates' effective sample size `ess`."""
 
     def __init__(self, game="Hanabi-Full", players=2, config=None, stateless=True):
         self.det = Determinizer(game, players, config)
@@ -935,66 +773,31 @@ class ConditionedDeterminizer:
                 torch.sum(env.legal, dim=1, dtype=torch.int32, out=nleg[k])
             _ask(partner, env, int(partner_seed), int(partner_draw), moves[k], self._scratch)
 
-    @torch.no_grad()
     def sample(self, rows, prev_rows, partner, seat, replicas, oversample, seed, draw, partner_seed, partner_draw, first_game_id,
                valid=None, first_row_id=0, out=None, epsilon=None):
         """rows [m, SW] the current states (seat `seat` to act), prev_rows [m, SW] the states the partner moved from, partner:
         the agent that moved (its eval_moves is called with partner_seed / partner_draw on games first_game_id + i: what it was
-        called with in the real game), valid [m] (0: no usable previous state; the root keeps the unconditioned belief). K =
-        replicas * oversample candidates per root are drawn with (seed, draw) and row ids first_row_id + i * K + k. A prev_rows
-        that is not the state the partner moved from (another deal, a hand of another size for `seat`) gives some legal
-        hypothetical state, not a specified one.
-        -> (rows_out [m * replicas, SW] int32, weights [m * replicas] int64, n_surv [m] int32, fallback [m] uint8). `out`: an
-        optional (rows_out, weights_u32) pair to write into (the weights then come back as the int32 buffer). epsilon: see the
-        class docstring; the tuple then ends with ess [m] float32, and the replicas are drawn with (seed, draw) and row ids
-        first_row_id + i."""
+        called with in the real game), valid [m] (0: no usable previous state; the root keeps the unconditioned belief). A
+        prev_rows that is not the state the partner moved from (another deal, a hand of another size for `seat`) gives some
+        legal hypothetical state, not a specified one. This is sample_history() on the `LastMove` of these arguments: the
+        same `BeliefSample`, n_surv [1, m]."""
         r = _rows(rows, self.state_words)
-        m, R, ov = r.shape[0], int(replicas), int(oversample)
-        if R < 1 or ov < 1:
-            raise ValueError(f"replicas and oversample must be >= 1, got {replicas} and {oversample}")
-        if not 0 <= int(seat) < self.players:
-            raise ValueError(f"seat {seat} out of range for {self.players} players")
-        if not hasattr(partner, "eval_moves"):
-            raise TypeError(f"{type(partner).__name__} has no eval_moves()")
-        dev, Kn = r.device, R * ov
-        prev, _, _, _, valid = _history((prev_rows, 0, 0, 0, valid), m, self.state_words, dev)
-        b = self._setup(m, Kn, dev)
-        env = b["env"]
-        table, nleg = (None, None) if epsilon is None else self._soft(b, epsilon, 1, Kn, m, dev)
-        with torch.cuda.device(dev):
-            usable = running(r) if valid is None else running(r) & (valid != 0)
-            # a root without a usable previous state is never filtered: its slab rows only have to be states the partner's
-            # policy can be run on, and the current row is one
-            prev = torch.where(usable.view(m, 1), prev, r).contiguous()
-            self.det.sample(r, seat=int(seat), replicas=Kn, seed=seed, draw=draw, first_row_id=first_row_id,
-                            out=(b["cand_rows"], b["cand_w"]))
-            belief_splice(self.cfg, prev, b["cand_rows"], int(seat), Kn, out=b["hyp_rows"])
-            env.first_game_id = int(first_game_id)   # (the scratch env never deals: its game ids key the partner's draws only)
-            self._slab_moves(b, partner, m, Kn, dev, partner_seed, partner_draw, b["hyp_moves"], None if nleg is None else nleg[0])
-            if epsilon is not None:
-                res = belief_select_soft(self.cfg, r, b["cand_rows"], b["cand_w"], b["hyp_moves"].view(1, Kn, m), nleg,
-                                         last_move_uid(self.cfg, r).view(1, m), usable.to(torch.uint8).view(1, m), table, R, seed, draw,
-                                         first_row_id=first_row_id,
-                                         out=None if out is None else tuple(out) + _bufs(dev, None, ((1, m), torch.int32), ((m,), torch.int32),
-                                                                                         ((m,), torch.uint8), ((m,), torch.float32)))
-                return (res[0], res[1] if out is not None else res[1].long() & 0xFFFFFFFF, res[2][0], res[4], res[5])
-            res = belief_select(self.cfg, r, b["cand_rows"], b["cand_w"], b["hyp_moves"], last_move_uid(self.cfg, r),
-                                usable.to(torch.uint8), R,
-                                out=None if out is None else tuple(out) + _bufs(dev, None, ((m,), torch.int32), ((m,), torch.uint8)))
-        if out is not None:
-            return res
-        return res[0], res[1].long() & 0xFFFFFFFF, res[2], res[3]
+        last = LastMove(prev_rows, partner_seed, partner_draw, first_game_id, valid, m=r.shape[0], words=self.state_words, device=r.device)
+        return self.sample_history(r, last, partner, seat, replicas, oversample, seed, draw, partner_seed, first_game_id,
+                                   first_row_id=first_row_id, out=out, epsilon=epsilon)
 
     @torch.no_grad()
     def sample_history(self, rows, history, partner, seat, replicas, oversample, seed, draw, partner_seed, first_game_id,
                        first_row_id=0, out=None, epsilon=None):
-        """sample() over the partner's last history.depth moves (a PartnerHistory of these m roots, observer `seat`): the
-        candidates are drawn ONCE, as in sample(); for each entry d they are carried back to its previous state with its alive
-        mask (hb_belief_splice_alive) and the partner's eval_moves runs on the K slabs with (partner_seed, history.draws[d]);
-        one hb_belief_select_depth keeps, per root, the first `replicas` candidates that reproduce the most leading moves.
-        Entries that were never pushed cost no slab pass. -> (rows_out [m * replicas, SW] int32, weights [m * replicas] int64,
-        n_surv [depth, m] int32, depth_used [m] int32, fallback [m] uint8); `out` and `epsilon` as in sample() (with an epsilon
-        depth_used is the number of usable moves, fallback 0 or 2, and the tuple ends with ess [m] float32)."""
+        """rows [m, SW] the current states (seat `seat` to act), conditioned on the partner's last history.depth moves (a
+        `PartnerHistory` of these m roots, observer `seat`, or a `LastMove`). K = replicas * oversample candidates per root are
+        drawn ONCE, with (seed, draw) and row ids first_row_id + i * K + k; for each entry d they are carried back to its
+        previous state with its alive mask (hb_belief_splice_alive) and the partner's eval_moves runs on the K slabs with
+        (partner_seed, history.draws[d]) on games first_game_id + i; one hb_belief_select_depth keeps, per root, the first
+        `replicas` candidates that reproduce the most leading moves. Entries that were never pushed cost no slab pass.
+        -> `BeliefSample`. `out`: an optional (rows_out, weights_u32) pair to write into (the weights then come back as that
+        int32 buffer). epsilon: see the class docstring (hb_belief_select_soft: depth_used is the number of usable moves,
+        fallback 0 or 2, and the replicas are drawn with (seed, draw) and row ids first_row_id + i)."""
         r = _rows(rows, self.state_words)
         m, R, ov = r.shape[0], int(replicas), int(oversample)
         if R < 1 or ov < 1:
@@ -1003,13 +806,13 @@ class ConditionedDeterminizer:
             raise ValueError(f"seat {seat} out of range for {self.players} players")
         if not hasattr(partner, "eval_moves"):
             raise TypeError(f"{type(partner).__name__} has no eval_moves()")
-        if not isinstance(history, PartnerHistory):
-            raise TypeError(f"history must be a PartnerHistory, got {type(history).__name__}")
+        if not isinstance(history, (PartnerHistory, LastMove)):
+            raise TypeError(f"history must be a PartnerHistory or a LastMove, got {type(history).__name__}")
         if history.m != m or history.state_words != self.state_words:
             raise ValueError(f"the history holds {history.m} roots of {history.state_words} words, the rows are {tuple(r.shape)}")
         dev, Kn, D = r.device, R * ov, history.depth
-        if history.alive.device != dev:
-            raise ValueError(f"the history lives on {history.alive.device}, the rows on {dev}")
+        if history.prev_rows.device != dev:
+            raise ValueError(f"the history lives on {history.prev_rows.device}, the rows on {dev}")
         b = self._setup(m, Kn, dev)
         env = b["env"]
         hyp = b.get("hyp_depth")
@@ -1017,28 +820,30 @@ class ConditionedDeterminizer:
             hyp = b["hyp_depth"] = torch.zeros((D, Kn, m), dtype=torch.int32, device=dev)
         table, nleg = (None, None) if epsilon is None else self._soft(b, epsilon, D, Kn, m, dev)
         with torch.cuda.device(dev):
-            # the chain of usable entries, root by root: an entry behind an invalid one is never read, so its slab rows only
-            # have to be states the partner's policy can be run on, and the current row is one (as in sample())
-            chain = ((history.valid != 0) & running(r).view(1, m)).long().cumprod(0).to(torch.uint8).contiguous()
+            # the chain of usable entries, root by root: an entry behind an invalid one is never read, and a root without a
+            # usable entry is never filtered, so their slab rows only have to be states the partner's policy can be run on,
+            # and the current row is one
+            usable = running(r).view(1, m) if history.valid is None else (history.valid != 0) & running(r).view(1, m)
+            chain = usable if D == 1 else usable.cumprod(0) != 0   # [D, m] bool (one entry is its own chain: no launch for it)
+            chain_u8 = chain.to(torch.uint8)
             self.det.sample(r, seat=int(seat), replicas=Kn, seed=seed, draw=draw, first_row_id=first_row_id,
                             out=(b["cand_rows"], b["cand_w"]))
-            env.first_game_id = int(first_game_id)
+            env.first_game_id = int(first_game_id)   # (the scratch env never deals: its game ids key the partner's draws only)
             for d in range(min(D, history.filled)):
-                prev = torch.where((chain[d] != 0).view(m, 1), history.prev_rows[d], r).contiguous()
-                belief_splice_alive(self.cfg, prev, history.alive[d].contiguous(), b["cand_rows"], int(seat), Kn, out=b["hyp_rows"])
+                prev = torch.where(chain[d].view(m, 1), history.prev_rows[d], r).contiguous()
+                alive = None if history.alive is None else history.alive[d].contiguous()
+                belief_splice_alive(self.cfg, prev, alive, b["cand_rows"], int(seat), Kn, out=b["hyp_rows"])
                 self._slab_moves(b, partner, m, Kn, dev, partner_seed, history.draws[d], hyp[d], None if nleg is None else nleg[d])
-            if epsilon is not None:
-                res = belief_select_soft(self.cfg, r, b["cand_rows"], b["cand_w"], hyp, nleg, history.moves.contiguous(), chain, table, R,
-                                         seed, draw, first_row_id=first_row_id,
-                                         out=None if out is None else tuple(out) + _bufs(dev, None, ((D, m), torch.int32), ((m,), torch.int32),
-                                                                                         ((m,), torch.uint8), ((m,), torch.float32)))
-                return (res[0], res[1] if out is not None else res[1].long() & 0xFFFFFFFF) + tuple(res[2:])
-            res = belief_select_depth(self.cfg, r, b["cand_rows"], b["cand_w"], hyp, history.moves.contiguous(), chain, R,
-                                      out=None if out is None else tuple(out) + _bufs(dev, None, ((D, m), torch.int32), ((m,), torch.int32),
-                                                                                      ((m,), torch.uint8)))
-        if out is not None:
-            return res
-        return res[0], res[1].long() & 0xFFFFFFFF, res[2], res[3], res[4]
+            actual = last_move_uid(self.cfg, r).view(1, m) if history.moves is None else history.moves.contiguous()
+            if out is not None:
+                out = tuple(out) + _bufs(dev, None, ((D, m), torch.int32), ((m,), torch.int32), ((m,), torch.uint8))
+            if epsilon is None:
+                res = belief_select_depth(self.cfg, r, b["cand_rows"], b["cand_w"], hyp, actual, chain_u8, R, out=out) + (None,)
+            else:
+                res = belief_select_soft(self.cfg, r, b["cand_rows"], b["cand_w"], hyp, nleg, actual, chain_u8, table, R, seed, draw,
+                                         first_row_id=first_row_id,
+                                         out=None if out is None else out + _bufs(dev, None, ((m,), torch.float32)))
+        return BeliefSample(res[0], res[1] if out is not None else res[1].long() & 0xFFFFFFFF, *res[2:])
 
 
 def exact_table(n_actions, device=None):
@@ -1088,8 +893,8 @@ class TrackedBelief:
     are the search's replicas: the draws are exchangeable.
 
     A root STARTS OVER when it has no particle set yet, when its previous turn is not usable, or when its resampling total is 0
-    (no carried particle explains what was seen): it takes K rows from `ConditionedDeterminizer.sample_history` (a PartnerHistory
-    given) or `.sample` (none), with the caller's epsilon, K candidates. That path runs only when some root needs it (one host
+    (no carried particle explains what was seen): it takes K rows from `ConditionedDeterminizer.sample_history` (on the PartnerHistory
+    given, or on the `LastMove`), with the caller's epsilon, K candidates. That path runs only when some root needs it (one host
     synchronisation per step decides). A restart is normal — a first move, a partner that explores — and only counted."""
 
     def __init__(self, game="Hanabi-Full", players=2, config=None, replicas=32, oversample=8, cdet=None):
@@ -1155,7 +960,8 @@ class TrackedBelief:
             raise ValueError(f"seat {seat} out of range for 2 players")
         if not hasattr(partner, "eval_moves"):
             raise TypeError(f"{type(partner).__name__} has no eval_moves()")
-        prev, _, _, _, valid = _history((prev_rows, 0, 0, 0, valid), m, SW, dev)
+        last = LastMove(prev_rows, partner_seed, partner_draw, first_game_id, valid, m=m, words=SW, device=dev)
+        prev, valid = last.prev_rows[0], None if last.valid is None else last.valid[0]
         if self.rows is None or self.rows.shape[0] != m * Kn or self.rows.device != dev:
             self.rows = torch.zeros((m * Kn, SW), dtype=torch.int32, device=dev)
             self.weights = torch.zeros(m * Kn, dtype=torch.int32, device=dev)
@@ -1193,25 +999,15 @@ class TrackedBelief:
             n_surv, used = n_surv[0], tracked.int()
             fallback = torch.where(tracked, 0, 2).to(torch.uint8)
             if bool(restarted.any().item()):
-                if history is not None:
-                    got = cd.sample_history(r, history, partner, seat, Kn, 1, seed, draw, partner_seed, first_game_id,
-                                            first_row_id=first_row_id, epsilon=epsilon)
-                    surv_d, used2, fb2 = got[2], got[3].int(), got[4]
-                    surv2 = torch.where(used2 > 0, surv_d.gather(0, (used2.long() - 1).clamp(min=0).view(1, m)).view(m), 0)
-                    ess2 = got[5] if epsilon is not None else None
-                else:
-                    got = cd.sample(r, prev_rows, partner, seat, Kn, 1, seed, draw, partner_seed, partner_draw, first_game_id,
-                                    valid=valid, first_row_id=first_row_id, epsilon=epsilon)
-                    surv2, fb2 = got[2], got[3]
-                    used2 = (fb2 == 0).int()
-                    ess2 = got[4] if epsilon is not None else None
+                new = cd.sample_history(r, history if history is not None else last, partner, seat, Kn, 1, seed, draw, partner_seed,
+                                        first_game_id, first_row_id=first_row_id, epsilon=epsilon)
                 pick = restarted.view(m, 1)
-                new_rows.view(m, Kn * SW).copy_(torch.where(pick, got[0].view(m, Kn * SW), new_rows.view(m, Kn * SW)))
-                new_w.view(m, Kn).copy_(torch.where(pick, got[1].view(m, Kn).int(), new_w.view(m, Kn)))
-                n_surv, used = torch.where(restarted, surv2, n_surv), torch.where(restarted, used2, used)
-                fallback = torch.where(restarted, fb2, fallback)
-                if ess2 is not None:
-                    ess = torch.where(restarted, ess2, ess)
+                new_rows.view(m, Kn * SW).copy_(torch.where(pick, new.rows.view(m, Kn * SW), new_rows.view(m, Kn * SW)))
+                new_w.view(m, Kn).copy_(torch.where(pick, new.weights.view(m, Kn).int(), new_w.view(m, Kn)))
+                n_surv, used = torch.where(restarted, new.survivors(), n_surv), torch.where(restarted, new.depth_used, used)
+                fallback = torch.where(restarted, new.fallback, fallback)
+                if new.ess is not None:
+                    ess = torch.where(restarted, new.ess, ess)
             self._next = (self.rows, self.weights)
             self.rows, self.weights = new_rows, new_w
             self.have = live.clone()
@@ -1227,18 +1023,20 @@ class SearchResult:
     the weighted mean over the replicas of score[slot] - score[baseline], `se` [m, C] f64 its standard error (inf with fewer
     than two live replicas; both 0 in the baseline's slot, NaN where there is no candidate, no baseline or no live replica) and
     `n_pair` [m] int32 the live replicas (hb_search_compare). None when not computed. With `history` (the belief conditioned on
-    the partner's last move): `n_surv` [m] int32 and `fallback` [m] uint8 of hb_belief_select; None without. With a
+    the partner's last move): `n_surv` [m] int32 and `fallback` [m] uint8 of hb_belief_select_depth; None without. With a
     `PartnerHistory` (its last `depth` moves): `n_surv` [depth, m], `fallback` and `depth_used` [m] int32 of
     hb_belief_select_depth; `depth_used` is None when not computed. With the search's `epsilon` (the soft filter,
     hb_belief_select_soft): `ess` [m] float32, the effective sample size of each root's weighted candidates; None without.
+    `sample` is the `BeliefSample` these four are read from (None without a history, and with a `TrackedRows`).
     With the search's `score_belief`: `belief`, the `BeliefScore` of the replicas searched against the roots' real hands."""
 
     def __init__(self, value, wsum, n_live, best, rollouts, turns, dead=0, replicas=0, diff=None, se=None, n_pair=None, cand=None,
-                 best_uid=None, n_surv=None, fallback=None, depth_used=None, ess=None, belief=None):
+                 best_uid=None, n_surv=None, fallback=None, depth_used=None, ess=None, belief=None, sample=None):
         self.value, self.wsum, self.n_live, self.best = value, wsum, n_live, best
         self.rollouts, self.turns, self.dead, self.replicas = int(rollouts), int(turns), int(dead), int(replicas)
         self.diff, self.se, self.n_pair, self.cand, self.best_uid = diff, se, n_pair, cand, best_uid
         self.n_surv, self.fallback, self.depth_used, self.ess, self.belief = n_surv, fallback, depth_used, ess, belief
+        self.sample = sample
 
     def __repr__(self):
         return f"SearchResult(roots={self.value.shape[0]}, rollouts={self.rollouts}, turns={self.turns})"
@@ -1383,7 +1181,7 @@ class RolloutSearch:
         if not cps:
             return self._nothing(m, Cn, dev, compared=base_slot is not None)
         cp, env = int(cps[0]), b["env"]
-        n_surv = fallback = depth_used = ess = None
+        n_surv = fallback = depth_used = ess = sample = None
         with torch.cuda.device(dev):
             if history is None:
                 self.det.sample(r, seat=cp, replicas=R, seed=self.seed, draw=draw, first_row_id=first_row_id,
@@ -1391,23 +1189,15 @@ class RolloutSearch:
             elif isinstance(history, TrackedRows):
                 history.take(m, R, (b["det_rows"], b["weights"]))
                 n_surv, fallback, depth_used, ess = history.n_surv, history.fallback, history.depth_used, history.ess
-            elif isinstance(history, PartnerHistory):
+            else:   # a PartnerHistory or a LastMove
                 if self.cdet is None:
                     self.cdet = ConditionedDeterminizer(config=self.cfg)
-                got = self.cdet.sample_history(
+                sample = self.cdet.sample_history(
                     r, history, blueprint[(cp - 1) % self.players], cp, R, self.oversample, self.seed, draw, history.partner_seed,
                     history.first_game_id, first_row_id=first_row_id, out=(b["det_rows"], b["weights"]), epsilon=self.epsilon)
-                n_surv, depth_used, fallback = got[2:5]
-                ess = got[5] if self.epsilon is not None else None
-            else:
-                prev, p_seed, p_draw, gid, valid = history
-                if self.cdet is None:
-                    self.cdet = ConditionedDeterminizer(config=self.cfg)
-                got = self.cdet.sample(r, prev, blueprint[(cp - 1) % self.players], cp, R, self.oversample, self.seed, draw, p_seed,
-                                       p_draw, gid, valid=valid, first_row_id=first_row_id, out=(b["det_rows"], b["weights"]),
-                                       epsilon=self.epsilon)
-                n_surv, fallback = got[2:4]
-                ess = got[4] if self.epsilon is not None else None
+                # (the result of a last-move history keeps its public shapes: n_surv [m], no depth_used)
+                n_surv, depth_used = (sample.n_surv[0], None) if isinstance(history, LastMove) else (sample.n_surv, sample.depth_used)
+                fallback, ess = sample.fallback, sample.ess
             belief = belief_score(self.cfg, r, b["det_rows"], b["weights"], cp, R) if self.score_belief else None
             # [m, C, R]: block c of root i holds the same R replicas. A slot without a candidate (an illegal action, in run()) is
             # never counted (done up front); its games move in step with the others on the root's filler move, so that no illegal
@@ -1431,7 +1221,7 @@ class RolloutSearch:
             value, wsum, n_live, best = search_reduce(scores, weights, slots)
             rollouts, dead, roots = counts.tolist()
             res = SearchResult(value, wsum, n_live, best, rollouts, turns, dead=dead, replicas=roots * R, n_surv=n_surv,
-                               fallback=fallback, depth_used=depth_used, ess=ess, belief=belief)
+                               fallback=fallback, depth_used=depth_used, ess=ess, belief=belief, sample=sample)
             if base_slot is not None:
                 res.diff, res.se, res.n_pair = search_compare(scores, weights, cand, base_slot)
         return res
@@ -1447,7 +1237,7 @@ class RolloutSearch:
         r = roots[0]
         dev = r.device
         m, A = r.shape[0], self.num_actions
-        if history is not None and not isinstance(history, (PartnerHistory, TrackedRows)):
+        if history is not None and not isinstance(history, (PartnerHistory, TrackedRows, LastMove)):
             history = _history(history, m, self.det.state_words, dev)
         lg = torch.as_tensor(legal).to(device=dev, dtype=torch.int8).contiguous()
         if lg.shape != (m, A):
@@ -1477,7 +1267,7 @@ class RolloutSearch:
         roots = self._roots(rows, blueprint, None)
         dev = roots[0].device
         m = roots[0].shape[0]
-        if history is not None and not isinstance(history, (PartnerHistory, TrackedRows)):
+        if history is not None and not isinstance(history, (PartnerHistory, TrackedRows, LastMove)):
             history = _history(history, m, self.det.state_words, dev)
         R = self.replicas if replicas is None else int(replicas)
         if R < 1:
@@ -1829,16 +1619,14 @@ class SearchPlayer:
                     self._track_ess = t_ess if self._track_ess is None else self._track_ess + t_ess
                     t_counts = torch.stack([history.tracked.sum(), history.restarted.sum(), history.carried_live.sum()]).long()
                     self._track_stats = t_counts if self._track_stats is None else self._track_stats + t_counts
-                elif self.depth == 1:
-                    n_surv, used = res.n_surv, (res.fallback == 0).long()
                 else:   # the candidates that pass the filter of the depth used, root by root
-                    used = res.depth_used.long()
-                    n_surv = torch.where(used > 0, res.n_surv.gather(0, (used - 1).clamp(min=0).view(1, -1)).view(-1), 0)
-                    D = torch.arange(1, self.depth + 1, device=rows.device).view(-1, 1)
-                    have = ((history.valid != 0) & live.view(1, -1)).long().cumprod(0).sum(0).view(1, -1)   # L_i
-                    by_depth = torch.stack([(have >= D).sum(1), (res.n_surv * (have >= D)).sum(1), ((used.view(1, -1) == D) & filtered).sum(1),
-                                            ((have == D) & (used.view(1, -1) < D)).sum(1)])
-                    self._by_depth = by_depth if self._by_depth is None else self._by_depth + by_depth
+                    n_surv, used = res.sample.survivors(), res.sample.depth_used.long()
+                    if self.depth > 1:
+                        D = torch.arange(1, self.depth + 1, device=rows.device).view(-1, 1)
+                        have = ((history.valid != 0) & live.view(1, -1)).long().cumprod(0).sum(0).view(1, -1)   # L_i
+                        by_depth = torch.stack([(have >= D).sum(1), (res.n_surv * (have >= D)).sum(1),
+                                                ((used.view(1, -1) == D) & filtered).sum(1), ((have == D) & (used.view(1, -1) < D)).sum(1)])
+                        self._by_depth = by_depth if self._by_depth is None else self._by_depth + by_depth
                 counts.update(conditioned=filtered.sum(), unconditioned=(live & (res.fallback == 2)).sum(),
                               survivors=(n_surv * filtered).sum(), candidates=filtered.sum() * (self.replicas * self.oversample),
                               fallbacks=(filtered & (res.fallback == 1)).sum(), depth_used=(used * filtered).sum())

@@ -102,7 +102,7 @@ def main():
         res = []
         ms = 1e3 * timed(lambda: res.append(cd.sample(rows, prev, piers[1], 0, 32, ov, seed=9, draw=11, partner_seed=7, partner_draw=10,
                                                       first_game_id=0)))
-        n_surv, fallback = res[-1][2], res[-1][3]
+        n_surv, fallback = res[-1].n_surv[0], res[-1].fallback
         out["cost"][f"conditioned_sample_ov{ov}"] = dict(ms=ms, slabs=32 * ov, survivor_share=float(n_surv.double().mean()) / (32 * ov),
                                                          roots_short_of_32=float((n_surv < 32).double().mean()),
                                                          fallback_share=float((fallback == 1).double().mean()))

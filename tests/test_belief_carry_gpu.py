@@ -247,8 +247,8 @@ def test_tracked_step_equals_the_pipeline_by_hand(epsilon):
                 assert bool(tracked.any()) and bool(restarted[5]) == bool(live[5])
                 fresh = ConditionedDeterminizer("Hanabi-Full", 2).sample(rows, prev_rows, team[1], 0, Kn, 1, seed, draw, pseed, draw - 1,
                                                                          env.first_game_id, valid=valid, epsilon=epsilon)
-                want_rows = torch.where(restarted.view(m, 1, 1), fresh[0].view(m, Kn, -1), s_rows.view(m, Kn, -1))
-                want_w = torch.where(restarted.view(m, 1), fresh[1].view(m, Kn).int(), s_w.view(m, Kn))
+                want_rows = torch.where(restarted.view(m, 1, 1), fresh.rows.view(m, Kn, -1), s_rows.view(m, Kn, -1))
+                want_w = torch.where(restarted.view(m, 1), fresh.weights.view(m, Kn).int(), s_w.view(m, Kn))
                 assert torch.equal(got.rows.view(m, Kn, -1), want_rows) and torch.equal(got.weights.view(m, Kn), want_w)
                 assert torch.equal(got.carried_live, torch.where(tracked, (c_w.view(m, Kn) != 0).sum(1).int(), 0))
                 assert torch.equal(got.n_surv[tracked], n_surv[0][tracked]) and torch.equal(got.ess[tracked], ess[tracked])

@@ -239,20 +239,20 @@ def test_sample_history_soft_against_the_steps_by_hand():
     for stateless in (True, False):
         cd = ConditionedDeterminizer("Hanabi-Small", 2, stateless=stateless)
         got = cd.sample_history(rows, hist, team[partner], seat, R, ov, epsilon=eps, **kw)
-        assert len(got) == 6
-        assert np.array_equal(_u32(got[0]), want[0]) and np.array_equal(got[1].cpu().numpy(), want[1].astype(np.int64))
-        assert np.array_equal(got[2].cpu().numpy(), want[2]) and np.array_equal(got[3].cpu().numpy(), want[3])
-        assert np.array_equal(got[4].cpu().numpy(), want[4]) and np.allclose(got[5].cpu().numpy(), want[5], rtol=1e-6, atol=0)
+        assert got.ess is not None
+        assert np.array_equal(_u32(got.rows), want[0]) and np.array_equal(got.weights.cpu().numpy(), want[1].astype(np.int64))
+        assert np.array_equal(got.n_surv.cpu().numpy(), want[2]) and np.array_equal(got.depth_used.cpu().numpy(), want[3])
+        assert np.array_equal(got.fallback.cpu().numpy(), want[4]) and np.allclose(got.ess.cpu().numpy(), want[5], rtol=1e-6, atol=0)
         outs[stateless] = [t.clone() for t in got]
         # the out= form: the weights come back as the int32 buffer
-        buf = (torch.empty_like(got[0]), torch.empty(m * R, dtype=torch.int32, device="cuda"))
+        buf = (torch.empty_like(got.rows), torch.empty(m * R, dtype=torch.int32, device="cuda"))
         again = cd.sample_history(rows, hist, team[partner], seat, R, ov, epsilon=eps, out=buf, **kw)
-        assert again[0] is buf[0] and again[1] is buf[1] and torch.equal(buf[0], got[0]) and torch.equal(buf[1].long(), got[1])
+        assert again.rows is buf[0] and again.weights is buf[1] and torch.equal(buf[0], got.rows) and torch.equal(buf[1].long(), got.weights)
         # epsilon=None: the exact-match filter, as it was (the same determinizer object, after a soft call)
         hard = cd.sample_history(rows, hist, team[partner], seat, R, ov, **kw)
         ref = select_depth_ref(_u32(rows), _u32(cand), cw.cpu().numpy().astype(np.uint32), hyp, actual, None, K, R)
-        assert len(hard) == 5 and np.array_equal(_u32(hard[0]), ref[0]) and np.array_equal(hard[1].cpu().numpy(), ref[1].astype(np.int64))
-        assert all(np.array_equal(h.cpu().numpy(), r) for h, r in zip(hard[2:], ref[2:]))
+        assert hard.ess is None and np.array_equal(_u32(hard.rows), ref[0]) and np.array_equal(hard.weights.cpu().numpy(), ref[1].astype(np.int64))
+        assert all(np.array_equal(h.cpu().numpy(), r) for h, r in zip((hard.n_surv, hard.depth_used, hard.fallback), ref[2:]))
     for a, b in zip(outs[True], outs[False]):
         assert a.dtype == b.dtype and torch.equal(a, b)
     # sample(): the last move alone, the same figures as depth 1
@@ -261,8 +261,8 @@ def test_sample_history_soft_against_the_steps_by_hand():
                     first_game_id=0, first_row_id=1000, epsilon=eps)
     want1 = belief_select_soft_ref(_u32(rows), _u32(cand), cw.cpu().numpy().astype(np.uint32), hyp[:1], nl[:1], actual[:1], None, table, R, 5,
                                    turns + 1, first_row_id=1000)
-    assert len(one) == 5 and np.array_equal(_u32(one[0]), want1[0]) and np.array_equal(one[2].cpu().numpy(), want1[2][0])
-    assert np.array_equal(one[3].cpu().numpy(), want1[4]) and np.allclose(one[4].cpu().numpy(), want1[5], rtol=1e-6, atol=0)
+    assert one.ess is not None and np.array_equal(_u32(one.rows), want1[0]) and np.array_equal(one.n_surv[0].cpu().numpy(), want1[2][0])
+    assert np.array_equal(one.fallback.cpu().numpy(), want1[4]) and np.allclose(one.ess.cpu().numpy(), want1[5], rtol=1e-6, atol=0)
 
 
 # ---- OffBeliefSession ----------------------------------------------------------------------------------------------------------------------

@@ -270,7 +270,8 @@ def _both_settings(team, m, expect_stateless, turns=8):
             assert untouched == expect_stateless, "the scratch env and the stateless path"
         else:
             assert not untouched
-        out[stateless] = [t.clone() for t in one + more]
+        out[stateless] = [t.clone() for t in (one.rows, one.weights, one.n_surv[0], one.fallback,
+                                              more.rows, more.weights, more.n_surv, more.depth_used, more.fallback)]
     assert len(out[True]) == 4 + 5
     for a, b in zip(out[True], out[False]):
         assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b)

@@ -235,7 +235,7 @@ def test_histories_through_redeals_one_step_by_hand_and_what_conditioning_means(
         if want is None:
             continue
         # ---- one step by hand
-        w_rows, w_w, w_surv, w_used, w_fb = want
+        w_rows, w_w, w_surv, w_used, w_fb = want.rows, want.weights, want.n_surv, want.depth_used, want.fallback
         assert torch.equal(sess._det_rows, w_rows) and torch.equal(sess._det_w.long() & 0xFFFFFFFF, w_w)
         n_surv, used, fb = sess.last_belief
         assert torch.equal(n_surv, w_surv) and torch.equal(used, w_used) and torch.equal(fb, w_fb)

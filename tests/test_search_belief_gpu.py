@@ -157,8 +157,9 @@ def test_conditioned_determinizer_against_a_rerun_by_hand():
     assert bool((((rows[:, 0] >> 19) & 3) == 0).all())
     assert torch.equal(last_move_uid(env.cfg, rows), played)
     cd = ConditionedDeterminizer("Hanabi-Full", 2)
-    out, w, n_surv, fallback = cd.sample(rows, prev, team[partner], seat, R, ov, seed=5, draw=turns + 1, partner_seed=seed,
-                                         partner_draw=turns, first_game_id=0, first_row_id=100)
+    smp = cd.sample(rows, prev, team[partner], seat, R, ov, seed=5, draw=turns + 1, partner_seed=seed, partner_draw=turns,
+                    first_game_id=0, first_row_id=100)
+    out, w, n_surv, fallback = smp.rows, smp.weights, smp.n_surv[0], smp.fallback
     # by hand: the candidates, one scratch import per candidate, the partner's eval_moves with the real game's keys
     cand, cw = Determinizer("Hanabi-Full", 2).sample(rows, seat=seat, replicas=K, seed=5, draw=turns + 1, first_row_id=100)
     scratch = hanabi_hip.HanabiEnv("Hanabi-Full", 2, n_games=m, seed=99, first_game_id=0, auto_reset=False, packed=True)
@@ -203,8 +204,9 @@ def test_conditioned_determinizer_against_a_rerun_by_hand():
     # valid = 0 and the out= form
     buf = (torch.empty_like(out), torch.empty(m * R, dtype=torch.int32, device="cuda"))
     valid = torch.tensor([1, 0] * (m // 2), dtype=torch.uint8, device="cuda")
-    o2, w2, ns2, fb2 = cd.sample(rows, prev, team[partner], seat, R, ov, seed=5, draw=turns + 1, partner_seed=seed, partner_draw=turns,
-                                 first_game_id=0, valid=valid, first_row_id=100, out=buf)
+    smp2 = cd.sample(rows, prev, team[partner], seat, R, ov, seed=5, draw=turns + 1, partner_seed=seed, partner_draw=turns,
+                     first_game_id=0, valid=valid, first_row_id=100, out=buf)
+    o2, w2, ns2, fb2 = smp2.rows, smp2.weights, smp2.n_surv[0], smp2.fallback
     assert o2 is buf[0] and w2 is buf[1]
     assert bool((fb2[1::2] == 2).all()) and torch.equal(fb2[0::2], fallback[0::2]) and torch.equal(ns2[0::2], n_surv[0::2])
     assert torch.equal(o2.view(m, R, -1)[1::2], cand.view(m, K, -1)[1::2, :R]) and torch.equal(o2.view(m, R, -1)[0::2], out.view(m, R, -1)[0::2])

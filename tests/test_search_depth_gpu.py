@@ -186,8 +186,9 @@ def test_sample_history_against_a_rerun_by_hand():
     occupied = (((stored[-1][:, 10 + seat].view(m, 1) >> (5 * torch.arange(5, device="cuda"))) & 31) != 31).int()
     assert bool((hist.alive[-1].int() != (occupied << torch.arange(5, device="cuda")).sum(1)).any())
     cd = ConditionedDeterminizer("Hanabi-Full", 2)
-    out, w, n_surv, used, fallback = cd.sample_history(rows, hist, team[partner], seat, R, ov, seed=5, draw=turns + 1, partner_seed=seed,
-                                                       first_game_id=0, first_row_id=100)
+    smp = cd.sample_history(rows, hist, team[partner], seat, R, ov, seed=5, draw=turns + 1, partner_seed=seed, first_game_id=0,
+                            first_row_id=100)
+    out, w, n_surv, used, fallback = smp.rows, smp.weights, smp.n_surv, smp.depth_used, smp.fallback
     # by hand: the candidates, the restated splice, one scratch import per (entry, candidate), the real game's keys
     cand, cw = Determinizer("Hanabi-Full", 2).sample(rows, seat=seat, replicas=K, seed=5, draw=turns + 1, first_row_id=100)
     scratch = hanabi_hip.HanabiEnv("Hanabi-Full", 2, n_games=m, seed=99, first_game_id=0, auto_reset=False, packed=True)
@@ -223,8 +224,9 @@ def test_sample_history_against_a_rerun_by_hand():
     # an invalid middle entry: its root is filtered on the newest move alone; the out= form
     hist.valid[1, 1::2] = 0
     buf = (torch.empty_like(out), torch.empty(m * R, dtype=torch.int32, device="cuda"))
-    o2, w2, ns2, du2, fb2 = cd.sample_history(rows, hist, team[partner], seat, R, ov, seed=5, draw=turns + 1, partner_seed=seed,
-                                              first_game_id=0, first_row_id=100, out=buf)
+    smp2 = cd.sample_history(rows, hist, team[partner], seat, R, ov, seed=5, draw=turns + 1, partner_seed=seed, first_game_id=0,
+                             first_row_id=100, out=buf)
+    o2, w2, ns2, du2, fb2 = smp2.rows, smp2.weights, smp2.n_surv, smp2.depth_used, smp2.fallback
     assert o2 is buf[0] and w2 is buf[1]
     assert torch.equal(du2[1::2], (n_surv[0, 1::2] > 0).int()) and bool((ns2[1:, 1::2] == 0).all()) and torch.equal(ns2[:, 0::2], n_surv[:, 0::2])
     assert torch.equal(o2.view(m, R, -1)[0::2], out_v[0::2]) and torch.equal(du2[0::2], used[0::2]) and torch.equal(ns2[0], n_surv[0])
