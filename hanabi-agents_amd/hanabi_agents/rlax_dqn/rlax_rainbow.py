@@ -511,6 +511,34 @@ class DQNAgent:
         bf16 agents with bit-packed observations always act on the one-kernel actor here, at any row count; exploit() below
         HB_ACTOR_FUSED_MIN_ROWS rows takes the two-kernel form. Same weights and greedy rule, but a different accumulation order:
         where two legal moves' q values are within rounding of each other the two forms may pick different moves."""
+        return self._eval(observations, seed, draw, actions_out, scratch, False)[0]
+
+    @torch.no_grad()
+    def eval_q(self, observations, q_out=None, scratch=None):
+        """The q values eval_moves selects from: q [N, A] fp32 on the agent's device, for the same (obs, legal) forms, from the same
+        weights on the same branch (one-kernel actor, library GEMMs, the vanilla head's hidden-layer kernel, torch) — the same
+        launch, whose q buffer is returned, so bit for bit the numbers behind eval_moves' choice: the arg-max of it over the legal
+        moves is eval_moves' move (two legal moves of exactly equal q, which eval_moves draws between, aside). Entries of illegal
+        moves hold anything (the torch path: -inf); the consumer masks them. eval_moves' contract holds: the draw counter stays,
+        no noise is resampled, the actor's own buffers are untouched, and `scratch` (the dict the caller keeps for this agent,
+        shared with eval_moves) supplies the buffers the kernels write: the result is valid until the next call with that scratch
+        (on the actor kernels it IS scratch's "q"), unless `q_out` (fp32 [N, A], contiguous, on the device) is given and receives
+        a copy."""
+        obs = observations[1][0]
+        n = obs.shape[0]
+        scratch = {} if scratch is None else scratch
+        moves = scratch.get("moves")
+        if moves is None or moves.shape != (n,) or moves.dtype != torch.int32 or moves.device.type != self.device.type:
+            moves = scratch["moves"] = torch.empty(n, dtype=torch.int32, device=self.device)
+        q = self._eval(observations, 0, 0, moves, scratch, True)[1]
+        if q_out is None:
+            return q
+        assert q_out.dtype == torch.float32 and q_out.is_contiguous() and q_out.shape == (n, self.n_actions)
+        return q_out.copy_(q)
+
+    def _eval(self, observations, seed, draw, actions_out, scratch, want_q):
+        """eval_moves and eval_q: (actions_out, the q [N, A] fp32 the moves were selected from — None unless want_q, where a
+        branch would have to write it out for that alone)."""
         obs, legal = observations[1]
         obs = obs if isinstance(obs, torch.Tensor) else torch.as_tensor(np.asarray(obs))
         legal = legal if isinstance(legal, torch.Tensor) else torch.as_tensor(np.asarray(legal))
@@ -538,18 +566,21 @@ class DQNAgent:
                 act = fl.actor if (fl is not None and self.use_mfma_actor) else None
                 if act is not None and (act.accepts(obs) or (act.fused and obs.dtype == torch.int32)):
                     (qs, qd), (hs, hd) = act.scratch_shapes(n)
+                    q = buf("q", qs, qd)
                     return act.act(obs, legal, support, 0.0, seed, draw, self.first_game_id, s=fl.acting_set(), actions_out=actions_out,
-                                   bufs=(buf("q", qs, qd), buf("h", hs, hd)), one_kernel=True)
+                                   bufs=(q, buf("h", hs, hd)), one_kernel=True), q
                 # library GEMMs + hb_policy_act, as _act_fused takes them
                 x, scratch["x"] = self._library_logits(obs, eff, scratch.get("x"))
-                return ops.policy_act(x, legal, support, 0.0, seed, draw, self.first_game_id, actions_out=actions_out)
+                # (hb_policy_act writes the unmasked q it selects from only where it is asked to)
+                q = buf("q", (n, self.n_actions), torch.float32) if want_q else None
+                return ops.policy_act(x, legal, support, 0.0, seed, draw, self.first_game_id, actions_out=actions_out, q_out=q), q
             # vanilla DQN (BASELINE config 2): the hidden-layer MFMA kernel into the caller's h, the output GEMM, hb_policy_select
             pa = self._plain_actor_obj()
             self._refresh_plain_weights(pa)
             q = self._plain_q(obs, pa, buf("h", (n, self.params.layers[0]), torch.bfloat16))
             K.check(K.lib().hb_policy_select(q.data_ptr(), legal.data_ptr(), n, self.n_actions, 0.0, seed, draw, self.first_game_id,
                                              actions_out.data_ptr(), K.current_stream()))
-            return actions_out
+            return actions_out, q
         # torch path (CPU, deeper nets, scalar head without the bf16 kernels)
         gen = scratch.get("gen")
         if gen is None or gen.device != torch.device(self.device):
@@ -557,9 +588,9 @@ class DQNAgent:
         gen.manual_seed((seed * 0x9E3779B1 + draw) & 0x7FFFFFFFFFFFFFFF)
         obs, legal = obs.to(self.device), legal.to(self.device)
         u = torch.rand(n, device=self.device, generator=gen)
-        actions = DQNPolicy.eval_policy(self.online, self.atoms, self._net_input(obs), legal, u, self.distributional)
-        actions_out.copy_(actions.to(torch.int32))
-        return actions_out
+        q = DQNPolicy.q_values(self.online, self.atoms, self._net_input(obs), legal, self.distributional)
+        actions_out.copy_(DQNPolicy.sample(q, legal, 0.0, torch.ones_like(u), u).to(torch.int32))   # (eval_policy, its q kept)
+        return actions_out, q.float()
 
     @torch.no_grad()
     def eval_operands(self):

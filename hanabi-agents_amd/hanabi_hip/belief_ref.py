@@ -216,3 +216,64 @@ def belief_score_ref(cfg, true_rows, det_rows, weights, seat, replicas):
             if true[s] < NC:
                 out["hit"][i, s] = out["counts"][i, s, true[s]]
     return out
+
+
+LEAF_SCALE = 4   # a depth-limited search keeps its leaf values in quarter points, in the int8 buffer the reduce kernels read
+
+
+def _mix32_np(x):
+    """The 32-bit finalizer of leaf_dither_ref on int64 arrays (or Python ints) below 2^32: xor-shift 16, times 0x7FEB352D, xor-shift
+    15, times 0x846CA68B, xor-shift 16, every product taken mod 2^32 from 16-bit halves of the constant so that no intermediate
+    reaches 2^49 (nothing ever wraps: plain signed 64-bit arithmetic gives the same bits everywhere)."""
+    def mul(x, c):
+        return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & _M32
+
+    x = x ^ (x >> 16)
+    x = mul(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = mul(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+def leaf_dither_ref(seed, draw, first_row_id, m, replicas):
+    """The dither of a depth-limited search's stochastic rounding: u [m, replicas] float64 in [0, 1), a multiple of 2^-24 and a pure
+    function of (seed, draw, row id = first_row_id + i * replicas + r) — the row id of the replica, so every slot of a replica
+    rounds with the same u. h = 0x9E3779B9; for each 32-bit word v of (seed lo, seed hi, draw lo, draw hi, row id lo, row id hi)
+    in that order h = mix32(h ^ v); u = (h >> 8) * 2^-24. ("Depth-limited rollouts".)"""
+    import numpy as np
+
+    m, R = int(m), int(replicas)
+    seed, draw = int(seed) & _M64, int(draw) & _M64
+    h = 0x9E3779B9
+    for v in (seed & _M32, seed >> 32, draw & _M32, draw >> 32):
+        h = _mix32_np(h ^ v)
+    rid = int(first_row_id) + np.arange(m * R, dtype=np.int64).reshape(m, R)
+    h = _mix32_np(np.int64(h) ^ (rid & _M32))
+    h = _mix32_np(h ^ ((rid >> 32) & _M32))
+    return (h >> 8).astype(np.float64) * 2.0 ** -24
+
+
+def search_leaf_ref(done, final_score, score, q, legal, u, max_score):
+    """The leaf step of a depth-limited search in numpy (the specification of `hanabi_hip.search.search_leaf`): done [m, C, R]
+    uint8 (hb_eval_tally's status byte), final_score and score [m, C, R] int8 (the tally's final score; the env's current score),
+    q [m, C, R, A] float (None: leaf="score", v = 0), legal [m, C, R, A] (!= 0: legal), u [m, R] float64 (leaf_dither_ref) ->
+    leaf4 [m, C, R] int8, the value of every rollout game in quarter points:
+
+      bit 7 of done set (finished before the horizon, or never played):  4 * final_score
+      else, with v = the largest FINITE q over the legal moves (0 when there is none; NaN and +-inf entries are passed over)
+      and x = 4 * (score + v) in float64:                                clamp(floor(x + u[i, r]), 0, 4 * max_score)
+
+    Stochastic rounding: E_u[leaf4] = x wherever the clamp is inactive."""
+    import numpy as np
+
+    done, fs, sc = np.asarray(done), np.asarray(final_score).astype(np.int64), np.asarray(score).astype(np.float64)
+    m, Cn, R = done.shape
+    u = np.asarray(u, np.float64).reshape(m, 1, R)
+    v = np.zeros((m, Cn, R), np.float64)
+    if q is not None:
+        qq = np.asarray(q).astype(np.float64)
+        ok = (np.asarray(legal) != 0) & np.isfinite(qq)
+        v = np.where(ok.any(-1), np.where(ok, qq, -np.inf).max(-1), 0.0)
+    x = LEAF_SCALE * (sc + v)
+    run = np.clip(np.floor(x + u), 0, LEAF_SCALE * int(max_score))
+    return np.where((done & 0x80) != 0, LEAF_SCALE * fs, run.astype(np.int64)).astype(np.int8)

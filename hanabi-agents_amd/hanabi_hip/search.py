@@ -43,7 +43,12 @@
   belief above.
 * `SearchPlayer` is an agent for `Evaluator.run`: the blueprint's move unless the search finds one that is better by more than
   `threshold` and, with `z` / `confirm_replicas`, by more than z standard errors of the paired difference.
-* The kernels' numpy restatements (`belief_select_soft_ref`, `belief_carry_ref`, `belief_score_ref`) live in hanabi_hip.belief_ref.
+* `horizon=H` (`RolloutSearch`, `SearchPlayer`, `SelfPlaySession.search`; default None: rollouts to the end, unchanged) cuts every
+  rollout after H turns and values a game still running at its score so far plus the largest legal q of `leaf`'s `eval_q`
+  (default: the blueprint's own agent of the seat then to act; "score": nothing), in quarter points with a shared dither
+  (`search_leaf`, `leaf_dither`), in the int8 buffer the two reduce kernels already read.
+* The kernels' numpy restatements (`belief_select_soft_ref`, `belief_carry_ref`, `belief_score_ref`) live in hanabi_hip.belief_ref,
+  with the leaf step's specification (`search_leaf_ref`, `leaf_dither_ref`).
 
 Colour-shuffled envs are refused: the rollout env's game ids would draw other permutations than the source's.
 """
@@ -167,6 +172,50 @@ def search_compare(scores, weights, cand, base_slot):
         K.check(K.lib().hb_search_compare(K.dptr(scores), K.dptr(weights), K.dptr(cand), K.dptr(base_slot), m, Cn, R, K.dptr(diff),
                                           K.dptr(se), K.dptr(n_pair), K.current_stream()))
     return diff, se, n_pair
+
+
+LEAF_SCALE = 4   # a depth-limited search keeps its leaf values in quarter points, in the int8 buffer the reduce kernels read
+
+
+def _mix32(x):
+    """belief_ref._mix32_np on int64 tensors below 2^32 (no intermediate reaches 2^49: nothing wraps)."""
+    def mul(x, c):
+        return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & 0xFFFFFFFF
+
+    x = x ^ (x >> 16)
+    x = mul(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = mul(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+def leaf_dither(seed, draw, first_row_id, m, replicas, device=None):
+    """belief_ref.leaf_dither_ref in torch int64 ops: u [m, replicas] float64 in [0, 1), a multiple of 2^-24, a pure function of
+    (seed, draw, first_row_id + i * replicas + r). The four words of seed and draw are hashed on the host."""
+    m, R = int(m), int(replicas)
+    seed, draw = int(seed) & _M64, int(draw) & _M64
+    h = 0x9E3779B9
+    for v in (seed & 0xFFFFFFFF, seed >> 32, draw & 0xFFFFFFFF, draw >> 32):
+        h = _mix32(h ^ v)
+    rid = torch.arange(m * R, dtype=torch.int64, device=device).view(m, R) + int(first_row_id)
+    h = _mix32((rid & 0xFFFFFFFF) ^ h)
+    h = _mix32(h ^ ((rid >> 32) & 0xFFFFFFFF))
+    return (h >> 8).double() * 2.0 ** -24
+
+
+def search_leaf(done, final_score, score, q, legal, u, max_score, out=None):
+    """belief_ref.search_leaf_ref in torch, the same bits on any device: done [m, C, R] uint8, final_score and score [m, C, R]
+    int8, q [m, C, R, A] float32 (None: v = 0), legal [m, C, R, A] int8, u [m, R] float64 -> leaf4 [m, C, R] int8 (`out`, when
+    given). Elementwise ops, and one max over the A entries of a row, which no order of evaluation changes."""
+    m, Cn, R = done.shape
+    x = score.double()
+    if q is not None:
+        ok = (legal != 0) & torch.isfinite(q)
+        v = torch.where(ok, q, float("-inf")).amax(-1)
+        x = x + torch.where(ok.any(-1), v, 0.0).double()
+    run = torch.floor(LEAF_SCALE * x + u.view(m, 1, R)).clamp(0, LEAF_SCALE * int(max_score))
+    leaf4 = torch.where((done & 0x80) != 0, LEAF_SCALE * final_score.long(), run.long()).to(torch.int8)
+    return leaf4 if out is None else out.copy_(leaf4)
 
 
 def belief_splice(cfg, prev_rows, det_rows, seat, n_cand, out=None):
@@ -1028,11 +1077,14 @@ class SearchResult:
     hb_belief_select_depth; `depth_used` is None when not computed. With the search's `epsilon` (the soft filter,
     hb_belief_select_soft): `ess` [m] float32, the effective sample size of each root's weighted candidates; None without.
     `sample` is the `BeliefSample` these four are read from (None without a history, and with a `TrackedRows`).
-    With the search's `score_belief`: `belief`, the `BeliefScore` of the replicas searched against the roots' real hands."""
+    With the search's `score_belief`: `belief`, the `BeliefScore` of the replicas searched against the roots' real hands.
+    `horizon`: the search's (None: rollouts to the end); `leaves`: the played games that were still running after `horizon` turns
+    and were valued there (0 without a horizon); `turns` is then at most the horizon."""
 
     def __init__(self, value, wsum, n_live, best, rollouts, turns, dead=0, replicas=0, diff=None, se=None, n_pair=None, cand=None,
-                 best_uid=None, n_surv=None, fallback=None, depth_used=None, ess=None, belief=None, sample=None):
+                 best_uid=None, n_surv=None, fallback=None, depth_used=None, ess=None, belief=None, sample=None, horizon=None, leaves=0):
         self.value, self.wsum, self.n_live, self.best = value, wsum, n_live, best
+        self.horizon, self.leaves = horizon, int(leaves)
         self.rollouts, self.turns, self.dead, self.replicas = int(rollouts), int(turns), int(dead), int(replicas)
         self.diff, self.se, self.n_pair, self.cand, self.best_uid = diff, se, n_pair, cand, best_uid
         self.n_surv, self.fallback, self.depth_used, self.ess, self.belief = n_surv, fallback, depth_used, ess, belief
@@ -1043,14 +1095,18 @@ class SearchResult:
 
 
 def rollout(env, cfg, blueprint, seed, first_seat, forced, done, final_score, length, counters, act, scratch, check_every=8,
-            turn_limit=None):
+            turn_limit=None, horizon=None):
     """Play the games of `env` (auto-reset off, state imported) to the end: turn 0 plays `forced` for seat `first_seat`, turn
     t >= 1 the move of blueprint[(first_seat + t) % P].eval_moves with draw t + 1; hb_eval_tally after every step. `done`
-    (bit 0x80: not played) and `counters` ([0] = games live) are set up by the caller. Returns the number of turns played."""
+    (bit 0x80: not played) and `counters` ([0] = games live) are set up by the caller. Returns the number of turns played.
+    horizon = H (default None: to the end): at most H turns, the forced one included; returns (turns, games still live), and
+    games still live are then no error: seat (first_seat + turns) % P is to act in them, on the env's current observation."""
     L, P, n = K.lib(), cfg.players, env.n
     cfg_ref = C.byref(cfg)
     bufs = tuple(K.dptr(t) for t in (env.reward, env.terminal, env.score, done, final_score, length, counters))
     limit = max_turns(cfg) if turn_limit is None else turn_limit
+    if horizon is not None:
+        limit = min(limit, int(horizon))
     live, t = -1, 0
     while t < limit:
         seat = (first_seat + t) % P
@@ -1066,13 +1122,64 @@ def rollout(env, cfg, blueprint, seed, first_seat, forced, done, final_score, le
             live = int(counters[0].item())
             if live == 0:
                 break
+    if horizon is not None:
+        return t, live
     if live != 0:
         raise RuntimeError(f"{live} rollout games still live after {limit} turns")
     return t
 
 
+def check_horizon(horizon):
+    """horizon as the search keeps it: None (play to the end), or an int >= 1 (a bool or a float is refused)."""
+    if horizon is None:
+        return None
+    if isinstance(horizon, bool) or not isinstance(horizon, int):
+        raise TypeError(f"horizon is a number of turns (an int >= 1) or None, got {horizon!r}")
+    if horizon < 1:
+        raise ValueError(f"horizon must be >= 1 (the forced first move counts), got {horizon}")
+    return horizon
+
+
+def leaf_max_score(cfg):
+    """colors * ranks of a config whose scores fit the int8 score buffer in quarter points; ValueError for any other."""
+    top = int(cfg.colors) * int(cfg.ranks)
+    if LEAF_SCALE * top > 127:
+        raise ValueError(f"a depth-limited search keeps quarter points in int8: {LEAF_SCALE} * colors * ranks = {LEAF_SCALE * top} > 127")
+    return top
+
+
+def leaf_agents(blueprint, leaf, seats=None):
+    """The agents whose eval_q values the leaves, one per seat, or "score": leaf = None (the blueprint's own), a list of one
+    agent per seat, or "score" (no agent: a pure truncated rollout). seats: the seats that can be to act at a leaf; the agent of
+    each must have eval_q (TypeError)."""
+    n = len(blueprint)
+    if isinstance(leaf, str):
+        if leaf != "score":
+            raise ValueError(f'leaf is None, "score" or one agent per seat, got {leaf!r}')
+        return "score"
+    agents = list(blueprint) if leaf is None else list(leaf)
+    if len(agents) != n:
+        raise ValueError(f"one leaf agent per seat: {n} players, {len(agents)} agents")
+    for s in range(n) if seats is None else seats:
+        if not hasattr(agents[s], "eval_q"):
+            raise TypeError(f"{type(agents[s]).__name__} (seat {s}) has no eval_q() to value a leaf with: pass leaf=[one agent with eval_q "
+                            f'per seat] (a DQNAgent), or leaf="score" for a truncated rollout that counts the score so far')
+    return agents
+
+
 class RolloutSearch:
     """Value of every root action under `blueprint` by belief-sampled rollouts; see the module docstring.
+
+    horizon = H (default None: every rollout is played to the end, and nothing below exists), leaf: depth-limited rollouts.
+    A rollout plays H turns, the forced first move included; a game still running then is worth its score so far plus the
+    largest legal q of `eval_q` of the seat then to act, (cp + H) % P, asked once on the env's current observation: leaf = None
+    asks the blueprint's own agent of that seat (TypeError when it has no eval_q), leaf = [one agent per seat] any agents with
+    eval_q (a DQNAgent valuing a rule list's states), leaf = "score" nobody (v = 0: a pure truncated rollout). The values are
+    rounded to quarter points with a dither shared by the slots of a replica (`search_leaf`, `leaf_dither`: stochastic
+    rounding, unbiased, and the paired differences keep their common random numbers) into an int8 buffer [m, C, R] that
+    hb_search_reduce and hb_search_compare read as they read the final scores; value, diff and se are divided by 4, which is
+    exact. When no game reaches the horizon running, nothing of this runs and the result is the full search's, bit for bit.
+    The result carries `horizon` and `leaves`, the played games valued at the horizon.
 
     first_game_id: global id of rollout game 0 (keys the blueprint's draws, like Evaluator's). The rollout env and every
     buffer are built by the first search of a size (m roots, C slots — run(): the A actions —, replicas) and kept for the next,
@@ -1090,9 +1197,10 @@ class RolloutSearch:
     right after the determinization (hb_belief_score) and the result carries `belief`; the search itself is unchanged."""
 
     def __init__(self, game="Hanabi-Full", players=2, replicas=32, seed=1, device=None, config=None, check_every=8, first_game_id=0,
-                 oversample=8, epsilon=None, score_belief=False):
+                 oversample=8, epsilon=None, score_belief=False, horizon=None, leaf=None):
         self.cfg = eval_config(game, players, config)
         self.players = self.cfg.players
+        self.set_horizon(horizon, leaf)
         self.replicas = int(replicas)
         if self.replicas < 1:
             raise ValueError(f"replicas must be >= 1, got {replicas}")
@@ -1118,6 +1226,17 @@ class RolloutSearch:
         self.n_counters = K.lib().hb_eval_counters(C.byref(self.cfg))
         self._sized = {}   # (m, C, replicas) -> the rollout env and buffers of that size, with the scratch of its blueprint
         self._uid = None   # [1, A] int32: every uid, on the device (built by the first run())
+
+    def set_horizon(self, horizon, leaf=None):
+        """The horizon and leaf agents of the searches from here on (the constructor's arguments, and its checks)."""
+        horizon = check_horizon(horizon)
+        if horizon is not None:
+            self.max_score = leaf_max_score(self.cfg)
+            if leaf is not None:
+                leaf_agents([None] * self.players, leaf, seats=())   # (the checks that need neither blueprint nor seat)
+        elif leaf is not None:
+            raise ValueError("leaf= values the games a horizon cuts short: it needs horizon=H")
+        self.horizon, self.leaf = horizon, leaf
 
     def _setup(self, m, Cn, R, first_game_id, dev):
         b = self._sized.get((m, Cn, R))
@@ -1179,8 +1298,13 @@ class RolloutSearch:
         (m, Cn), dev = cand.shape, r.device
         b = self._setup(m, Cn, R, first_game_id, dev)
         if not cps:
-            return self._nothing(m, Cn, dev, compared=base_slot is not None)
+            res = self._nothing(m, Cn, dev, compared=base_slot is not None)
+            res.horizon = self.horizon
+            return res
         cp, env = int(cps[0]), b["env"]
+        H, leaves = self.horizon, 0
+        if H is not None:   # (before anything is played: the agent that values a leaf must be able to)
+            valuers = leaf_agents(blueprint, self.leaf, seats=((cp + H) % self.players,))
         n_surv = fallback = depth_used = ess = sample = None
         with torch.cuda.device(dev):
             if history is None:
@@ -1214,17 +1338,40 @@ class RolloutSearch:
             env.import_state(b["rows"])
             illegal0 = env.illegal_count()
             turns = rollout(env, self.cfg, blueprint, self.seed, cp, b["forced"], b["done"], b["final_score"], b["length"],
-                            b["counters"], b["act"], b["scratch"], self.check_every)
+                            b["counters"], b["act"], b["scratch"], self.check_every, horizon=H)
+            if H is not None:
+                turns, leaves = turns
             illegal = env.illegal_count() - illegal0
             if illegal:
                 raise RuntimeError(f"{illegal} illegal moves in the rollouts (a candidate that is illegal at its root, or the blueprint's)")
+            if leaves:   # games cut short by the horizon: every game's value in quarter points, where the final scores were read
+                scores = self._leaves(b, valuers, (cp + turns) % self.players, m, Cn, R, draw, first_row_id)
             value, wsum, n_live, best = search_reduce(scores, weights, slots)
             rollouts, dead, roots = counts.tolist()
             res = SearchResult(value, wsum, n_live, best, rollouts, turns, dead=dead, replicas=roots * R, n_surv=n_surv,
-                               fallback=fallback, depth_used=depth_used, ess=ess, belief=belief, sample=sample)
+                               fallback=fallback, depth_used=depth_used, ess=ess, belief=belief, sample=sample, horizon=H, leaves=leaves)
             if base_slot is not None:
                 res.diff, res.se, res.n_pair = search_compare(scores, weights, cand, base_slot)
+            if leaves:   # quarter points -> points: a division by a power of two, exact
+                res.value = value / LEAF_SCALE
+                if base_slot is not None:
+                    res.diff, res.se = res.diff / LEAF_SCALE, res.se / LEAF_SCALE
         return res
+
+    def _leaves(self, b, valuers, seat, m, Cn, R, draw, first_row_id):
+        """The leaf step (class docstring) on the rollout env of `b` as the horizon left it, `seat` to act in every running game ->
+        the quarter-point buffer [m, C, R] int8 of this size (built by the first search that reaches a leaf)."""
+        env, A = b["env"], self.num_actions
+        leaf4 = b.get("leaf4")
+        if leaf4 is None:
+            leaf4 = b["leaf4"] = torch.empty((m, Cn, R), dtype=torch.int8, device=env.device)
+        q = None
+        if valuers != "score":
+            agent = valuers[seat]
+            q = agent.eval_q((env, (env.net_obs, env.legal)), scratch=b["scratch"].setdefault(agent, {})).view(m, Cn, R, A)
+        u = leaf_dither(self.seed, draw, first_row_id, m, R, device=env.device)
+        return search_leaf(b["done"].view(m, Cn, R), b["final_score"].view(m, Cn, R), env.score.view(m, Cn, R), q,
+                           env.legal.view(m, Cn, R, A), u, self.max_score, out=leaf4)
 
     @torch.no_grad()
     def run(self, rows, legal, blueprint, draw, seat=None, baseline=None, history=None):
@@ -1386,18 +1533,27 @@ class SearchPlayer:
 
     score_belief (default False: nothing is computed or allocated, and the moves played are the same bits either way): every
     first-stage search scores its replicas against the real hands (RolloutSearch's score_belief, hb_belief_score) and the player
-    adds the sums up on the device; belief_stats() gives the means."""
+    adds the sums up on the device; belief_stats() gives the means.
 
-    COUNTERS = ("moves", "deviations", "confirmed", "rejected", "conditioned", "unconditioned", "survivors", "candidates", "fallbacks",
+    horizon, leaf (defaults None: rollouts to the end, the player above bit for bit): RolloutSearch's depth-limited rollouts, in
+    both stages. The seat whose agent values the leaves is (seat + horizon) % P; with leaf=None it is the blueprint's own agent of
+    that seat and must have eval_q (TypeError here, at construction). `leaf_games` totals the rollout games valued at the horizon."""
+
+    COUNTERS =("moves", "deviations", "confirmed", "rejected", "conditioned", "unconditioned", "survivors", "candidates", "fallbacks",
                 "depth_used")
     TRACK_COUNTERS = ("tracked", "restarts", "carried_live")
 
     def __init__(self, blueprint, seat, replicas=32, threshold=0.0, seed=1, check_every=8, z=None, confirm_replicas=0,
-                 condition=False, oversample=8, depth=1, epsilon=None, score_belief=False, track=False):
+                 condition=False, oversample=8, depth=1, epsilon=None, score_belief=False, track=False, horizon=None, leaf=None):
         self.blueprint = list(blueprint)
         self.seat = int(seat)
         if not 0 <= self.seat < len(self.blueprint):
             raise ValueError(f"seat {seat} out of range for {len(self.blueprint)} players")
+        self.horizon, self.leaf = check_horizon(horizon), leaf
+        if self.horizon is not None:   # the one seat that can be to act at a leaf of this player's searches
+            leaf_agents(self.blueprint, leaf, seats=((self.seat + self.horizon) % len(self.blueprint),))
+        elif leaf is not None:
+            raise ValueError("leaf= values the games a horizon cuts short: it needs horizon=H")
         self.own = self.blueprint[self.seat]
         for a in self.blueprint:
             if not hasattr(a, "eval_moves"):
@@ -1456,6 +1612,7 @@ class SearchPlayer:
     def reset_stats(self):
         self._stats = None   # [len(COUNTERS)] int64 on the device, built by the first eval_moves: read through the properties
         self.dead_replicas = self.replicas_drawn = self.searches = self.rollouts = 0
+        self.leaf_games = 0   # horizon: rollout games valued at the horizon instead of played out (both stages)
         self._by_depth = None   # depth > 1: [4, depth] int64 on the device, see depth_stats()
         self._ess = None        # epsilon: [2] float64 on the device, sum of ess and count over the conditioned roots
         self._belief = None     # score_belief: [2, len(BeliefScore.SUMS), H] float64 on the device (conditioned roots, the others)
@@ -1562,7 +1719,7 @@ class SearchPlayer:
         if self._search is None or self._search.cfg.players != env.cfg.players:
             self._search = RolloutSearch(config=env.cfg, replicas=self.replicas, seed=self.seed, device=env.device,
                                          check_every=self.check_every, oversample=self.oversample, epsilon=self.epsilon,
-                                         score_belief=self.score_belief)
+                                         score_belief=self.score_belief, horizon=self.horizon, leaf=self.leaf)
         rows = env.export_state()
         staged = self.z is not None or self.confirm_replicas > 0
         history = None
@@ -1592,6 +1749,7 @@ class SearchPlayer:
         deviate = (ok & ((v_best - v_bp) > self.threshold)).view(-1) & live   # (NaN compares false)
         counts = {}   # this call's share of the device counters
         self.rollouts += res.rollouts
+        self.leaf_games += res.leaves
         if staged:
             challenger = deviate & (res.best != actions_out)
             if self.confirm_replicas > 0:
@@ -1601,6 +1759,7 @@ class SearchPlayer:
                                                   torch.where(challenger, res.best, -1), self.confirm_replicas, history=history)
                     deviate = challenger & self._significant(second.diff[:, 1], second.se[:, 1], self.z or 0.0)
                     self.rollouts += second.rollouts
+                    self.leaf_games += second.leaves
                 counts.update(confirmed=challenger.sum(), rejected=(challenger & ~deviate).sum())
             else:
                 deviate = challenger & self._significant(res.diff.gather(1, best).view(-1), res.se.gather(1, best).view(-1), self.z)
