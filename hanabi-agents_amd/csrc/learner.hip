@@ -22,11 +22,14 @@
 #include <hip/hip_fp16.h>
 
 #include "../../include/hanabi_hip.h"
+#include "adam_rule.hpp"
 #include "common.hpp"
 
 using hb::fail;
 
 namespace {
+
+using namespace hb::adam;
 
 template <typename T> __device__ __forceinline__ float ld(const T* p, long long i);
 template <> __device__ __forceinline__ float ld<float>(const float* p, long long i) { return p[i]; }
@@ -247,208 +250,26 @@ __global__ __launch_bounds__(1024) void relu_bwd_colsum_kernel(T* __restrict__ d
 }
 
 // ---------------------------------------------------------------------------------------------
-struct AdamArgs {
-  float *w, *w_mu, *w_sigma;
-  const float* noise;  // eps of the layer (same shape); bias noise for bias tensors
-  const void* grad;    // d loss / d (merged tensor): fp32 / bf16 / f16 (grad_dtype), rows grad_ld elements apart
-  float *m_w, *v_w, *m_mu, *v_mu, *m_sg, *v_sg;
-  const float* step;   // number of completed Adam steps (device scalar)
-  void* eff;           // merged tensor in the GEMM dtype for the next forward
-  long long n;
-  int cols, eff_ld;    // parameter tensors are [n/cols, cols] row-major; eff rows are eff_ld >= cols elements apart
-  int grad_dtype, grad_ld;
-  float lr, b1, b2, eps;
-  float step_offset;   // this step's number t = *step + step_offset
-};
-
-__device__ __forceinline__ float load_grad(const void* g, int dtype, long long i) {
-  if (dtype == 1) return __bfloat162float(static_cast<const __hip_bfloat16*>(g)[i]);
-  if (dtype == 2) return __half2float(static_cast<const __half*>(g)[i]);
-  return static_cast<const float*>(g)[i];
-}
-
-__device__ __forceinline__ float adam1(float p, float g, float& m, float& v, float b1, float b2, float bc1, float bc2s,
-                                       float lr, float eps) {
-  // explicit roundings (no compiler-chosen FMA contraction): the scalar and the 4-wide kernels must agree bit for bit
-  m = __fmaf_rn(b1, m, __fmul_rn(1.f - b1, g));
-  v = __fmaf_rn(b2, v, __fmul_rn(__fmul_rn(1.f - b2, g), g));
-  // torch.optim.Adam / optix.adam: eps outside the sqrt
-  return __fsub_rn(p, __fdiv_rn(__fmul_rn(lr / bc1, m), __fadd_rn(__fdiv_rn(sqrtf(v), bc2s), eps)));
-}
-// The step Adam takes for moments (m, v): p_new = p - adam_step(...). w and w_mu of a NoisyLinear always see the same
-// gradient, so their moments are equal for ever; a caller may pass the SAME moment arrays for both (m_mu == m_w,
-// v_mu == v_w) and the kernels then apply w's step to w_mu without touching the moments a second time.
-__device__ __forceinline__ float adam_step(float m, float v, float bc1, float bc2s, float lr, float eps) {
-  return __fdiv_rn(__fmul_rn(lr / bc1, m), __fadd_rn(__fdiv_rn(sqrtf(v), bc2s), eps));
-}
-__device__ __forceinline__ float merged(float w, float mu, float sg, float nz) {  // W = w + w_mu + w_sigma * noise
-  return __fadd_rn(__fadd_rn(w, mu), __fmul_rn(sg, nz));
-}
-
+// AdamArgs / AdamMulti and the per-element rule (adam1, step_element, step_group, step_block): adam_rule.hpp, shared with
+// learner_tail_l2_dw1_kernel (learner2.hip)
 template <typename T>
 __global__ __launch_bounds__(256) void noisy_adam_kernel(const AdamArgs a) {
-  const float t = *a.step + a.step_offset;
-  const float bc1 = 1.f - powf(a.b1, t), bc2s = sqrtf(1.f - powf(a.b2, t));
-  T* eff = static_cast<T*>(a.eff);
+  float bc1, bc2s;
+  bias_corrections(a, bc1, bc2s);
   for (long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x; i < a.n;
-       i += static_cast<long long>(gridDim.x) * blockDim.x) {
-    const long long row = i / a.cols, col = i - row * a.cols;
-    const float g = load_grad(a.grad, a.grad_dtype, row * a.grad_ld + col), nz = a.noise[i];
-    float m, v;
-    m = a.m_w[i]; v = a.v_w[i];
-    const float w = adam1(a.w[i], g, m, v, a.b1, a.b2, bc1, bc2s, a.lr, a.eps);
-    a.m_w[i] = m; a.v_w[i] = v; a.w[i] = w;
-    float mu;
-    if (a.m_mu == a.m_w) {  // shared moments: (m, v) are w's, already advanced
-      mu = __fsub_rn(a.w_mu[i], adam_step(m, v, bc1, bc2s, a.lr, a.eps));
-    } else {
-      m = a.m_mu[i]; v = a.v_mu[i];
-      mu = adam1(a.w_mu[i], g, m, v, a.b1, a.b2, bc1, bc2s, a.lr, a.eps);
-      a.m_mu[i] = m; a.v_mu[i] = v;
-    }
-    a.w_mu[i] = mu;
-    m = a.m_sg[i]; v = a.v_sg[i];
-    const float sg = adam1(a.w_sigma[i], __fmul_rn(g, nz), m, v, a.b1, a.b2, bc1, bc2s, a.lr, a.eps);
-    a.m_sg[i] = m; a.v_sg[i] = v; a.w_sigma[i] = sg;
-    st<T>(eff, row * a.eff_ld + col, merged(w, mu, sg, nz));
-  }
+       i += static_cast<long long>(gridDim.x) * blockDim.x)
+    step_element<T>(a, i, bc1, bc2s);
 }
 
-// all merged tensors of the network in ONE launch: workgroup b belongs to tensor t where first[t] <= b < first[t+1]
-struct AdamMulti {
-  AdamArgs t[8];
-  int first[9];
-  int count;
-};
-
-// W consecutive elements per thread (one 16- or 8-byte access per array); every tensor has cols % 4 == 0, n < 2^31 and
-// 16-byte aligned rows (checked on the host), so a group never straddles a row
-// W consecutive elements per thread. W = 4 (16-byte accesses, 72 registers) is the form that runs; W = 2 (8-byte accesses,
-// 44 registers) fits into the 48 registers per SIMD lane the one-kernel actor (csrc/actor_fused.hip) leaves free and so runs
-// BESIDE the policy kernel instead of waiting for it — measured slower in the loop (hb_noisy_adam_multi below; DESIGN
-// section 5c "Co-residency"), kept for measurements. Same arithmetic per element in every form (adam1's explicit roundings).
-template <int W> struct VecW;
-template <> struct VecW<4> { typedef float4 type; };
-template <> struct VecW<2> { typedef float2 type; };
-// (element offsets are 32-bit unsigned — the host checks n < 2^30 — so every access is "scalar base + 32-bit lane offset": one
-//  address register per thread instead of a 64-bit pair per array)
-template <int W>
-__device__ __forceinline__ void ldw(const float* p, uint32_t off, float out[W]) {
-  const typename VecW<W>::type v = *reinterpret_cast<const typename VecW<W>::type*>(reinterpret_cast<const char*>(p) + static_cast<uint64_t>(off << 2));
-  const float* f = reinterpret_cast<const float*>(&v);
-#pragma unroll
-  for (int k = 0; k < W; ++k) out[k] = f[k];
-}
-template <int W>
-__device__ __forceinline__ void stw(float* p, uint32_t off, const float in[W]) {
-  typename VecW<W>::type v;
-  float* f = reinterpret_cast<float*>(&v);
-#pragma unroll
-  for (int k = 0; k < W; ++k) f[k] = in[k];
-  *reinterpret_cast<typename VecW<W>::type*>(reinterpret_cast<char*>(p) + static_cast<uint64_t>(off << 2)) = v;
-}
-template <int W>
-__device__ __forceinline__ void load_gradw(const void* g, int dtype, uint32_t i, float out[W]) {
-  if (dtype == 0) {
-    ldw<W>(static_cast<const float*>(g), i, out);
-  } else if (dtype == 1) {
-    const uint32_t* p = reinterpret_cast<const uint32_t*>(static_cast<const char*>(g) + static_cast<uint64_t>(i << 1));
-    if constexpr (W == 4) {
-      const uint2 v = *reinterpret_cast<const uint2*>(p);
-      out[0] = __uint_as_float(v.x << 16); out[1] = __uint_as_float(v.x & 0xFFFF0000u);
-      out[2] = __uint_as_float(v.y << 16); out[3] = __uint_as_float(v.y & 0xFFFF0000u);
-    } else {
-      const uint32_t v = *p;
-      out[0] = __uint_as_float(v << 16); out[1] = __uint_as_float(v & 0xFFFF0000u);
-    }
-  } else {
-    const __half* h = reinterpret_cast<const __half*>(static_cast<const char*>(g) + static_cast<uint64_t>(i << 1));
-#pragma unroll
-    for (int k = 0; k < W; ++k) out[k] = __half2float(h[k]);
-  }
-}
-
+// W consecutive elements per thread (W = 4 is the form that runs, W = 2 the 44-register one: adam_rule.hpp)
 template <typename T, int W>
 __global__ __launch_bounds__(256) void noisy_adam_multiw_kernel(const AdamMulti m) {
-  constexpr int SH = W == 4 ? 2 : 1;
-  int ti = 0;
-  while (ti + 1 < m.count && static_cast<int>(blockIdx.x) >= m.first[ti + 1]) ++ti;
-  const AdamArgs& a = m.t[ti];
-  const float t = *a.step + a.step_offset;
-  const float bc1 = 1.f - powf(a.b1, t), bc2s = sqrtf(1.f - powf(a.b2, t));
-  T* eff = static_cast<T*>(a.eff);
-  const int nw = static_cast<int>(a.n >> SH), cw = a.cols >> SH;
-  // (no grid-stride loop: the host launches one thread per group, so no address becomes a loop-carried 64-bit pointer)
-  const int q = (static_cast<int>(blockIdx.x) - m.first[ti]) * 256 + static_cast<int>(threadIdx.x);
-  if (q < nw) {
-    const int row = q / cw, col = (q - row * cw) << SH;
-    const uint32_t i = static_cast<uint32_t>(q) << SH;
-    float g[W], nz[W];
-    load_gradw<W>(a.grad, a.grad_dtype, static_cast<uint32_t>(row) * static_cast<uint32_t>(a.grad_ld) + col, g);
-    ldw<W>(a.noise, i, nz);
-    float res[3][W], lm[W], lv[W];
-    auto one = [&](float* p, float* mp, float* vp, int which) {
-      float pa[W], ma[W], va[W];
-      ldw<W>(p, i, pa); ldw<W>(mp, i, ma); ldw<W>(vp, i, va);
-#pragma unroll
-      for (int k = 0; k < W; ++k) {
-        pa[k] = adam1(pa[k], which == 2 ? __fmul_rn(g[k], nz[k]) : g[k], ma[k], va[k], a.b1, a.b2, bc1, bc2s, a.lr, a.eps);
-        res[which][k] = pa[k];
-        lm[k] = ma[k];
-        lv[k] = va[k];
-      }
-      stw<W>(p, i, pa); stw<W>(mp, i, ma); stw<W>(vp, i, va);
-    };
-    one(a.w, a.m_w, a.v_w, 0);
-
-    if (a.m_mu == a.m_w) {  // shared moments: apply w's step to w_mu
-      float pv[W];
-      ldw<W>(a.w_mu, i, pv);
-#pragma unroll
-      for (int k = 0; k < W; ++k) res[1][k] = pv[k] = __fsub_rn(pv[k], adam_step(lm[k], lv[k], bc1, bc2s, a.lr, a.eps));
-      stw<W>(a.w_mu, i, pv);
-    } else {
-      one(a.w_mu, a.m_mu, a.v_mu, 1);
-    }
-
-    one(a.w_sigma, a.m_sg, a.v_sg, 2);
-    const uint32_t e = static_cast<uint32_t>(row) * static_cast<uint32_t>(a.eff_ld) + col;
-#pragma unroll
-    for (int k = 0; k < W; ++k) st<T>(eff, e + k, merged(res[0][k], res[1][k], res[2][k], nz[k]));
-  }
+  step_block<T, W>(m, static_cast<int>(blockIdx.x), static_cast<int>(threadIdx.x));
 }
 
 template <typename T>
 __global__ __launch_bounds__(256) void noisy_adam_multi_kernel(const AdamMulti m) {
-  int ti = 0;
-  while (ti + 1 < m.count && static_cast<int>(blockIdx.x) >= m.first[ti + 1]) ++ti;
-  const AdamArgs& a = m.t[ti];
-  const int nb = m.first[ti + 1] - m.first[ti];
-  const float t = *a.step + a.step_offset;
-  const float bc1 = 1.f - powf(a.b1, t), bc2s = sqrtf(1.f - powf(a.b2, t));
-  T* eff = static_cast<T*>(a.eff);
-  for (long long i = static_cast<long long>(blockIdx.x - m.first[ti]) * 256 + threadIdx.x; i < a.n;
-       i += static_cast<long long>(nb) * 256) {
-    const long long row = i / a.cols, col = i - row * a.cols;
-    const float g = load_grad(a.grad, a.grad_dtype, row * a.grad_ld + col), nz = a.noise[i];
-    float mm, vv;
-    mm = a.m_w[i]; vv = a.v_w[i];
-    const float w = adam1(a.w[i], g, mm, vv, a.b1, a.b2, bc1, bc2s, a.lr, a.eps);
-    a.m_w[i] = mm; a.v_w[i] = vv; a.w[i] = w;
-    float mu;
-    if (a.m_mu == a.m_w) {
-      mu = __fsub_rn(a.w_mu[i], adam_step(mm, vv, bc1, bc2s, a.lr, a.eps));
-    } else {
-      mm = a.m_mu[i]; vv = a.v_mu[i];
-      mu = adam1(a.w_mu[i], g, mm, vv, a.b1, a.b2, bc1, bc2s, a.lr, a.eps);
-      a.m_mu[i] = mm; a.v_mu[i] = vv;
-    }
-    a.w_mu[i] = mu;
-    mm = a.m_sg[i]; vv = a.v_sg[i];
-    const float sg = adam1(a.w_sigma[i], __fmul_rn(g, nz), mm, vv, a.b1, a.b2, bc1, bc2s, a.lr, a.eps);
-    a.m_sg[i] = mm; a.v_sg[i] = vv; a.w_sigma[i] = sg;
-    st<T>(eff, row * a.eff_ld + col, merged(w, mu, sg, nz));
-  }
+  step_block<T, 1>(m, static_cast<int>(blockIdx.x), static_cast<int>(threadIdx.x));
 }
 
 // ---- Adam that also writes the copies the forward kernels read (round 3) -----------------------------
@@ -710,43 +531,31 @@ int hb_noisy_adam_multi(const hb_adam_tensor* tensors, int32_t count, const floa
                         float lr, float beta1, float beta2, float eps, void* stream) {
   if (!tensors || !step_dev) return fail(HB_ERR_INVALID, "null argument");
   if (count < 1 || count > 8) return fail(HB_ERR_INVALID, "count must be 1..8");
+  // a gradient-product entry (gx != NULL): the other entries' step and the product share one launch (learner2.hip)
+  int prod = -1;
+  for (int i = 0; i < count; ++i) {
+    if (!tensors[i].gx) continue;
+    if (prod >= 0) return fail(HB_ERR_INVALID, "at most one gradient-product entry (tensors %d and %d)", prod, i);
+    prod = i;
+  }
+  if (prod >= 0) {
+    hb_adam_tensor steps[8];
+    int n_steps = 0;
+    for (int i = 0; i < count; ++i)
+      if (i != prod) steps[n_steps++] = tensors[i];
+    return launch_tail(steps, n_steps, tensors[prod], step_dev, step_offset, eff_dtype, lr, beta1, beta2, eps, stream);
+  }
   AdamMulti m{};
-  m.count = count;
   int blocks = 0;
-  bool vec4 = true;  // several elements per thread when every tensor allows 16-byte accesses
   // Elements per thread: 4 by default; HB_ADAM_WIDTH=2 is the 44-register form that fits beside the one-kernel actor, =1 the
   // scalar one (36 registers). Same arithmetic per element in all three. Measured in the benched loop (round 3, same box,
   // alternating): 4 -> 0.112-0.114 ms per step, 2 -> 0.120, 1 -> 0.117: an Adam that shares the CUs with the policy kernel
   // streams its 55 MB through the L2 the policy kernel's weights live in and itself runs at one workgroup per CU; waiting for
   // the CUs is faster. The narrow forms stay for measurements (profiles/r03/README.md).
-  const int width = [] { const char* e = getenv("HB_ADAM_WIDTH"); const int w = e ? atoi(e) : 4; return w == 2 || w == 1 ? w : 4; }();
-  if (width == 1) vec4 = false;
-  for (int i = 0; i < count; ++i) {
-    const hb_adam_tensor& d = tensors[i];
-    const int gl = d.grad_ld ? d.grad_ld : d.cols;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-    // (32-bit element offsets inside the vector kernels: n < 2^30, rows * row stride < 2^31)
-    vec4 = vec4 && d.cols > 0 && d.cols % 4 == 0 && d.n % 4 == 0 && d.n < (1LL << 30) &&
-           (d.n / d.cols) * static_cast<long long>(d.eff_ld > gl ? d.eff_ld : gl) < (1LL << 31) && d.eff_ld % 4 == 0 && gl % 4 == 0 && al16(d.w) &&
-           al16(d.w_mu) && al16(d.w_sigma) && al16(d.noise) && al16(d.grad) && al16(d.m_w) && al16(d.v_w) && al16(d.m_mu) &&
-           al16(d.v_mu) && al16(d.m_sigma) && al16(d.v_sigma);
-  }
-  for (int i = 0; i < count; ++i) {
-    const hb_adam_tensor& d = tensors[i];
-    if (!d.w || !d.w_mu || !d.w_sigma || !d.noise || !d.grad || !d.m_w || !d.v_w || !d.m_mu || !d.v_mu || !d.m_sigma ||
-        !d.v_sigma || !d.eff)
-      return fail(HB_ERR_INVALID, "null pointer in tensor %d", i);
-    if (d.n <= 0 || d.cols < 1 || d.eff_ld < d.cols || d.n % d.cols) return fail(HB_ERR_INVALID, "bad shape in tensor %d", i);
-    if (d.grad_dtype < 0 || d.grad_dtype > 2 || (d.grad_ld != 0 && d.grad_ld < d.cols))
-      return fail(HB_ERR_INVALID, "bad gradient dtype / row stride in tensor %d", i);
-    m.t[i] = AdamArgs{d.w, d.w_mu, d.w_sigma, d.noise, d.grad, d.m_w, d.v_w, d.m_mu, d.v_mu, d.m_sigma, d.v_sigma,
-                      step_dev, d.eff, d.n, d.cols, d.eff_ld, d.grad_dtype, d.grad_ld ? d.grad_ld : d.cols, lr, beta1, beta2, eps, step_offset};
-    m.first[i] = blocks;
-    long long nb = ((vec4 ? d.n / width : d.n) + 255) / 256;
-    if (!vec4 && nb > 1024) nb = 1024;   // (the vector kernels take one group per thread, the scalar one strides)
-    blocks += static_cast<int>(nb);
-  }
-  m.first[count] = blocks;
+  const int asked = [] { const char* e = getenv("HB_ADAM_WIDTH"); const int w = e ? atoi(e) : 4; return w == 2 || w == 1 ? w : 4; }();
+  const int width = plan_multi(tensors, count, step_dev, step_offset, lr, beta1, beta2, eps, asked, m, &blocks);
+  if (width < 0) return width;
+  const bool vec4 = width != 1;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (vec4 && width == 4 && eff_dtype == 0) hipLaunchKernelGGL((noisy_adam_multiw_kernel<float, 4>), dim3(blocks), dim3(256), 0, s, m);
   else if (vec4 && width == 4 && eff_dtype == 1) hipLaunchKernelGGL((noisy_adam_multiw_kernel<__hip_bfloat16, 4>), dim3(blocks), dim3(256), 0, s, m);

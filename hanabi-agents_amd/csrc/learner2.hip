@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "../../include/hanabi_hip.h"
+#include "adam_rule.hpp"
 #include "common.hpp"
 
 using hb::fail;
@@ -659,6 +660,107 @@ __global__ __launch_bounds__(64) void thin_gemm_kernel(const ThinArgs a, const i
   }
 }
 
+// ---- the update's tail: the output layer's optimizer step BESIDE the first layer's weight gradient, one launch ---------------
+// After hb_c51_backward the update still owes dW1 = X^T dH and the optimizer step. Only the first layer's step reads dW1; the
+// output layer's (W2 and b2, 59 % of the merged parameters) needs dW2 and db2 alone. As a library GEMM dW1 is launch- and
+// latency-bound (K is the batch: 185 MFLOP on 88 tiles of a 256-CU chip) and the whole step waited behind it. Here the two
+// share a launch: a workgroup takes one of two ROLES by its index, the roles share no data — no grid-wide synchronisation.
+//   role A, workgroups [0, g_adam): the step of adam_rule.hpp on the caller's table entries, the arithmetic and the
+//           element -> thread mapping of noisy_adam_multiw_kernel (W = 4) / noisy_adam_multi_kernel (W = 1)
+//   role B, the rest: one 32 x 64 tile of dW1 [k_rows, hidden] each. Both operands are stored with the CONTRACTED index (the
+//           sample) slowest, MFMA fragments want 8 consecutive samples per lane: the tile's operand columns go through LDS
+//           transposed ([column][sample], rows 264 halfwords apart: 16-byte aligned, 132 dwords = 4 banks apart), samples
+//           >= batch zero-filled up to the next K step. Each of the four wavefronts then owns 32 rows x 16 columns: per K step
+//           of 32 samples one dH fragment, two X fragments (ds_read_b128 each), two v_mfma_f32_16x16x32, fp32 accumulation in
+//           ascending sample order; rounded once to the operand dtype, 4 consecutive columns per lane.
+// This launch runs in the update's whole-CU window, never beside the policy kernel: registers and LDS (50 KB) are not budgeted.
+struct TailArgs {
+  hb::adam::AdamMulti adam;
+  const unsigned char* x;    // [batch][ldx], 16-bit
+  const unsigned char* dh;   // [batch][dh_ld], 16-bit
+  unsigned char* dw1;        // [k_rows][dw1_ld], 16-bit
+  int batch, k_rows, hidden;
+  unsigned ldx, dh_ld, dw1_ld;
+  int g_adam;                // role A's workgroups
+  int col_tiles;             // role B: 64-column tiles per 32-row tile
+};
+constexpr int kTailLd = 264;   // halfwords between the LDS rows of a transposed operand column (256 samples + 8)
+
+// 8 consecutive columns of sample b (one 16-byte load, or zeros) -> LDS rows col .. col + 7 at sample b
+__device__ __forceinline__ void tail_scatter(uint16_t* lds, int col, int b, const uint4& v) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    lds[(col + 2 * i) * kTailLd + b] = static_cast<uint16_t>(w[i] & 0xFFFFu);
+    lds[(col + 2 * i + 1) * kTailLd + b] = static_cast<uint16_t>(w[i] >> 16);
+  }
+}
+
+template <bool F16, int W>
+__global__ __launch_bounds__(256) void learner_tail_l2_dw1_kernel(const TailArgs a) {
+  typedef typename std::conditional<F16, __half, __hip_bfloat16>::type T;
+  __shared__ __attribute__((aligned(16))) uint16_t xt[32 * kTailLd];   // [row of the tile = column of X][sample]
+  __shared__ __attribute__((aligned(16))) uint16_t dt[64 * kTailLd];   // [column of the tile = column of dH][sample]
+  const int tid = static_cast<int>(threadIdx.x);
+  if (static_cast<int>(blockIdx.x) < a.g_adam) {
+    hb::adam::step_block<T, W>(a.adam, static_cast<int>(blockIdx.x), tid);
+    return;
+  }
+  const int tile = static_cast<int>(blockIdx.x) - a.g_adam;
+  const int rt = tile / a.col_tiles, ctile = tile - rt * a.col_tiles;
+  const int r0 = rt * 32, c0 = ctile * 64;
+  const int kb = (a.batch + 31) & ~31;   // samples the K loop covers (batch <= 256: the host checks)
+  // every load of the tile first (12 per thread at batch 256), then the transposing 2-byte LDS writes
+  uint4 xv[4], dv[8];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {   // X: 4 chunks of 8 columns per sample
+    const int c = tid + it * 256, b = c >> 2, col = r0 + (c & 3) * 8;
+    xv[it] = make_uint4(0u, 0u, 0u, 0u);
+    // (a chunk that starts below k_rows may end above it, inside the row: ldx >= k_rows rounded up to 8; those rows are not stored)
+    if (b < a.batch && col < a.k_rows) xv[it] = *reinterpret_cast<const uint4*>(a.x + (static_cast<size_t>(b) * a.ldx + col) * 2u);
+  }
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {   // dH: 8 chunks per sample
+    const int c = tid + it * 256, b = c >> 3, col = c0 + (c & 7) * 8;
+    dv[it] = make_uint4(0u, 0u, 0u, 0u);
+    if (b < a.batch && col < a.hidden) dv[it] = *reinterpret_cast<const uint4*>(a.dh + (static_cast<size_t>(b) * a.dh_ld + col) * 2u);
+  }
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int c = tid + it * 256, b = c >> 2;
+    if (b < kb) tail_scatter(xt, (c & 3) * 8, b, xv[it]);
+  }
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    const int c = tid + it * 256, b = c >> 3;
+    if (b < kb) tail_scatter(dt, (c & 7) * 8, b, dv[it]);
+  }
+  __syncthreads();
+  const int lane = tid & 63, wave = tid >> 6;
+  const int lr = lane & 15, kq = lane >> 4;
+  const uint16_t* dp = dt + (wave * 16 + lr) * kTailLd + kq * 8;
+  const uint16_t* xp0 = xt + lr * kTailLd + kq * 8;
+  const uint16_t* xp1 = xp0 + 16 * kTailLd;
+  tg_f32x4 acc0 = tg_f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+  for (int k0 = 0; k0 < kb; k0 += 32) {
+    const uint4 d = *reinterpret_cast<const uint4*>(dp + k0);
+    const uint4 x0 = *reinterpret_cast<const uint4*>(xp0 + k0), x1 = *reinterpret_cast<const uint4*>(xp1 + k0);
+    acc0 = tg_mfma<F16>(d, x0, acc0);
+    acc1 = tg_mfma<F16>(d, x1, acc1);
+  }
+  // acc_m[j] = dW1[r0 + 16 m + (lane & 15)][c0 + 16 wave + 4 (lane >> 4) + j] (the fragment layout of thin_gemm_kernel)
+  const int col = c0 + wave * 16 + kq * 4;
+  if (col < a.hidden) {   // (hidden % 8 == 0: the four columns are inside together)
+    const int row0 = r0 + lr, row1 = row0 + 16;
+    if (row0 < a.k_rows)
+      *reinterpret_cast<uint2*>(a.dw1 + (static_cast<size_t>(row0) * a.dw1_ld + col) * 2u) =
+          make_uint2(tg_pack<F16>(acc0[0], acc0[1]), tg_pack<F16>(acc0[2], acc0[3]));
+    if (row1 < a.k_rows)
+      *reinterpret_cast<uint2*>(a.dw1 + (static_cast<size_t>(row1) * a.dw1_ld + col) * 2u) =
+          make_uint2(tg_pack<F16>(acc1[0], acc1[1]), tg_pack<F16>(acc1[2], acc1[3]));
+  }
+}
+
 // ---- the learner's forward pass on the thin GEMM's arithmetic, restricted to what the C51 loss and the backward read --------
 // hb_thin_gemm computes every element of [2B, 2H] (layer 1) and [2, 2B, Np] (layer 2). Nobody reads the target network on
 // obs_tm1 (rows [0, B): a quarter of layer 1, a quarter of layer 2), and of the online logits on obs_tm1 the loss reads only
@@ -984,3 +1086,48 @@ int hb_c51_backward(const float* dl_dev, const int32_t* act_dev, const void* hid
 }
 
 }  // extern "C"
+
+// hb_noisy_adam_multi (learner.hip) with a gradient-product entry in its table: the two-role launch above. `steps` are the
+// entries to step (role A; n_steps may be 0), `prod` the product entry (role B); eff_dtype is both the effective weights' type
+// and the product's operand type.
+int hb::adam::launch_tail(const hb_adam_tensor* steps, int n_steps, const hb_adam_tensor& prod, const float* step_dev,
+                          float step_offset, int eff_dtype, float lr, float beta1, float beta2, float eps, void* stream) {
+  const int dtype = prod.grad_dtype;
+  if (!prod.gdh || !prod.grad) return fail(HB_ERR_INVALID, "gradient product: null gdh / grad");
+  if (dtype != 1 && dtype != 2) return fail(HB_ERR_INVALID, "gradient product: grad_dtype must be 1 (bf16) or 2 (f16)");
+  if (eff_dtype != dtype) return fail(HB_ERR_INVALID, "gradient product: eff_dtype must equal the product's grad_dtype");
+  if (prod.g_batch < 1 || prod.g_batch > 256)
+    return fail(HB_ERR_INVALID, "gradient product: g_batch must be 1..256 (a workgroup keeps the tile's operand columns of the whole batch in LDS)");
+  if (prod.cols < 8 || prod.cols % 8 || prod.n < prod.cols || prod.n % prod.cols || prod.n / prod.cols >= (1LL << 24))
+    return fail(HB_ERR_INVALID, "gradient product: need cols a positive multiple of 8 and n a multiple of cols");
+  const int hidden = prod.cols, k_rows = static_cast<int>(prod.n / prod.cols);
+  const int ldx = prod.g_ldx, dh_ld = prod.g_ldh, dw1_ld = prod.grad_ld ? prod.grad_ld : prod.cols;
+  if (ldx < k_rows || ldx % 8 || dh_ld < hidden || dh_ld % 8 || dw1_ld < hidden || dw1_ld % 4)
+    return fail(HB_ERR_INVALID, "gradient product: bad leading dimensions (g_ldx >= n / cols, g_ldh, grad_ld >= cols; g_ldx % 8 == 0, g_ldh % 8 == 0, grad_ld % 4 == 0)");
+  if ((reinterpret_cast<uintptr_t>(prod.gx) & 15u) || (reinterpret_cast<uintptr_t>(prod.gdh) & 15u) || (reinterpret_cast<uintptr_t>(prod.grad) & 7u))
+    return fail(HB_ERR_ALIGN, "gradient product: gx / gdh must be 16-byte aligned, grad 8-byte aligned");
+  TailArgs a{};
+  int g_adam = 0, width = 4;
+  if (n_steps > 0) {
+    // (no 2-wide form here: that one exists to fit beside the policy kernel, this launch never runs there)
+    width = hb::adam::plan_multi(steps, n_steps, step_dev, step_offset, lr, beta1, beta2, eps, 4, a.adam, &g_adam);
+    if (width < 0) return width;
+  }
+  a.x = static_cast<const unsigned char*>(prod.gx);
+  a.dh = static_cast<const unsigned char*>(prod.gdh);
+  a.dw1 = static_cast<unsigned char*>(const_cast<void*>(prod.grad));
+  a.batch = prod.g_batch; a.k_rows = k_rows; a.hidden = hidden;
+  a.ldx = static_cast<unsigned>(ldx); a.dh_ld = static_cast<unsigned>(dh_ld); a.dw1_ld = static_cast<unsigned>(dw1_ld);
+  a.g_adam = g_adam;
+  a.col_tiles = (hidden + 63) / 64;
+  const long long tiles = static_cast<long long>((k_rows + 31) / 32) * a.col_tiles;
+  if (tiles + g_adam >= (1LL << 31)) return fail(HB_ERR_INVALID, "too many workgroups");
+  const dim3 grid(static_cast<unsigned>(tiles + g_adam)), block(256);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (dtype == 2 && width == 4) hipLaunchKernelGGL((learner_tail_l2_dw1_kernel<true, 4>), grid, block, 0, s, a);
+  else if (dtype == 2) hipLaunchKernelGGL((learner_tail_l2_dw1_kernel<true, 1>), grid, block, 0, s, a);
+  else if (width == 4) hipLaunchKernelGGL((learner_tail_l2_dw1_kernel<false, 4>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((learner_tail_l2_dw1_kernel<false, 1>), grid, block, 0, s, a);
+  HB_HIP(hipGetLastError());
+  return HB_OK;
+}

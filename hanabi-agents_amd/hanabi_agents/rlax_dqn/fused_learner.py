@@ -151,6 +151,13 @@ class FusedLearner:
         # actor's packer also writes the thin GEMMs' copies (one launch instead of two, `pack_thin`).
         self.adam_pack = None
         self._pack_tab = None
+        # The update's tail as an hb_noisy_adam_multi launch with a gradient-product entry + the first layer's optimizer step
+        # (DESIGN section 5c "Learner tail"): dW1 on the library's place, and the output layer's step, which does not read dW1, beside it in the same launch. Decided at
+        # the first update (it needs `direct`); HB_TAIL_OVERLAP=0 keeps the library GEMM and the one four-tensor Adam launch, =1
+        # takes the new launches wherever the shapes allow.
+        self.tail_overlap = None
+        self._dw1_pending = False         # part1(defer_dw1=True) left dW1 to part2's launch
+        self._adam_tab_l2 = None
         self._gw2_out = torch.zeros(H, self.Np, dtype=self.cd, device=dev)
         self._gw1_out = torch.zeros(self.Kp, H, dtype=self.cd, device=dev)
         self.refresh_effective()
@@ -265,8 +272,27 @@ class FusedLearner:
         K.check(L.hb_per_sample_gather(*args, K.current_stream()))
         return self._idx, self._prob
 
-    def part1(self, indices, prios, gathered=False):
-        """Forward, loss, backward into flat_grad. indices int64 [B], prios float64 [B] (device)."""
+    def _tail_launch(self, adam):
+        """dW1 = X^T dH into _gw1_out (rows [0, obs_len): the padding rows keep their zeros) as a gradient-product entry of an
+        hb_noisy_adam_multi table (hb_adam_tensor.gx) and, with `adam`, the output layer's optimizer step (entries 2 and 3 of
+        the Adam table: W2, b2) in the same launch."""
+        if self._adam_tab_l2 is None:
+            tab = self._adam_table()
+            tail, prod = (K.HbAdamTensor * 3)(), (K.HbAdamTensor * 1)()
+            tail[0], tail[1], tail[2] = tab[0], tab[2], tab[3]
+            prod[0] = tab[0]
+            for d in (tail[0], prod[0]):   # W1's entry, with the product that fills its gradient buffer instead of the step
+                d.gx, d.gdh, d.g_batch, d.g_ldx, d.g_ldh = self.x.data_ptr(), self.dh.data_ptr(), self.B, self.Kp, self.H
+            self._adam_tab_l2 = (tail, prod)
+        p = self.agent.params
+        tab, n = (self._adam_tab_l2[0], 3) if adam else (self._adam_tab_l2[1], 1)
+        K.check(K.lib().hb_noisy_adam_multi(tab, n, K.dptr(self.step), 0.0, _DT[self.cd], float(p.learning_rate), 0.9, 0.999,
+                                            3.125e-5, K.current_stream()))
+
+    def part1(self, indices, prios, gathered=False, defer_dw1=False):
+        """Forward, loss, backward into flat_grad. indices int64 [B], prios float64 [B] (device). defer_dw1 (tail_overlap only):
+        the caller issues part2(opt=True) next, which computes dW1 beside the output layer's optimizer step; without it dW1 is
+        complete when part1 returns."""
         a, L = self.agent, K.lib()
         buf, B = a.experience, self.B
         if self.direct is None:
@@ -274,6 +300,12 @@ class FusedLearner:
         if self.adam_pack is None:
             self.adam_pack = bool(self.direct and self.thin and not self.lag and self.actor is not None and self.actor.fused
                                   and self.H == 512 and os.environ.get("HB_ADAM_PACK", "0") == "1")
+        if self.tail_overlap is None:
+            # Default where it measured faster (the synchronous 1-step agent, bf16 and fp16); with n-step returns and with
+            # actor_lag the step measured 1-2 % slower with it, so those keep the library GEMM unless HB_TAIL_OVERLAP=1 asks for it
+            want = os.environ.get("HB_TAIL_OVERLAP", "1" if a.params.n_step == 1 and not self.lag else "0")
+            self.tail_overlap = bool(self.direct and self.sparse_backward and not self.adam_pack and self.H % 8 == 0
+                                     and self.cd in (torch.bfloat16, torch.float16) and want != "0")
         if a.params.n_step > 1 and (buf.rows_per_insert is None or buf.rows_per_insert < 1):
             raise ValueError("n_step > 1 needs inserts of a constant row count (lock-step self-play)")
         s = K.current_stream()
@@ -338,7 +370,14 @@ class FusedLearner:
             K.check(L.hb_colsum(K.dptr(dl), _DT[self.cd], B, self.Np, K.dptr(self._gb2_pad), s))
             dh = torch.mm(dl, w2.t())                                      # masked by the ReLU in place, with its column sums
             K.check(L.hb_relu_bwd_colsum(K.dptr(dh), K.dptr(hb), hb.stride(0), _DT[self.cd], B, dh.shape[1], K.dptr(self.g_b1), s))
-        torch.mm(xb.t(), dh, out=self._gw1_out)                       # [Kp, H]; the padding rows are never read
+        if self.tail_overlap:
+            # (a dW1 still owed by an earlier part1(defer_dw1=True) would mean that _gw1_out was read stale or never stepped)
+            assert not self._dw1_pending, "part1(defer_dw1=True) must be followed by part2(opt=True) before the next part1"
+            self._dw1_pending = bool(defer_dw1)
+            if not defer_dw1:
+                self._tail_launch(adam=False)
+        else:
+            torch.mm(xb.t(), dh, out=self._gw1_out)                   # [Kp, H]; the padding rows are never read
         if not self.direct:  # pack the all-reduce bucket (fp32, unpadded)
             self.g_w2.copy_(self._gw2_out[:, :self.AK])
             self.g_b2.copy_(self._gb2_pad[:self.AK])
@@ -404,7 +443,12 @@ class FusedLearner:
             return
         # self.step was advanced by this update's loss kernel (part1): it already is this step's number
         if opt:
-            K.check(K.lib().hb_noisy_adam_multi(self._adam_table(), 4, K.dptr(self.step), 0.0, _DT[self.cd],
+            n_adam = 4
+            if self._dw1_pending:   # dW1 beside the output layer's step; only the first layer's step (entries 0, 1) reads dW1
+                self._tail_launch(adam=True)
+                self._dw1_pending = False
+                n_adam = 2
+            K.check(K.lib().hb_noisy_adam_multi(self._adam_table(), n_adam, K.dptr(self.step), 0.0, _DT[self.cd],
                                                 float(p.learning_rate), 0.9, 0.999, 3.125e-5, K.current_stream()))
         if not pack:
             return

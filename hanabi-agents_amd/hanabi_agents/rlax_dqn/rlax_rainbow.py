@@ -1017,7 +1017,7 @@ class DQNAgent:
                 indices, prios = self._sample_indices()
                 gathered = False
             self._note_local_is_max(prios)
-            td, _ = fl.part1(indices, prios, gathered=gathered)
+            td, _ = fl.part1(indices, prios, gathered=gathered, defer_dw1=True)   # (every caller issues _update_part2 next)
             return None, indices, td  # the loss value is formed on demand (last_loss) from td and the IS weights
         fv = self._fused_vanilla()
         if fv is not None:

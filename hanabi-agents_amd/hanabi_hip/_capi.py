@@ -41,7 +41,10 @@ class HbAdamTensor(C.Structure):
 
     _fields_ = [(n, C.c_void_p) for n in ("w", "w_mu", "w_sigma", "noise", "grad", "m_w", "v_w", "m_mu", "v_mu", "m_sigma",
                                           "v_sigma", "eff")] + [("n", C.c_int64), ("cols", C.c_int32), ("eff_ld", C.c_int32),
-                                                                                   ("grad_dtype", C.c_int32), ("grad_ld", C.c_int32)]
+                                                                                   ("grad_dtype", C.c_int32), ("grad_ld", C.c_int32),
+                                                                                   ("gx", C.c_void_p), ("gdh", C.c_void_p),
+                                                                                   ("g_batch", C.c_int32), ("g_ldx", C.c_int32),
+                                                                                   ("g_ldh", C.c_int32), ("g_reserved", C.c_int32)]
 
 
 class HbAdamPack(C.Structure):

@@ -594,9 +594,26 @@ typedef struct hb_adam_tensor {
   int64_t n;
   int32_t cols, eff_ld;
   int32_t grad_dtype, grad_ld; /* grad rows are grad_ld >= cols elements apart (0: contiguous)                       */
+  /* Optional (hb_noisy_adam_multi only; NULL / 0 otherwise): a GRADIENT PRODUCT. An entry with gx != NULL is not stepped by the
+   * launch; instead the launch computes this entry's gradient buffer for a later call that steps it:
+   *   grad[k, j] = sum_b gx[b, k] * gdh[b, j]   for k < n / cols, j < cols   (dW = X^T dH of a dense layer)
+   * gx [g_batch, g_ldx] and gdh [g_batch, g_ldh] in grad_dtype (1 bf16 or 2 f16), v_mfma_f32_16x16x32 with fp32 accumulation over
+   * the samples in ascending order, rounded once to grad_dtype; nothing outside those rows and columns of grad is written. Of
+   * such an entry only grad, grad_dtype, grad_ld, n, cols and these fields are read. g_batch 1 .. 256, cols % 8 == 0,
+   * g_ldx >= n / cols, g_ldx % 8 == 0 (whole 16-byte pieces of a row of gx are read, up to n / cols rounded up to 8),
+   * g_ldh >= cols, g_ldh % 8 == 0, grad row stride % 4 == 0; gx, gdh 16-byte and grad 8-byte aligned.                        */
+  const void *gx, *gdh;
+  int32_t g_batch, g_ldx, g_ldh, g_reserved;
 } hb_adam_tensor;
 /* This step's number (Adam's bias correction) is t = *step_dev + step_offset: 1 when step_dev counts completed steps
  * (hb_noisy_adam's convention), 0 when it already counts the running one (see hb_c51_loss_grad's counter).      */
+/* With ONE gradient-product entry among `tensors` (see hb_adam_tensor) the launch is learner_tail_l2_dw1_kernel
+ * (csrc/learner2.hip): its workgroups take one of two roles that share no data — the step of the other entries (same arithmetic
+ * per element and same element -> thread mapping as without the product; 4 elements per thread or, where a tensor does not allow
+ * 16-byte accesses, the scalar form) and one 32 x 64 tile of the product each (50 KB of LDS per workgroup: it runs in the
+ * update's whole-CU window, not beside the policy kernel). eff_dtype must then equal the product's grad_dtype. The caller passes
+ * the product together with the entries whose gradients are final (the output layer's W2 and b2 beside dW1) and steps the
+ * product's tensor with a second call. A table of the product entry alone computes just the product.                         */
 int hb_noisy_adam_multi(const hb_adam_tensor* tensors /* host array of device pointers */, int32_t count,
                         const float* step_dev, float step_offset, int32_t eff_dtype, float lr, float beta1, float beta2,
                         float eps, void* stream);
