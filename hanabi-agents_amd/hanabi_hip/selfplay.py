@@ -143,7 +143,12 @@ class SelfPlaySession:
     def _chain_for(self, seat, agent, train, raw):
         """The seat's command array, built when (and rebuilt if) the conditions of the replay hold; None -> ordinary path.
         Covered: packed env, one-kernel actor, synchronous agent with split update on its own learner stream, prioritized
-        replay, the whole update captured in ONE graph (single rank), one update per step."""
+        replay, one update per step, and an update with no host-side collective: captured in one graph, or in the early update's
+        two (set_two_graphs). Refused: an agent whose update goes through the gradient all-reduce (agent._collective(): more than
+        one rank, or force_collective) — the all-reduce, gloo's division by the world size and the global_is_max rescale are host
+        calls BETWEEN the update's two graphs (update_begin / update_finish), and the command array replays the graphs only. The one
+        exception is the all-reduce captured INSIDE graph 1 (agent._collective_in_graph(), no second graph): replaying the graph
+        replays the collective. An agent built with process_group=False is local and keeps the one-call step."""
         env = self.env
         if not (self.native_chain and train and self.learner_stream is not None and self.fuse_select and self.updates_per_step == 1
                 and seat in self.train_seats and self.t >= env.players and getattr(env, "packed", False)):
@@ -158,6 +163,8 @@ class SelfPlaySession:
                 or agent._dense_call is None or fl._sg_call is None or agent.gathered_ev is None or agent.weights_ev is None
                 or seat not in self._acted_ev or not self._ready(agent) or not fl.actor.takes_fused(env.net_obs)):
             return None
+        if agent._collective() and not (agent._graph2 is None and agent._collective_in_graph()):
+            return None   # (the all-reduce is a host call between the two graphs: update_begin / update_finish)
         if agent.train_step % p.target_update_period == 0:
             return None   # (this update is followed by a target sync: torch copies, ordinary path)
         buf = agent.experience
