@@ -517,9 +517,23 @@ __device__ __forceinline__ void encode_seat(const uint32_t* const& row, uint32_t
 // SHUF: every seat plays in its own colour frame. The move arrives in the mover's frame and is taken back
 // to the true colours before the rules run; the observation and legal mask are written in the frame of the seat to act; a game
 // dealt here draws its seats' permutations into a.perms. With SHUF false none of this is compiled in.
-template <class K, int G, bool SHUF = false>
+//
+// RULES (default false: the step above, unchanged): the rules phase alone, for a caller that keeps its games' rows in LDS across
+// turns (playout.hip). Phases 2a and the row's scalar words of 2c run on the rows ALREADY in `srow`; the copy in and out (phases
+// 1 and 3), the deck pool and every re-deal (2b, 2c), the encoder, the per-game outputs and the counters are compiled out, and of
+// `a` only n, mode (MODE_STEP) and flags are read. `res` then takes the lane's game: play (in: false = leave this game alone)
+// and the step's reward, terminal, score and illegal (out).
+struct StepResult {
+  bool play;
+  float reward;
+  int terminal, score;
+  bool illegal;
+};
+
+template <class K, int G, bool SHUF = false, bool RULES = false>
 __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, int lane, uint32_t* const srow, int uid_in,
-                                              long long wslot) {
+                                              long long wslot, StepResult* const res = nullptr) {
+  static_assert(!(RULES && SHUF), "the rules-only step has no colour-permuted form");
   constexpr int P = K::P, C = K::C, R = K::R, H = K::H;
   // (Round 3 measured an encoder on all 64 lanes — 64 / G lanes per game, the knowledge slots and the other hands dealt out
   //  over them and OR-ed into the bit row with ds_or_b32 — against this lane-per-game one: bit-identical and SLOWER, 10.5 vs
@@ -535,7 +549,7 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
   HB_STAMP(0);
 
   // the per-game inputs are requested first so their HBM latency hides under the state copy
-  const bool active = lane < nvalid && lane < G;
+  const bool active = lane < nvalid && lane < G && (!RULES || res->play);
   const long long gi = g0 + lane;
   bool mask_in = true;
   // This game's pre-shuffled next deck (64 B), used only on a re-deal. Round 3: fetched only by games that CAN end with this
@@ -544,7 +558,7 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
   // and is in flight while the rules run; a masked reset knows at once.
   uint4 nd[4] = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
   const uint4* const ndp = reinterpret_cast<const uint4*>(a.next_deck + gi * NEXT_DECK_BYTES);
-  if (active) {
+  if (!RULES && active) {
     if (mode == MODE_RESET && a.mask) mask_in = a.mask[gi] != 0;
     if (mode == MODE_RESET && mask_in) {
       nd[0] = ndp[0]; nd[1] = ndp[1]; nd[2] = ndp[2]; nd[3] = ndp[3];
@@ -556,7 +570,7 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
   }
 
   // ---- phase 1: state rows HBM -> LDS (coalesced 16-byte loads) ---------------------------
-  {
+  if constexpr (!RULES) {
     // every 16-byte piece of the wave's G rows is requested before the first one is written to LDS: ONE memory round trip
     // for the whole copy (a run-time-bounded loop waits for each piece in turn: G / 8 round trips)
     constexpr int Q = K::SW / 4;
@@ -614,7 +628,7 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
         int fsum = 0;
 #pragma unroll
         for (int c = 0; c < C; ++c) fsum += fw(c);
-        if (((w0 >> 10) & 7) <= 1 || (w0 & 63) == 0 || fsum >= C * R - 1) {
+        if (!RULES && (((w0 >> 10) & 7) <= 1 || (w0 & 63) == 0 || fsum >= C * R - 1)) {
           nd[0] = ndp[0]; nd[1] = ndp[1]; nd[2] = ndp[2]; nd[3] = ndp[3];
         }
       }
@@ -757,7 +771,7 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
   HB_STAMP(3);
   // ---- phase 2b: a finished / masked game takes its pre-shuffled next deck (lane-local copy into the LDS row);
   // the shuffle itself happens off this kernel's critical path in refill_kernel -----------------------------
-  if (active && need_reset) {
+  if (!RULES && active && need_reset) {
     const uint32_t* ndw = reinterpret_cast<const uint32_t*>(nd);
 #pragma unroll
     for (int i = 0; i < 13; ++i) row[K::W_DECK + i] = ndw[i];
@@ -769,7 +783,7 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
 
   // ---- phase 2c: deal fresh games, encode, publish fields -----------------------------------
   if (active) {
-    if (need_reset) {
+    if (!RULES && need_reset) {
       const uint8_t* deckb = reinterpret_cast<const uint8_t*>(row + K::W_DECK);
       w0 = static_cast<uint32_t>(K::D - P * H) | (static_cast<uint32_t>(K::INFO) << 6) | (static_cast<uint32_t>(K::LIFE) << 10) |
            (static_cast<uint32_t>(reset_start) << 13) | (static_cast<uint32_t>(P) << 16);
@@ -816,7 +830,7 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
       row[8] = static_cast<uint32_t>(disc); row[9] = static_cast<uint32_t>(disc >> 32);
     }
 
-    if (mode != MODE_RESET) {
+    if (!RULES && mode != MODE_RESET) {
       const int o = (w0 >> 13) & 7;
       uint32_t sg = 0;  // (SHUF) the observer's permutation: true colour c is seen as colour sig(c)
       if constexpr (SHUF) sg = perm_of(pm, o);
@@ -845,6 +859,13 @@ __device__ __forceinline__ void env_wave_step(const EnvArgs& a, long long g0, in
         if (a.score) a.score[gi] = static_cast<int8_t>(out_score);
       }
     }
+  }
+  if constexpr (RULES) {   // the lane's step, for the caller's own bookkeeping; the rows stay in LDS
+    res->reward = out_reward;
+    res->terminal = out_term;
+    res->score = out_score;
+    res->illegal = illegal;
+    return;
   }
   if (mode == MODE_STEP) {
     const unsigned long long bad = __ballot(illegal);

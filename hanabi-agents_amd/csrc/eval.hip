@@ -17,6 +17,7 @@
 
 #include "../../include/hanabi_hip.h"
 #include "common.hpp"
+#include "eval_tally.hpp"
 
 namespace {
 
@@ -36,9 +37,12 @@ struct TallyArgs {
 constexpr int kMaxCounters = 2 + 5 * 5 + 1 + 5 * 5;   // hb_eval_counters() at its largest (5 colours, 5 ranks, 5 players)
 constexpr int kMaxBlocks = 128;                        // at most this many global atomics per counter and turn
 
-__device__ __forceinline__ void wave_add(unsigned int* c, unsigned long long mask, int lane) {
-  if (mask && lane == 0) atomicAdd(c, static_cast<unsigned int>(__popcll(mask)));
-}
+// what hb_eval_tally does on the turn game g ends, and after a misplay that does not end it (HB_TALLY_GAME, eval_tally.hpp)
+#define TALLY_FINISH(SC, LEN, ST) \
+  a.final_score[g] = (SC);        \
+  a.length[g] = (LEN);            \
+  a.done[g] = (ST)
+#define TALLY_SET_DONE(ST) a.done[g] = (ST)
 
 // blockIdx.y selects a block of a0.n games and its own row of counters (hb_eval_tally: the one block). Grid-stride over the
 // block's games (the loop bound is uniform across the workgroup, so every lane takes part in every ballot). Each wave adds its
@@ -56,42 +60,12 @@ __global__ void __launch_bounds__(256) eval_tally_grouped_kernel(TallyArgs a0) {
   __syncthreads();
   for (long long base = static_cast<long long>(blockIdx.x) * 256; base < a.n; base += static_cast<long long>(gridDim.x) * 256) {
     const long long g = base + threadIdx.x;
-    int kind = -1, bin = 0;
-    bool ended = false, misplay = false, bomb = false;
+    HB_TALLY_VARS
     if (g < a.n) {
-      const uint8_t st = a.done[g];
-      if (!(st & 0x80u)) {   // a game counts only while it is live: finished games' env outputs are never read
-        const int u = a.actions[g];
-        if (u >= 0 && u < a.A) kind = u < a.H ? 0 : u < 2 * a.H ? 1 : u < 2 * a.H + (a.P - 1) * a.C ? 2 : 3;   // App. A.2 order
-        misplay = kind == 1 && a.reward[g] <= 0.f;   // a successful play always scores +1; a misplay 0, or -score at a bomb-out
-        const int lost = (st & 0x7f) + (misplay ? 1 : 0);
-        ended = a.terminal[g] != 0;
-        if (ended) {
-          const int sc = a.score[g];   // 0 after a bomb-out (hb_env_step)
-          bin = sc < 0 ? 0 : sc > B - 1 ? B - 1 : sc;
-          bomb = lost >= a.max_life;
-          a.final_score[g] = static_cast<int8_t>(sc);
-          a.length[g] = static_cast<int16_t>(a.turn + 1);
-          a.done[g] = static_cast<uint8_t>(0x80 | lost);
-        } else if (misplay) {
-          a.done[g] = static_cast<uint8_t>(lost);
-        }
-      }
+      HB_TALLY_GAME(a.A, a.H, a.P, a.C, B, a.max_life, a.turn, a.done[g], a.actions[g], a.reward[g], a.terminal[g], a.score[g],
+                    TALLY_FINISH, TALLY_SET_DONE)
     }
-    unsigned long long m = __ballot(ended);
-    if (m) {
-      wave_add(lc, m, lane);   // (slot 0 counts the games that ended: subtracted from the live count below)
-      wave_add(lc + 1 + B, __ballot(bomb), lane);
-      while (m) {   // histogram: one ballot per score that occurs in this wave (wave-uniform loop)
-        const int b = __shfl(bin, __ffsll(static_cast<unsigned long long>(m)) - 1);
-        const unsigned long long mb = __ballot(ended && bin == b);
-        wave_add(lc + 1 + b, mb, lane);
-        m &= ~mb;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) wave_add(lc + 2 + B + 4 * a.seat + k, __ballot(kind == k), lane);
-    wave_add(lc + 2 + B + 4 * a.P + a.seat, __ballot(misplay), lane);
+    HB_TALLY_WAVE(lc, B, a.P, a.seat, lane)
   }
   __syncthreads();
   for (int i = threadIdx.x; i < nc; i += 256) {

@@ -25,6 +25,12 @@ the separate evaluation env of its external session). `Evaluator` does that with
   conditional action matrix of the Other-Play and SAD papers. With `color_shuffle=True` the combination is allowed, but every
   move is in its mover's own frame: `prev` is in the partner's frame and `uid` in mine, so reveal-colour rows and columns of
   shuffled seats are not in a common frame (hanabi_hip.symmetry maps uids between frames; that mapping is not applied here).
+* `playout=True` (default False: the loop above, launch for launch): a team of `RulebasedAgent`s only, with `responses` and
+  `color_shuffle` off, is played by ONE launch of hb_rule_playout (hanabi_hip.playout) on a scratch copy of the deals instead of
+  the loop; any other team or option takes the loop. `Evaluator.last_path` says which ran: "playout" or "loop". The result is the
+  loop's, from the same counters, with two documented differences: `EvalResult.turns` is the longest game's length (the loop
+  reports the first multiple of `check_every` at or after it), and recorded actions are -1 from a game's end on (the loop
+  records moves the env ignored). The host reads the counters once per run instead of once per `check_every` turns.
 """
 import ctypes as C
 import math
@@ -35,6 +41,7 @@ import torch
 
 from . import _capi as K
 from .env import HanabiEnv
+from . import playout as _playout
 
 
 def max_turns(cfg):
@@ -212,12 +219,16 @@ class Evaluator:
     never auto-reset and score without leniency). first_game_id: global id of game 0 (keys the deals and the agents' draws)."""
 
     def __init__(self, game="Hanabi-Full", players=2, n_games=4096, seed=1, first_game_id=0, device=None, record_actions=False,
-                 config=None, check_every=8, color_shuffle=False, responses=False):
+                 config=None, check_every=8, color_shuffle=False, responses=False, playout=False):
         n_games = int(n_games)
         if n_games < 1:
             raise ValueError(f"n_games must be >= 1, got {n_games}")
         self.color_shuffle = bool(color_shuffle)
         self.responses = bool(responses)
+        if not isinstance(playout, bool):
+            raise TypeError(f"playout is a switch (True or False), got {playout!r}")
+        self.playout = playout
+        self.last_path = None   # "playout" or "loop": the path the last run() took
         cfg = eval_config(game, players, config)
         self.cfg = cfg
         self.players = cfg.players
@@ -263,6 +274,10 @@ class Evaluator:
             if not hasattr(a, "eval_moves"):
                 raise TypeError(f"{type(a).__name__} has no eval_moves()")
         self._setup()
+        if self.playout and _playout.playout_supported(agents, responses=self.responses, color_shuffle=self.color_shuffle):
+            self.last_path = "playout"
+            return self._run_playout(agents)
+        self.last_path = "loop"
         env, L, cfg = self.env, K.lib(), self.cfg
         perms = None
         if self.color_shuffle:   # DQN seats shuffled, rule seats not; the import below draws the deals' permutations
@@ -315,3 +330,32 @@ class Evaluator:
                           actions=self.actions[:t].clone() if self.record_actions else None, turns=t, perms=perms,
                           responses=self.resp if self.responses else None,
                           kinds=uid_kinds(P, cfg.colors, cfg.hand_size, env.num_actions))
+
+    def _run_playout(self, agents):
+        """run() for a team of rule lists: one hb_rule_playout launch on a scratch copy of the deals (module docstring). The
+        same buffers, the same counters, the same errors; one host read."""
+        cfg, P, dev = self.cfg, self.players, self.env.device
+        if getattr(self, "_play_rows", None) is None:
+            self._play_rows = torch.empty_like(self.rows0)
+            self._play_tail = (torch.empty(1, dtype=torch.int64, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
+        with torch.cuda.device(dev):
+            self._play_rows.copy_(self.rows0)
+            self.done.zero_()
+            self.final_score.zero_()
+            self.length.zero_()
+            self.counters.zero_()
+            self.counters[0] = self.n
+            log = self.actions if self.record_actions else None
+            res = _playout._launch(cfg, self._play_rows, agents, self.seed, 0, None, self.max_turns, self.first_game_id, self.done,
+                                   self.final_score, self.length, self.counters, log, tail=self._play_tail)
+            c = torch.cat([self.counters, res.illegal, res.max_len.long()]).cpu()   # the one host read of the run
+        live, illegal, t = int(c[0]), int(c[-2]), int(c[-1])
+        if live != 0:
+            raise RuntimeError(f"{live} evaluation games still live after max_turns = {self.max_turns} turns")
+        if illegal:
+            raise RuntimeError(f"evaluation agents chose {illegal} illegal moves")
+        B = self.max_score + 1
+        return EvalResult(self.final_score, self.length, self.max_score, histogram=c[1:1 + B], bombouts=int(c[1 + B]),
+                          moves=c[2 + B:2 + B + 4 * P].view(P, 4), misplays=c[2 + B + 4 * P:2 + B + 5 * P],
+                          actions=self.actions[:t].clone() if self.record_actions else None, turns=t,
+                          kinds=uid_kinds(P, cfg.colors, cfg.hand_size, self.env.num_actions))

@@ -62,6 +62,7 @@ from . import _capi as K
 from .encode import encode_rows
 from .env import HanabiEnv
 from .evaluate import eval_config, max_turns
+from .playout import _launch as playout_launch, playout_supported
 
 
 def _rows(rows, words, device=None):
@@ -1095,16 +1096,30 @@ class SearchResult:
 
 
 def rollout(env, cfg, blueprint, seed, first_seat, forced, done, final_score, length, counters, act, scratch, check_every=8,
-            turn_limit=None, horizon=None):
+            turn_limit=None, horizon=None, playout=False, rows=None):
     """Play the games of `env` (auto-reset off, state imported) to the end: turn 0 plays `forced` for seat `first_seat`, turn
     t >= 1 the move of blueprint[(first_seat + t) % P].eval_moves with draw t + 1; hb_eval_tally after every step. `done`
     (bit 0x80: not played) and `counters` ([0] = games live) are set up by the caller. Returns the number of turns played.
     horizon = H (default None: to the end): at most H turns, the forced one included; returns (turns, games still live), and
-    games still live are then no error: seat (first_seat + turns) % P is to act in them, on the env's current observation."""
+    games still live are then no error: seat (first_seat + turns) % P is to act in them, on the env's current observation.
+    playout=True with `rows` (default False: the loop above, launch for launch): when the blueprint is rule lists only and there
+    is no horizon (`playout_supported`), the games are played by one hb_rule_playout launch on `rows` [n, state_words] in place
+    instead — the env is not touched, it need not hold the states —, with the env's game ids; done, final_score, length and
+    counters end as the loop leaves them, the slots not played keep their rows, and the turns returned are the longest game's
+    length. Illegal moves raise here (the loop's caller reads the env's count). Any other blueprint, or a horizon: the loop."""
+    limit = max_turns(cfg) if turn_limit is None else turn_limit
+    if playout and rows is not None and playout_supported(blueprint, horizon=horizon):
+        res = playout_launch(cfg, rows, blueprint, seed, first_seat, forced, limit, env.first_game_id, done, final_score, length,
+                             counters, None)
+        live, illegal, t = torch.cat([counters[:1], res.illegal, res.max_len.long()]).tolist()   # the one host read
+        if illegal:
+            raise RuntimeError(f"{illegal} illegal moves in the rollouts (a candidate that is illegal at its root, or the blueprint's)")
+        if live != 0:
+            raise RuntimeError(f"{live} rollout games still live after {limit} turns")
+        return t
     L, P, n = K.lib(), cfg.players, env.n
     cfg_ref = C.byref(cfg)
     bufs = tuple(K.dptr(t) for t in (env.reward, env.terminal, env.score, done, final_score, length, counters))
-    limit = max_turns(cfg) if turn_limit is None else turn_limit
     if horizon is not None:
         limit = min(limit, int(horizon))
     live, t = -1, 0
@@ -1194,13 +1209,22 @@ class RolloutSearch:
     `depth_used`. epsilon (default None: the exact-match filter): with a history, the candidates are weighed by the likelihood of
     an epsilon-greedy partner instead of filtered (`ConditionedDeterminizer`'s epsilon) and the result carries `ess`.
     score_belief (default False: nothing is computed): the replicas of every search are scored against the roots' real hands
-    right after the determinization (hb_belief_score) and the result carries `belief`; the search itself is unchanged."""
+    right after the determinization (hb_belief_score) and the result carries `belief`; the search itself is unchanged.
+    playout (default False: the rollouts run on the turn loop, launch for launch as before): a blueprint of `RulebasedAgent`s only,
+    searched without a horizon, is rolled out by ONE hb_rule_playout launch (hanabi_hip.playout) on the
+    laid-out rows, with the forced first moves and the preset `done` bytes; the rollout env is not touched. Every figure of the
+    result is the loop's bit for bit except `turns`, the longest rollout's length instead of the next multiple of `check_every`.
+    Any other blueprint, or a horizon, takes the loop; `last_path` ("playout" or "loop") says what the last search did."""
 
     def __init__(self, game="Hanabi-Full", players=2, replicas=32, seed=1, device=None, config=None, check_every=8, first_game_id=0,
-                 oversample=8, epsilon=None, score_belief=False, horizon=None, leaf=None):
+                 oversample=8, epsilon=None, score_belief=False, horizon=None, leaf=None, playout=False):
         self.cfg = eval_config(game, players, config)
         self.players = self.cfg.players
         self.set_horizon(horizon, leaf)
+        if not isinstance(playout, bool):
+            raise TypeError(f"playout is a switch (True or False), got {playout!r}")
+        self.playout = playout
+        self.last_path = None   # "playout" or "loop": how the last search's rollouts were played
         self.replicas = int(replicas)
         if self.replicas < 1:
             raise ValueError(f"replicas must be >= 1, got {replicas}")
@@ -1335,13 +1359,18 @@ class RolloutSearch:
             # enqueued ahead of the rollouts, read after them: games played, dead replicas of the running roots, running roots
             counts = torch.stack([b["counters"][0], (live.view(m, 1) & (weights == 0)).sum(), live.sum()])
             slots = (cand >= 0).to(torch.int8)
-            env.import_state(b["rows"])
-            illegal0 = env.illegal_count()
+            # a blueprint of rule lists, no horizon: one hb_rule_playout launch on b["rows"] instead of the env and the loop
+            fast = self.playout and playout_supported(blueprint, horizon=H)
+            self.last_path = "playout" if fast else "loop"
+            illegal0 = 0
+            if not fast:
+                env.import_state(b["rows"])
+                illegal0 = env.illegal_count()
             turns = rollout(env, self.cfg, blueprint, self.seed, cp, b["forced"], b["done"], b["final_score"], b["length"],
-                            b["counters"], b["act"], b["scratch"], self.check_every, horizon=H)
+                            b["counters"], b["act"], b["scratch"], self.check_every, horizon=H, playout=fast, rows=b["rows"])
             if H is not None:
                 turns, leaves = turns
-            illegal = env.illegal_count() - illegal0
+            illegal = 0 if fast else env.illegal_count() - illegal0
             if illegal:
                 raise RuntimeError(f"{illegal} illegal moves in the rollouts (a candidate that is illegal at its root, or the blueprint's)")
             if leaves:   # games cut short by the horizon: every game's value in quarter points, where the final scores were read
@@ -1544,9 +1573,13 @@ class SearchPlayer:
     TRACK_COUNTERS = ("tracked", "restarts", "carried_live")
 
     def __init__(self, blueprint, seat, replicas=32, threshold=0.0, seed=1, check_every=8, z=None, confirm_replicas=0,
-                 condition=False, oversample=8, depth=1, epsilon=None, score_belief=False, track=False, horizon=None, leaf=None):
+                 condition=False, oversample=8, depth=1, epsilon=None, score_belief=False, track=False, horizon=None, leaf=None,
+                 playout=False):
         self.blueprint = list(blueprint)
         self.seat = int(seat)
+        if not isinstance(playout, bool):
+            raise TypeError(f"playout is a switch (True or False), got {playout!r}")
+        self.playout = playout   # RolloutSearch's: rule-list blueprints without a horizon roll out in one launch per search
         if not 0 <= self.seat < len(self.blueprint):
             raise ValueError(f"seat {seat} out of range for {len(self.blueprint)} players")
         self.horizon, self.leaf = check_horizon(horizon), leaf
@@ -1719,7 +1752,8 @@ class SearchPlayer:
         if self._search is None or self._search.cfg.players != env.cfg.players:
             self._search = RolloutSearch(config=env.cfg, replicas=self.replicas, seed=self.seed, device=env.device,
                                          check_every=self.check_every, oversample=self.oversample, epsilon=self.epsilon,
-                                         score_belief=self.score_belief, horizon=self.horizon, leaf=self.leaf)
+                                         score_belief=self.score_belief, horizon=self.horizon, leaf=self.leaf,
+                                         playout=self.playout)
         rows = env.export_state()
         staged = self.z is not None or self.confirm_replicas > 0
         history = None
