@@ -40,12 +40,15 @@ __global__ void __launch_bounds__(128) rule_kernel(RuleArgs a) {
   HB_RULE_GAME(g, a.n_rules, a.rules)
 }
 
-// hb_rule_act_grouped: blockIdx.y = block b of a.n games, blockIdx.x * 128 + lane = its row. The block's rule set (and with it the
-// rule walked at each step) is uniform over the workgroup.
+// hb_rule_act_grouped / hb_rule_act_blocks: blockIdx.y = block b of a.n games, blockIdx.x * 128 + lane = its row r. The block's rule
+// set (and with it the rule walked at each step) is uniform over the workgroup. The Philox game id of the row is
+// a.first_gid + b * id_stride + r: stride 0 for blocks that replay the same deals (cross-play), stride a.n for the blocks of one
+// training env, whose row r of block b is the env's game b * a.n + r.
 struct RuleGroups {
   const int32_t* set_of_block;   // [n_blocks]
   const hb_rule* rules;          // [n_sets][HB_MAX_RULES]
   const int32_t* n_rules;        // [n_sets]
+  long long id_stride;           // (ahead of n_sets: the four 8-byte fields are then fetched by one kernel-argument load)
   int n_sets;
 };
 __global__ void __launch_bounds__(128) rule_grouped_kernel(RuleArgs a, RuleGroups grp) {
@@ -57,23 +60,8 @@ __global__ void __launch_bounds__(128) rule_grouped_kernel(RuleArgs a, RuleGroup
   const hb_rule* rules = grp.rules + static_cast<long long>(set) * HB_MAX_RULES;
   const int n_rules = min(max(grp.n_rules[set], 0), HB_MAX_RULES);
   const long long g = static_cast<long long>(b) * a.n + r;
-  HB_RULE_GAME(r, n_rules, rules)
+  HB_RULE_GAME(b * grp.id_stride + r, n_rules, rules)
 }
-
-// hb_rule_act_blocks: the grouped kernel's layout, but a training env's blocks hold distinct games: row r of block b is game
-// b * a.n + r of the env and takes its global game id a.first_gid + b * a.n + r.
-__global__ void __launch_bounds__(128) rule_blocks_kernel(RuleArgs a, RuleGroups grp) {
-  const int b = static_cast<int>(blockIdx.y);
-  const int set = grp.set_of_block[b];
-  if (set < 0 || set >= grp.n_sets) return;   // (-1: a block of other agents)
-  const long long r = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (r >= a.n) return;
-  const hb_rule* rules = grp.rules + static_cast<long long>(set) * HB_MAX_RULES;
-  const int n_rules = min(max(grp.n_rules[set], 0), HB_MAX_RULES);
-  const long long g = static_cast<long long>(b) * a.n + r;
-  HB_RULE_GAME(g, n_rules, rules)
-}
-
 
 }  // namespace
 
@@ -112,10 +100,10 @@ extern "C" int hb_rule_act(const hb_config* cfg, const uint32_t* state_rows_dev,
   return HB_OK;
 }
 
-extern "C" int hb_rule_act_grouped(const hb_config* cfg, const uint32_t* state_rows_dev, int64_t n_blocks, int64_t block_rows,
-                                   int64_t first_game_id, const int32_t* set_of_block_dev, const hb_rule* rules_dev,
-                                   const int32_t* n_rules_dev, int32_t n_sets, uint64_t seed, uint64_t draw, int32_t* actions_dev,
-                                   int32_t* fired_dev, void* stream) {
+static int rule_act_grouped(const hb_config* cfg, const uint32_t* state_rows_dev, int64_t n_blocks, int64_t block_rows,
+                            int64_t first_game_id, int64_t id_stride, const int32_t* set_of_block_dev, const hb_rule* rules_dev,
+                            const int32_t* n_rules_dev, int32_t n_sets, uint64_t seed, uint64_t draw, int32_t* actions_dev,
+                            int32_t* fired_dev, void* stream) {
   if (!cfg || !state_rows_dev || !actions_dev || !set_of_block_dev || !rules_dev || !n_rules_dev) return hb::fail(HB_ERR_INVALID, "null argument");
   if (int rc = hb_config_validate(cfg)) return rc;
   if (n_sets < 1) return hb::fail(HB_ERR_INVALID, "n_sets must be >= 1");
@@ -123,27 +111,25 @@ extern "C" int hb_rule_act_grouped(const hb_config* cfg, const uint32_t* state_r
   if (block_rows < 0 || block_rows > (int64_t{1} << 31) * 128 - 1) return hb::fail(HB_ERR_INVALID, "block_rows out of range");
   if (n_blocks == 0 || block_rows == 0) return HB_OK;
   const RuleArgs a = rule_args(cfg, state_rows_dev, block_rows, first_game_id, seed, draw, actions_dev, fired_dev);
-  const RuleGroups grp{set_of_block_dev, rules_dev, n_rules_dev, n_sets};
+  const RuleGroups grp{set_of_block_dev, rules_dev, n_rules_dev, id_stride, n_sets};
   const dim3 grid(static_cast<unsigned>((block_rows + 127) / 128), static_cast<unsigned>(n_blocks));
   hipLaunchKernelGGL(rule_grouped_kernel, grid, dim3(128), 0, static_cast<hipStream_t>(stream), a, grp);
   HB_HIP(hipGetLastError());
   return HB_OK;
 }
 
+extern "C" int hb_rule_act_grouped(const hb_config* cfg, const uint32_t* state_rows_dev, int64_t n_blocks, int64_t block_rows,
+                                   int64_t first_game_id, const int32_t* set_of_block_dev, const hb_rule* rules_dev,
+                                   const int32_t* n_rules_dev, int32_t n_sets, uint64_t seed, uint64_t draw, int32_t* actions_dev,
+                                   int32_t* fired_dev, void* stream) {
+  return rule_act_grouped(cfg, state_rows_dev, n_blocks, block_rows, first_game_id, 0, set_of_block_dev, rules_dev, n_rules_dev, n_sets,
+                          seed, draw, actions_dev, fired_dev, stream);
+}
+
 extern "C" int hb_rule_act_blocks(const hb_config* cfg, const uint32_t* state_rows_dev, int64_t n_blocks, int64_t block_rows,
                                   int64_t first_game_id, const int32_t* set_of_block_dev, const hb_rule* rules_dev,
                                   const int32_t* n_rules_dev, int32_t n_sets, uint64_t seed, uint64_t draw, int32_t* actions_dev,
                                   int32_t* fired_dev, void* stream) {
-  if (!cfg || !state_rows_dev || !actions_dev || !set_of_block_dev || !rules_dev || !n_rules_dev) return hb::fail(HB_ERR_INVALID, "null argument");
-  if (int rc = hb_config_validate(cfg)) return rc;
-  if (n_sets < 1) return hb::fail(HB_ERR_INVALID, "n_sets must be >= 1");
-  if (n_blocks < 0 || n_blocks > 65535) return hb::fail(HB_ERR_INVALID, "n_blocks must be 0..65535 (one grid row per block)");
-  if (block_rows < 0 || block_rows > (int64_t{1} << 31) * 128 - 1) return hb::fail(HB_ERR_INVALID, "block_rows out of range");
-  if (n_blocks == 0 || block_rows == 0) return HB_OK;
-  const RuleArgs a = rule_args(cfg, state_rows_dev, block_rows, first_game_id, seed, draw, actions_dev, fired_dev);
-  const RuleGroups grp{set_of_block_dev, rules_dev, n_rules_dev, n_sets};
-  const dim3 grid(static_cast<unsigned>((block_rows + 127) / 128), static_cast<unsigned>(n_blocks));
-  hipLaunchKernelGGL(rule_blocks_kernel, grid, dim3(128), 0, static_cast<hipStream_t>(stream), a, grp);
-  HB_HIP(hipGetLastError());
-  return HB_OK;
+  return rule_act_grouped(cfg, state_rows_dev, n_blocks, block_rows, first_game_id, block_rows, set_of_block_dev, rules_dev, n_rules_dev,
+                          n_sets, seed, draw, actions_dev, fired_dev, stream);
 }

@@ -13,10 +13,11 @@ teams on the same deals and returns one `EvalResult` per team, each equal to wha
   are the standalone Evaluator's deals). Padding rows are real games, acted on and stepped, but their `done` byte starts at
   "finished", so they are never counted. Teams go into chunks of at most `max_rows` games; a chunk's env and buffers are built
   once and kept.
-* One turn (seat t mod P) issues, on the current stream: one hb_actor_fused_act_grouped per operand dtype for the blocks whose
-  seat agent takes the one-kernel actor (each 128-row tile reads its own network's descriptor), one hb_rule_act_grouped for the
-  rule-agent blocks, one HanabiEnv.step over the whole chunk and one hb_eval_tally_grouped (a row of counters per block). The
-  descriptor and rule-set tables are uploaded once per chunk and run, not per turn. Agents off the one-kernel actor take their
+* One turn (seat t mod P) issues, on the current stream: the launches of the seat's move table (hanabi_hip.grouped) — one
+  hb_actor_fused_act_grouped per (dtype, hidden, n_atoms) group for the blocks whose seat agent takes the one-kernel actor (each
+  128-row tile reads its own network's descriptor), one hb_rule_act_grouped for the rule-agent blocks — then one HanabiEnv.step
+  over the whole chunk and one hb_eval_tally_grouped (a row of counters per block). The descriptor tables are uploaded once per
+  chunk and run, the rule-set table once per run, not per turn. Agents off the one-kernel actor take their
   own eval_moves on row slices of their block (the generic path): rows [r0, r0 + n) in one call — exactly the standalone
   shape, which the library GEMMs' kernel choice and the torch path's generator depend on — then the padding rows.
 * `color_shuffle=True`: as Evaluator's, per block: the seats of a block held by DQN-style agents play in colour-permuted frames,
@@ -39,8 +40,7 @@ import torch
 from . import _capi as K
 from .env import HanabiEnv
 from .evaluate import EvalResult, eval_config, max_turns, normalize_rows, shuffle_mask, uid_kinds
-
-TILE = 128   # rows per workgroup of the one-kernel actor, and per hb_fused_tile
+from .grouped import TILE, MoveTable, RuleSets, classify
 
 
 def default_teams(k, players):
@@ -237,8 +237,6 @@ class CrossPlay:
     def run(self, pool, teams=None, grouped=True):
         """pool: list of agents (DQNAgent / RulebasedAgent); teams: P-tuples of pool indices (default: default_teams).
         grouped=False: every agent takes its own eval_moves per block (the generic path). Returns a CrossPlayResult."""
-        from hanabi_agents.rule_based import RulebasedAgent
-
         pool = list(pool)
         k = len(pool)
         default = teams is None
@@ -246,80 +244,53 @@ class CrossPlay:
         for a in pool:
             if not hasattr(a, "eval_moves"):
                 raise TypeError(f"{type(a).__name__} has no eval_moves()")
-        # the agents' per-run operands: a tile descriptor for one-kernel DQN agents, a rule set for rule agents
-        kinds = {}
-        rule_sets = []
-        for a in pool:
-            if id(a) in kinds:
-                continue
-            if isinstance(a, RulebasedAgent):
-                kinds[id(a)] = ("rule", len(rule_sets)) if grouped else ("rule_generic", None)
-                if grouped:
-                    rule_sets.append(a)
-            elif grouped and a.requires_vectorized_observation() and hasattr(a, "eval_operands"):
-                ops = a.eval_operands()
-                kinds[id(a)] = ("tile", ops) if ops is not None else ("generic", None)
-            elif a.requires_vectorized_observation():
-                kinds[id(a)] = ("generic", None)
-            else:
-                raise TypeError(f"{type(a).__name__}: cross-play runs DQN-style agents (vectorised observations) and RulebasedAgent")
+        kinds, rule_sets = self.classify_pool(pool, grouped)
         results = [None] * len(teams)
         self.last_turns = []
-        rules_dev = n_rules_dev = None
         for first, nb in self.chunks(len(teams)):
             ch = self._chunk(nb)
-            if rule_sets and rules_dev is None:
-                tab = (K.HbRule * (K.MAX_RULES * len(rule_sets)))()
-                for s, a in enumerate(rule_sets):
-                    for q in range(len(a.rules)):
-                        tab[s * K.MAX_RULES + q] = a._tab[q]
-                dev = ch.env.device
-                rules_dev = torch.frombuffer(bytearray(tab), dtype=torch.uint8).to(dev)
-                n_rules_dev = torch.tensor([len(a.rules) for a in rule_sets], dtype=torch.int32, device=dev)
+            if len(rule_sets) and rule_sets.table_dev is None:   # once per run, shared by every seat's table
+                rule_sets.upload(ch.env.device)
             chunk_teams = teams[first:first + nb]
-            plans = [self._seat_plan(ch, [pool[t[s]] for t in chunk_teams], kinds) for s in range(self.players)]
+            tables = [self.seat_table(ch, [pool[t[s]] for t in chunk_teams], kinds, rule_sets) for s in range(self.players)]
             masks = [shuffle_mask([pool[i] for i in t]) for t in chunk_teams] if self.color_shuffle else None
-            out = self._play(ch, plans, rules_dev, n_rules_dev, len(rule_sets), masks)
+            out = self._play(ch, tables, masks)
             for b, res in enumerate(out):
                 results[first + b] = res
         return CrossPlayResult(teams, results, k, self.players, default)
 
-    def _seat_plan(self, ch, agents, kinds):
-        """One seat of one chunk: the tile tables per operand dtype (device), the rule set of every block (device, or None when
-        no block of this seat is a rule agent) and the (block, agent, kind) list of the generic path."""
-        n_tiles, per_block = ch.rows // TILE, self.n_pad // TILE
-        env = ch.env
-        tiles = {}
-        sets = [-1] * ch.nb
-        generic = []
+    def classify_pool(self, pool, grouped=True):
+        """(kinds, rule_sets) of one run: id(agent) -> grouped.classify's (kind, argument), and the RuleSets (not uploaded) of the
+        pool's rule agents in pool order. grouped=False: nothing takes the grouped kernels; a rule agent is ("rule_generic",
+        agent), hb_rule_act per block."""
+        L, cfg_ref = K.lib(), C.byref(self.cfg)
+        obs_len, n_actions = L.hb_obs_len(cfg_ref), L.hb_num_actions(cfg_ref)
+        kinds = {}
+        for a in pool:
+            if id(a) not in kinds:
+                kind, arg = classify(a, obs_len, n_actions, fused=grouped)
+                kinds[id(a)] = ("rule_generic" if kind == "rule" and not grouped else kind, arg)
+        return kinds, RuleSets(arg for kind, arg in kinds.values() if kind == "rule")
+
+    def seat_table(self, ch, agents, kinds, rule_sets):
+        """One seat of one chunk: the MoveTable (uploaded) of the blocks' seat agents `agents`; its generic entries are (block,
+        agent, kind). A block's tile i keys its rows from the agent's own first_game_id + 128 * i; the rule launch replays the
+        evaluator's game ids in every block (id_stride 0)."""
+        per_block = self.n_pad // TILE
+        tab = MoveTable(ch.rows // TILE, (ch.nb, self.n_pad, 0), rule_sets)
+        held = []
         for b, a in enumerate(agents):
             kind, arg = kinds[id(a)]
             if kind == "tile":
-                if arg["obs_len"] != env.obs_len or arg["n_actions"] != env.num_actions:
-                    raise ValueError(f"agent of obs_len {arg['obs_len']} / {arg['n_actions']} actions in a game of "
-                                     f"{env.obs_len} / {env.num_actions}")
-                tab = tiles.get(arg["dtype"])
-                if tab is None:
-                    tab = tiles[arg["dtype"]] = (K.HbFusedTile * n_tiles)()
-                for i in range(per_block):
-                    d = tab[b * per_block + i]
-                    d.w1f, d.b1f, d.w2f, d.b2f, d.support = arg["w1f"], arg["b1f"], arg["w2f"], arg["b2f"], arg["support"]
-                    d.first_game_id = arg["first_game_id"] + TILE * i
-                    d.active = 1
+                held.append((b * per_block, per_block, arg, arg["first_game_id"]))
             elif kind == "rule":
-                sets[b] = arg
+                tab.walk(b, a)
             else:
-                generic.append((b, a, kind))
-        dev = env.device
-        tile_dev = [(dt, torch.frombuffer(bytearray(tab), dtype=torch.uint8).to(dev)) for dt, tab in sorted(tiles.items())]
-        hidden = {kinds[id(a)][1]["hidden"] for a in agents if kinds[id(a)][0] == "tile"}
-        atoms = {kinds[id(a)][1]["n_atoms"] for a in agents if kinds[id(a)][0] == "tile"}
-        set_dev = torch.tensor(sets, dtype=torch.int32, device=dev) if any(s >= 0 for s in sets) else None
-        keep = [kinds[id(a)][1]["support_t"] for a in agents if kinds[id(a)][0] == "tile"]   # (alive until the run ends)
-        return dict(tiles=tile_dev, hidden=hidden.pop() if hidden else 0, n_atoms=atoms.pop() if atoms else 0, sets=set_dev,
-                    generic=generic, keep=keep)
+                tab.generic.append((b, a, kind))
+        tab.set_tiles(held)
+        return tab.upload(ch.env.device)
 
-    def _play(self, ch, plans, rules_dev, n_rules_dev, n_sets, masks=None):
+    def _play(self, ch, tables, masks=None):
         env, L, cfg = ch.env, K.lib(), self.cfg
         perms = None
         if masks is not None:
@@ -340,11 +311,7 @@ class CrossPlay:
         ch.counters.copy_(ch.counters0)
         P, n, n_pad, nb, rows = self.players, self.n, self.n_pad, ch.nb, ch.rows
         cfg_ref = C.byref(cfg)
-        state = L.hb_env_state(env.h)
-        obs, legal, q = env.obs_bits, env.legal, ch.q
         tally_bufs = tuple(K.dptr(x) for x in (env.reward, env.terminal, env.score, ch.done, ch.final_score, ch.length, ch.counters))
-        rules_p = K.dptr(rules_dev)
-        n_rules_p = K.dptr(n_rules_dev)
         resp_bufs = None
         if self.responses:
             ch.prev.fill_(-1)
@@ -353,17 +320,9 @@ class CrossPlay:
         live, t = nb * n, 0
         while t < self.max_turns:
             seat = t % P
-            plan = plans[seat]
             act = ch.actions[t if self.record_actions else 0]
-            stream = K.current_stream()
-            for dt, tab in plan["tiles"]:
-                K.check(L.hb_actor_fused_act_grouped(K.dptr(tab), rows, K.dptr(obs), K.dptr(legal), env.obs_len, plan["hidden"],
-                                                     env.num_actions, plan["n_atoms"], K.dptr(q), 0.0, self.seed, t + 1, K.dptr(act),
-                                                     dt, stream))
-            if plan["sets"] is not None:
-                K.check(L.hb_rule_act_grouped(cfg_ref, state, nb, n_pad, self.first_game_id, K.dptr(plan["sets"]), rules_p, n_rules_p,
-                                              n_sets, self.seed, t + 1, K.dptr(act), None, stream))
-            for b, a, kind in plan["generic"]:
+            tables[seat].launch(env, self.seed, t + 1, self.first_game_id, act, ch.q)
+            for b, a, kind in tables[seat].generic:
                 self._generic_moves(ch, b, a, kind, t, act)
             env.step(act)
             if resp_bufs is not None:   # before the tally: `done` still says which games were finished before this turn
@@ -382,7 +341,6 @@ class CrossPlay:
         self.last_turns.append(t)
         c = ch.counters.cpu()
         fs, ln = ch.final_score.cpu(), ch.length.cpu()
-        B = self.max_score + 1
         resp = ch.resp.cpu().numpy() if self.responses else None
         kinds = uid_kinds(P, cfg.colors, cfg.hand_size, env.num_actions)
         out = []
@@ -391,12 +349,10 @@ class CrossPlay:
             lengths = ln[r0:r0 + n]
             # the turns the standalone Evaluator plays: it reads the live count every check_every turns
             tb = min(self.max_turns, math.ceil(int(lengths.max()) / self.check_every) * self.check_every)
-            cb = c[b]
-            out.append(EvalResult(fs[r0:r0 + n], lengths, self.max_score, histogram=cb[1:1 + B], bombouts=int(cb[1 + B]),
-                                  moves=cb[2 + B:2 + B + 4 * P].view(P, 4), misplays=cb[2 + B + 4 * P:2 + B + 5 * P],
-                                  actions=ch.actions[:tb, r0:r0 + n].clone() if self.record_actions else None, turns=tb,
-                                  perms=perms[r0:r0 + n] if perms is not None and masks[b] else None,
-                                  responses=resp[b] if resp is not None else None, kinds=kinds))
+            out.append(EvalResult.from_counters(fs[r0:r0 + n], lengths, self.max_score, c[b], P,
+                                                actions=ch.actions[:tb, r0:r0 + n].clone() if self.record_actions else None, turns=tb,
+                                                perms=perms[r0:r0 + n] if perms is not None and masks[b] else None,
+                                                responses=resp[b] if resp is not None else None, kinds=kinds))
         return out
 
     def _generic_moves(self, ch, b, agent, kind, t, act):

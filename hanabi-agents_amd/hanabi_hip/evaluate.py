@@ -153,6 +153,15 @@ class EvalResult:
             self.responses = r.astype(np.int64, copy=True)
         self.kinds = None if kinds is None else np.asarray(kinds, np.int64)
 
+    @classmethod
+    def from_counters(cls, final_score, length, max_score, counters_row, players, **rest):
+        """The result of a counter row of hb_eval_tally (layout: the header comment of hb_eval_counters / hb_eval_tally): [0] live
+        games, [1, 1 + B) the score histogram (B = max_score + 1), [1 + B] bomb-outs, then moves [P][4] and misplays [P]; a
+        longer row's tail is ignored. rest: EvalResult's other arguments."""
+        c, B, P = counters_row, int(max_score) + 1, int(players)
+        return cls(final_score, length, max_score, histogram=c[1:1 + B], bombouts=int(c[1 + B]),
+                   moves=c[2 + B:2 + B + 4 * P].view(P, 4), misplays=c[2 + B + 4 * P:2 + B + 5 * P], **rest)
+
     def response_matrix(self, seat=None, kinds=False):
         """P(my move | the move made just before mine) as float64 [A + 1, A] (seat=None: the seats' counts pooled, then
         normalised) — row 0 is the first move of a game; every row is divided by its sum and a row without counts is NaN.
@@ -323,13 +332,10 @@ class Evaluator:
         illegal = env.illegal_count() - illegal0
         if illegal:
             raise RuntimeError(f"evaluation agents chose {illegal} illegal moves")
-        c = self.counters.cpu()
-        B = self.max_score + 1
-        return EvalResult(self.final_score, self.length, self.max_score, histogram=c[1:1 + B], bombouts=int(c[1 + B]),
-                          moves=c[2 + B:2 + B + 4 * P].view(P, 4), misplays=c[2 + B + 4 * P:2 + B + 5 * P],
-                          actions=self.actions[:t].clone() if self.record_actions else None, turns=t, perms=perms,
-                          responses=self.resp if self.responses else None,
-                          kinds=uid_kinds(P, cfg.colors, cfg.hand_size, env.num_actions))
+        return EvalResult.from_counters(self.final_score, self.length, self.max_score, self.counters.cpu(), P,
+                                        actions=self.actions[:t].clone() if self.record_actions else None, turns=t, perms=perms,
+                                        responses=self.resp if self.responses else None,
+                                        kinds=uid_kinds(P, cfg.colors, cfg.hand_size, env.num_actions))
 
     def _run_playout(self, agents):
         """run() for a team of rule lists: one hb_rule_playout launch on a scratch copy of the deals (module docstring). The
@@ -354,8 +360,6 @@ class Evaluator:
             raise RuntimeError(f"{live} evaluation games still live after max_turns = {self.max_turns} turns")
         if illegal:
             raise RuntimeError(f"evaluation agents chose {illegal} illegal moves")
-        B = self.max_score + 1
-        return EvalResult(self.final_score, self.length, self.max_score, histogram=c[1:1 + B], bombouts=int(c[1 + B]),
-                          moves=c[2 + B:2 + B + 4 * P].view(P, 4), misplays=c[2 + B + 4 * P:2 + B + 5 * P],
-                          actions=self.actions[:t].clone() if self.record_actions else None, turns=t,
-                          kinds=uid_kinds(P, cfg.colors, cfg.hand_size, self.env.num_actions))
+        return EvalResult.from_counters(self.final_score, self.length, self.max_score, c, P,
+                                        actions=self.actions[:t].clone() if self.record_actions else None, turns=t,
+                                        kinds=uid_kinds(P, cfg.colors, cfg.hand_size, self.env.num_actions))

@@ -7,9 +7,10 @@
 * Layout. The env's n games are cut into 128-game tiles; member k owns one contiguous run of tiles, in member order, with tile
   counts from `weights` (default equal) rounded by largest remainder (`pool_layout`, a pure function of n and the weights). Every
   member plays every seat the pool holds in its rows: a P-player team is (trainee, member, ..., member).
-* One pool turn issues, on the current stream: one hb_actor_fused_act_grouped per (dtype, hidden, n_atoms) group of one-kernel
-  DQN members (other tiles inactive), one hb_rule_act_blocks for all rule members, and each other member's own eval_moves on its
-  row range (the generic path). The tables are built once and rebuilt only when a member's eval_operands() addresses change.
+* One pool turn issues, on the current stream: the launches of its move table (hanabi_hip.grouped) — one
+  hb_actor_fused_act_grouped per (dtype, hidden, n_atoms) group of one-kernel DQN members (other tiles inactive), one
+  hb_rule_act_blocks for all rule members — and each other member's own eval_moves on its row range (the generic path). The
+  table's tiles are filled once and refilled only when a member's eval_operands() addresses change.
 * Randomness: Philox seed = the pool's `seed`, draw = the pool's own call counter (1, 2, ...), row r keyed by its global game id
   env.first_game_id + r. No member's draw counter, histogram, noise, buffers or weights move: members are frozen.
 * Statistics: after every env step the session issues `tally` (hb_train_tally): one int64 counter row per member, read by
@@ -22,8 +23,8 @@ import torch
 
 from . import _capi as K
 from .evaluate import MOVE_KINDS
+from .grouped import TILE, MoveTable, RuleSets, classify
 
-TILE = 128
 MAX_MEMBERS = K.TRAIN_MAX_MEMBERS
 FORMAT = "hanabi-agents_amd/partner_pool/1"
 
@@ -178,71 +179,38 @@ class PartnerPool:
         self._scratch = [dict() for _ in self.members]
         K.check(L.hb_train_tally_init(C.byref(env.cfg), L.hb_env_state(env.h), env.n, K.dptr(self._lost), K.dptr(self._length),
                                       K.current_stream()))
-        self._build_rule_tables()
+        # the move table of the env's tiles: the rule members' blocks now, the DQN members' tiles at the first moves(); every
+        # tile is a block of the rule launch and row r takes its global game id (id_stride = block_rows)
+        from hanabi_agents.rule_based import RulebasedAgent
+
+        self._rule_members = [k for k, m in enumerate(self.members) if isinstance(m, RulebasedAgent)]
+        rule_sets = RuleSets(self.members[k] for k in self._rule_members)
+        if len(rule_sets):
+            rule_sets.upload(dev)
+        self._table = MoveTable(env.n // TILE, (env.n // TILE, TILE, TILE), rule_sets)
+        for k in self._rule_members:
+            first, count = tiles[k]
+            for b in range(first, first + count):
+                self._table.walk(b, self.members[k])
+        self._table.upload(dev)
         if self._restore is not None:
             sd, self._restore = self._restore, None
             self.load_checkpoint_state(sd)
 
-    def _build_rule_tables(self):
-        from hanabi_agents.rule_based import RulebasedAgent
-
-        rule = [k for k, m in enumerate(self.members) if isinstance(m, RulebasedAgent)]
-        self._rule_members = rule
-        if not rule:
-            self._rules = None
-            return
-        dev = self.env.device
-        tab = (K.HbRule * (K.MAX_RULES * len(rule)))()
-        sets = [-1] * (self.env.n // TILE)
-        for s, k in enumerate(rule):
-            m = self.members[k]
-            for q in range(len(m.rules)):
-                tab[s * K.MAX_RULES + q] = m._tab[q]
-            first, count = self.tiles[k]
-            sets[first:first + count] = [s] * count
-        self._rules = (torch.tensor(sets, dtype=torch.int32, device=dev), torch.frombuffer(bytearray(tab), dtype=torch.uint8).to(dev),
-                       torch.tensor([len(self.members[k].rules) for k in rule], dtype=torch.int32, device=dev), len(rule))
-
-    def _tile_tables(self, env):
-        """(groups, generic): the device descriptor tables of the one-kernel DQN members, one per (dtype, hidden, n_atoms), and the
-        member indices of the generic path. Rebuilt when a member's eval_operands() addresses change."""
-        from hanabi_agents.rule_based import RulebasedAgent
-
-        ops = []
-        for k, m in enumerate(self.members):
-            if isinstance(m, RulebasedAgent):
-                ops.append(None)
-                continue
-            o = m.eval_operands() if (env.packed and hasattr(m, "eval_operands")) else None
-            if o is not None and (o["obs_len"] != env.obs_len or o["n_actions"] != env.num_actions):
-                raise ValueError(f"member {k}: an agent of obs_len {o['obs_len']} / {o['n_actions']} actions in a game of "
-                                 f"{env.obs_len} / {env.num_actions}")
-            ops.append(o)
-        key = tuple(None if o is None else (o["w1f"], o["b1f"], o["w2f"], o["b2f"], o["support"], o["dtype"], o["hidden"], o["n_atoms"])
-                    for o in ops)
-        if key == self._ops_key:
-            return self._groups, self._generic
-        tabs = {}
-        n_tiles = env.n // TILE
-        for k, o in enumerate(ops):
-            if o is None:
-                continue
-            g = (o["dtype"], o["hidden"], o["n_atoms"])
-            tab = tabs.get(g)
-            if tab is None:
-                tab = tabs[g] = (K.HbFusedTile * n_tiles)()
-            first, count = self.tiles[k]
-            for t in range(first, first + count):
-                d = tab[t]
-                d.w1f, d.b1f, d.w2f, d.b2f, d.support = o["w1f"], o["b1f"], o["w2f"], o["b2f"], o["support"]
-                d.first_game_id = env.first_game_id + TILE * t
-                d.active = 1
-        dev = env.device
-        self._groups = [(g, torch.frombuffer(bytearray(tab), dtype=torch.uint8).to(dev)) for g, tab in sorted(tabs.items())]
-        self._keep = [o["support_t"] for o in ops if o is not None]   # (alive while the tables hold their addresses)
-        self._generic = [k for k, m in enumerate(self.members) if ops[k] is None and not isinstance(m, RulebasedAgent)]
-        self._ops_key = key
-        return self._groups, self._generic
+    def move_table(self, env):
+        """The move table (grouped.MoveTable, uploaded) with the one-kernel DQN members' tiles and the member indices of the generic path. The tiles are
+        refilled when a member's eval_operands() addresses change."""
+        kinds = [classify(m, env.obs_len, env.num_actions, fused=env.packed, prefix=f"member {k}: ") for k, m in enumerate(self.members)]
+        key = tuple((o["w1f"], o["b1f"], o["w2f"], o["b2f"], o["support"], o["dtype"], o["hidden"], o["n_atoms"]) if kind == "tile" else None
+                    for kind, o in kinds)
+        tab = self._table
+        if key != self._ops_key:
+            tab.set_tiles([(first, count, o, env.first_game_id + TILE * first)
+                           for (first, count), (kind, o) in zip(self.tiles, kinds) if kind == "tile"])
+            tab.generic = [k for k, (kind, _) in enumerate(kinds) if kind == "generic"]
+            tab.upload(env.device)
+            self._ops_key = key
+        return tab
 
     # ---- colour shuffle ---------------------------------------------------------------------------------------------------
     def check_color_shuffle(self, env):
@@ -286,19 +254,12 @@ class PartnerPool:
             raise ValueError("a partner pool acts on the env of the session it was bound to")
         self.check_color_shuffle(env)
         self._draws += 1
-        L, stream = K.lib(), K.current_stream()
-        act, n, draw = self._actions, env.n, self._draws
-        groups, generic = self._tile_tables(env)
-        for (dt, hidden, n_atoms), tab in groups:
-            if self._q is None:
-                self._q = torch.empty(n, env.num_actions, dtype=torch.float32, device=env.device)
-            K.check(L.hb_actor_fused_act_grouped(K.dptr(tab), n, K.dptr(env.obs_bits), K.dptr(env.legal), env.obs_len, hidden,
-                                                 env.num_actions, n_atoms, K.dptr(self._q), 0.0, self.seed, draw, K.dptr(act), dt, stream))
-        if self._rules is not None:
-            sets, rules, n_rules, n_sets = self._rules
-            K.check(L.hb_rule_act_blocks(C.byref(env.cfg), L.hb_env_state(env.h), n // TILE, TILE, env.first_game_id, K.dptr(sets),
-                                         K.dptr(rules), K.dptr(n_rules), n_sets, self.seed, draw, K.dptr(act), None, stream))
-        for k in generic:
+        act, draw = self._actions, self._draws
+        tab = self.move_table(env)
+        if tab.groups and self._q is None:
+            self._q = torch.empty(env.n, env.num_actions, dtype=torch.float32, device=env.device)
+        tab.launch(env, self.seed, draw, env.first_game_id, act, self._q)
+        for k in tab.generic:
             m = self.members[k]
             lo, hi = self.rows(k)
             fgid = m.first_game_id

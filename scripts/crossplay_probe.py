@@ -34,21 +34,13 @@ def make_pool(players):
 
 def split(cp, pool):
     """One instrumented grouped run (one chunk): events around each turn's phases, summed over the turns; us per turn."""
-    from hanabi_agents.rule_based import RulebasedAgent as RA
-
     teams = hanabi_hip.crossplay.default_teams(len(pool), cp.players)
     (first, nb), = cp.chunks(len(teams))
     ch = cp._chunk(nb)
-    rule_sets = [a for a in pool if isinstance(a, RA)]
-    kinds = {id(a): ("rule", rule_sets.index(a)) if isinstance(a, RA) else ("tile", a.eval_operands()) for a in pool}
-    tab = (K.HbRule * (K.MAX_RULES * len(rule_sets)))()
-    for s, a in enumerate(rule_sets):
-        for q in range(len(a.rules)):
-            tab[s * K.MAX_RULES + q] = a._tab[q]
-    rules_dev = torch.frombuffer(bytearray(tab), dtype=torch.uint8).cuda()
-    n_rules_dev = torch.tensor([len(a.rules) for a in rule_sets], dtype=torch.int32, device="cuda")
-    plans = [cp._seat_plan(ch, [pool[t[s]] for t in teams], kinds) for s in range(cp.players)]
     env, L = ch.env, K.lib()
+    kinds, rule_sets = cp.classify_pool(pool)
+    rule_sets.upload(env.device)
+    tables = [cp.seat_table(ch, [pool[t[s]] for t in teams], kinds, rule_sets) for s in range(cp.players)]
     env.import_state(ch.rows0)
     env.observe()
     ch.done.copy_(ch.done0); ch.final_score.zero_(); ch.length.zero_(); ch.counters.copy_(ch.counters0)
@@ -56,19 +48,14 @@ def split(cp, pool):
     ms = dict(actor=0.0, rule=0.0, env=0.0, tally=0.0)
     live = []
     act = ch.actions[0]
-    state = L.hb_env_state(env.h)
     for t in range(cp.max_turns):
-        plan = plans[t % cp.players]
+        tab = tables[t % cp.players]
         e = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
         st = K.current_stream()
         e[0].record()
-        for dt, tb in plan["tiles"]:
-            K.check(L.hb_actor_fused_act_grouped(K.dptr(tb), ch.rows, K.dptr(env.obs_bits), K.dptr(env.legal), env.obs_len, plan["hidden"],
-                                                 env.num_actions, plan["n_atoms"], K.dptr(ch.q), 0.0, cp.seed, t + 1, K.dptr(act), dt, st))
+        tab.launch_tiles(env, cp.seed, t + 1, act, ch.q)
         e[1].record()
-        if plan["sets"] is not None:
-            K.check(L.hb_rule_act_grouped(C.byref(cp.cfg), state, nb, cp.n_pad, cp.first_game_id, K.dptr(plan["sets"]), K.dptr(rules_dev),
-                                          K.dptr(n_rules_dev), len(rule_sets), cp.seed, t + 1, K.dptr(act), None, st))
+        tab.launch_rules(env, cp.seed, t + 1, cp.first_game_id, act)
         e[2].record()
         env.step(act)
         e[3].record()

@@ -46,18 +46,13 @@ def timed(sess, steps):
 def launch_split(sess, pool, reps=200):
     """us per launch of the pool turn's parts and of the tally, on the session's env as it stands."""
     env, L = sess.env, K.lib()
-    groups, _ = pool._tile_tables(env)
-    sets, rules, n_rules, n_sets = pool._rules
-    act = pool._actions
-    state = L.hb_env_state(env.h)
+    tab = pool.move_table(env)
+    act = torch.zeros(env.n, dtype=torch.int32, device="cuda")
     q = torch.empty(env.n, env.num_actions, dtype=torch.float32, device="cuda")
     st = K.current_stream()
     parts = {
-        "grouped_actor": lambda: [K.check(L.hb_actor_fused_act_grouped(K.dptr(tab), env.n, K.dptr(env.obs_bits), K.dptr(env.legal),
-                                                                       env.obs_len, h, env.num_actions, a, K.dptr(q), 0.0, 1, 9,
-                                                                       K.dptr(act), dt, st)) for (dt, h, a), tab in groups],
-        "rule_blocks": lambda: K.check(L.hb_rule_act_blocks(C.byref(env.cfg), state, env.n // 128, 128, env.first_game_id, K.dptr(sets),
-                                                            K.dptr(rules), K.dptr(n_rules), n_sets, 1, 9, K.dptr(act), None, st)),
+        "grouped_actor": lambda: tab.launch_tiles(env, 1, 9, act, q),
+        "rule_blocks": lambda: tab.launch_rules(env, 1, 9, env.first_game_id, act),
     }
     out = {}
     for name, fn in parts.items():

@@ -22,7 +22,7 @@ ENV_WAVES = 4        # env_kernel / env_kernel_shuf (csrc/env_kernel.hpp): 256 t
 FUSED_ROWS = 128     # actor_fused_kernel, actor_fused_grouped_kernel, actor_env_fused_kernel (csrc/actor_fused.hip): FM
 GEMM_ROWS = 256      # actor_gemm_kernel (csrc/actor.hip): BM
 SELECT_ROWS = 128    # policy_select_kernel (csrc/actor.hip): SEL_T
-RULE_ROWS = 128      # rule_kernel / rule_grouped_kernel / rule_blocks_kernel (csrc/rule_agent.hip): one lane per game, 128 threads
+RULE_ROWS = 128      # rule_kernel / rule_grouped_kernel (csrc/rule_agent.hip): one lane per game, 128 threads
 LANE_ROWS = 256      # one lane per row in 256-thread workgroups: random_legal_kernel, get_kernel, the tallies, colour perms,
                      # train_tally_init_kernel, belief_history_step_kernel; and the 16-byte chunks of the grid-stride copies
 WAVE_ROWS = 4        # one wavefront per row, four per workgroup: sample_kernel, per_sample_kernel, c51_kernel, every

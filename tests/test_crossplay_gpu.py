@@ -117,15 +117,17 @@ def test_actor_grouped_matches_single_network_launches():
     assert all(a._draws == 0 for a in nets)
 
 
-def test_rule_grouped_matches_single_block_launches():
-    """Four rule sets over six blocks of 200 games (two skipped): each block equals hb_rule_act on its rows with its rule set."""
+@pytest.mark.parametrize("br,fgid", [(200, 11), (130, 2**32 - 7)])
+def test_rule_grouped_matches_single_block_launches(br, fgid):
+    """Four rule sets over seven blocks of `br` games (three skipped: two of set -1, one of set n_sets): each block equals
+    hb_rule_act on its rows with its rule set. 130 rows: one full workgroup and a 2-lane tail, with game ids that cross 2^32."""
     import torch
 
     from hanabi_agents.rule_based import RulebasedAgent, predefined_rules as PR
     from hanabi_hip import _capi as K
 
     L = K.lib()
-    br, sets_of_block = 200, [0, -1, 1, 2, -1, 3]
+    sets_of_block = [0, -1, 1, 2, -1, 3, 4]
     nb = len(sets_of_block)
     env = _played_env(3, nb * br, 8, 9)
     agents = [RulebasedAgent(r) for r in (PR.piers_rules, PR.iggi_rules, PR.outer_rules, PR.flawed_rules)]
@@ -140,12 +142,12 @@ def test_rule_grouped_matches_single_block_launches():
     fired = torch.full((nb * br,), -9, dtype=torch.int32, device="cuda")
     state = L.hb_env_state(env.h)
     cfg = C.byref(env.cfg)
-    fgid, seed, draw = 11, 123, 4
+    seed, draw = 123, 4
     K.check(L.hb_rule_act_grouped(cfg, state, nb, br, fgid, sob.data_ptr(), rules_dev.data_ptr(), n_rules.data_ptr(), 4, seed, draw,
                                   acts.data_ptr(), fired.data_ptr(), K.current_stream()))
     for b, s in enumerate(sets_of_block):
         rows = slice(b * br, b * br + br)
-        if s < 0:
+        if s < 0 or s >= 4:
             assert (acts[rows] == -7).all() and (fired[rows] == -9).all(), b
             continue
         a = agents[s]

@@ -76,20 +76,23 @@ def _assert_same_result(got, want, what=""):
 
 # ---- kernel level ------------------------------------------------------------------------------------------------------------
 
-def test_rule_blocks_match_per_block_launches():
-    """Five blocks of 128 games (one skipped) over the four rule lists: each block equals hb_rule_act on its rows with the state
-    pointer and game id offset to the block; the skipped block keeps the sentinel."""
+@pytest.mark.parametrize("br,fgid", [(128, None), (130, 2**32 - 300)])
+def test_rule_blocks_match_per_block_launches(br, fgid):
+    """Six blocks of `br` games (two skipped: set -1 and set n_sets) over the four rule lists: each block equals hb_rule_act on
+    its rows with the state pointer and game id offset to the block; the skipped blocks keep the sentinel. fgid None: the env's
+    own first game id; 2^32 - 300 with 130-row blocks: first_game_id + b * block_rows + r crosses 2^32 inside the third block."""
     import torch
 
     import hanabi_hip
     from hanabi_hip import _capi as K
 
     L = hanabi_hip.lib()
-    env = _env(2, 5 * 128, seed=3, first_game_id=1000)
+    env = _env(2, 6 * br, seed=3, first_game_id=1000)
+    fgid = env.first_game_id if fgid is None else fgid
     for t in range(23):
         env.step(env.random_legal_actions(seed=9, draw=t))
     agents = [_rule(x) for x in ("piers", "iggi", "outer", "flawed")]
-    sets = [0, 1, -1, 2, 3]
+    sets = [0, 1, -1, 2, 3, 4]
     tab = (K.HbRule * (K.MAX_RULES * 4))()
     for s, a in enumerate(agents):
         for q in range(len(a.rules)):
@@ -101,18 +104,18 @@ def test_rule_blocks_match_per_block_launches():
     fired = torch.full((env.n,), -7, dtype=torch.int32, device="cuda")
     state = L.hb_env_state(env.h)
     seed, draw = 77, 5
-    K.check(L.hb_rule_act_blocks(C.byref(env.cfg), state, 5, 128, env.first_game_id, K.dptr(sob), K.dptr(rules), K.dptr(n_rules), 4,
+    K.check(L.hb_rule_act_blocks(C.byref(env.cfg), state, 6, br, fgid, K.dptr(sob), K.dptr(rules), K.dptr(n_rules), 4,
                                  seed, draw, K.dptr(acts), K.dptr(fired), K.current_stream()))
     sw = env.state_words
     for b, s in enumerate(sets):
-        lo, hi = 128 * b, 128 * (b + 1)
-        if s < 0:
+        lo, hi = br * b, br * (b + 1)
+        if s < 0 or s >= 4:
             assert (acts[lo:hi] == -7).all() and (fired[lo:hi] == -7).all()
             continue
-        wa = torch.empty(128, dtype=torch.int32, device="cuda")
-        wf = torch.empty(128, dtype=torch.int32, device="cuda")
+        wa = torch.empty(br, dtype=torch.int32, device="cuda")
+        wf = torch.empty(br, dtype=torch.int32, device="cuda")
         a = agents[s]
-        K.check(L.hb_rule_act(C.byref(env.cfg), C.c_void_p(state + 4 * sw * lo), 128, env.first_game_id + lo, a._tab, len(a.rules), seed,
+        K.check(L.hb_rule_act(C.byref(env.cfg), C.c_void_p(state + 4 * sw * lo), br, fgid + lo, a._tab, len(a.rules), seed,
                               draw, K.dptr(wa), K.dptr(wf), K.current_stream()))
         assert torch.equal(acts[lo:hi], wa), b
         assert torch.equal(fired[lo:hi], wf), b
