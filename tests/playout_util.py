@@ -85,6 +85,7 @@ def oracle_playout(game, players, team_rules, seed, n, max_turns=None, first_mov
 
 
 @functools.lru_cache(maxsize=None)
-def expected(game, players, n, team, seed=DEAL_SEED, max_turns=None):
+def expected(game, players, n, team, seed=DEAL_SEED, max_turns=None, first_game_id=0):
     """oracle_playout of a named team (teams()), computed once per case and shared; treat the arrays as read-only."""
-    return oracle_playout(game, players, [rules_of(r) for r in teams()[team](players)], seed, n, max_turns=max_turns)
+    return oracle_playout(game, players, [rules_of(r) for r in teams()[team](players)], seed, n, max_turns=max_turns,
+                          first_game_id=first_game_id)

@@ -13,6 +13,9 @@ pytestmark = pytest.mark.gpu
 SEED = U.DEAL_SEED
 CASES = [("Hanabi-Very-Small", 2, 64), ("Hanabi-Small", 2, 193), ("Hanabi-Small", 4, 65), ("Hanabi-Full", 2, 257),
          ("Hanabi-Full", 3, 129), ("Hanabi-Full", 5, 65), ("Hanabi-Full", 2, 1), ("Hanabi-Full", 2, 63)]
+# the other six instantiations of the kernel (with CASES: all twelve), each with a partial wavefront; all four teams
+NEW_CASES = [("Hanabi-Full", 4, 65), ("Hanabi-Small", 3, 129), ("Hanabi-Small", 5, 65), ("Hanabi-Very-Small", 3, 63),
+             ("Hanabi-Very-Small", 4, 65), ("Hanabi-Very-Small", 5, 193)]
 TEAMS = ["piers", "flawed", "mixed", "everything"]
 
 
@@ -32,14 +35,26 @@ def _np(t):
     return t.cpu().numpy()
 
 
+def test_the_cases_launch_every_instantiation():
+    import deep_play
+
+    assert {(g, p) for g, p, _ in CASES + NEW_CASES} == set(deep_play.VARIANTS) and len(deep_play.VARIANTS) == 12
+    assert all(n % 64 for _, _, n in NEW_CASES)
+
+
 @pytest.mark.parametrize("team", TEAMS)
-@pytest.mark.parametrize("game,players,n", CASES)
+@pytest.mark.parametrize("game,players,n", CASES + NEW_CASES)
 def test_kernel_matches_the_cpu_expectation(game, players, n, team):
     import hanabi_hip
 
     e = U.expected(game, players, n, team)
     cfg = hanabi_hip.make_config(game, players)
     res = hanabi_hip.rule_playout(cfg, _dev_rows(e["rows0"]), _agents(team, players), SEED, log=True)
+    _assert_matches(res, e)
+
+
+def _assert_matches(res, e):
+    """Every output of a logged rule_playout against oracle_playout's."""
     assert np.array_equal(_np(res.rows).view(np.uint32), e["rows"])
     assert np.array_equal(_np(res.done), e["done"])
     assert np.array_equal(_np(res.final_score), e["final_score"])
@@ -53,6 +68,56 @@ def test_kernel_matches_the_cpu_expectation(game, players, n, team):
     assert int(res.illegal) == 0 == e["illegal"]
     assert int(res.max_len) == e["max_len"]
     assert int(res.counters[0]) == 0
+
+
+@pytest.mark.parametrize("team", TEAMS)
+def test_game_ids_across_two_to_the_32(team):
+    """first_game_id = 2^32 - 40: games 0..39 have ids below 2^32, games 40..128 above (the id's high word is part of the rule
+    walk's Philox key). The deals are the oracle env's of that id base; on the same deals the moves are not those of base 0."""
+    import hanabi_hip
+
+    base, n = 2 ** 32 - 40, 129
+    e = U.expected("Hanabi-Full", 2, n, team, first_game_id=base)
+    cfg = hanabi_hip.make_config("Hanabi-Full", 2)
+    res = hanabi_hip.rule_playout(cfg, _dev_rows(e["rows0"]), _agents(team, 2), SEED, first_game_id=base, log=True)
+    _assert_matches(res, e)
+    zero = hanabi_hip.rule_playout(cfg, _dev_rows(e["rows0"]), _agents(team, 2), SEED, first_game_id=0, log=True)
+    other = (_np(zero.actions) != _np(res.actions)).any(0)
+    assert other[:40].any() and other[40:].any()
+
+
+@pytest.mark.parametrize("game,players", [(g, p) for g, p, _ in NEW_CASES])
+def test_search_playout_equals_the_loop_on_deep_roots(game, players):
+    """The instantiations no search had driven, from mid-game rows: the running rows of tests/deep_rows.pick whose seat to act
+    is the last seat (first_seat != 0; cards to draw and empty decks, Very-Small 5 empty decks only), every legal first move
+    forced, [Piers] * P. One launch against the turn loop, figure for figure."""
+    import torch
+
+    import deep_rows as DR
+    import hanabi_hip
+    from hanabi_hip import RolloutSearch, encode_rows
+
+    p = DR.pick(game, players)
+    seat, deck = (p.rows[:, 0] >> 13) & 7, p.rows[:, 0] & 63
+    mine = (((p.rows[:, 0] >> 19) & 3) == 0) & (seat == players - 1)
+    assert (mine & (deck == 0)).sum() >= 4 and ((mine & (deck > 0)).sum() >= 2 or (game, players) == ("Hanabi-Very-Small", 5))
+    rows = _dev_rows(p.rows[mine])
+    cfg = hanabi_hip.make_config(game, players)
+    _, legal = encode_rows(cfg, rows)
+    assert bool((legal != 0).any(1).all())
+    team = _agents("piers", players)
+    fast = RolloutSearch(game, players, replicas=4, seed=3, playout=True)
+    slow = RolloutSearch(game, players, replicas=4, seed=3, playout=False)
+    a = fast.run(rows, legal, team, draw=5)
+    assert fast.last_path == "playout"
+    b = slow.run(rows, legal, team, draw=5)
+    assert slow.last_path == "loop"
+    for k in ("value", "wsum", "n_live", "best"):
+        x, y = getattr(a, k), getattr(b, k)
+        assert torch.equal(torch.nan_to_num(x.double(), nan=-7.0), torch.nan_to_num(y.double(), nan=-7.0)), k
+        assert torch.equal(torch.isnan(x.double()), torch.isnan(y.double())), k
+    assert a.rollouts == b.rollouts > 0 and a.dead == b.dead == 0 and a.turns <= b.turns
+    assert bool((a.best >= 0).all()) and torch.equal(rows, _dev_rows(p.rows[mine]))
 
 
 def _dqn(env_like, seed=5):

@@ -50,6 +50,17 @@ def test_layout_equals_the_torch_expressions(game, players, turns):
             assert torch.equal(n_played.long(), played.view(m, -1).sum(1))
 
 
+def layout_by_gather(det_rows, weights, cand, filler, R):
+    """hb_search_layout as a direct numpy gather (also tests/test_determinize_deep_gpu.py's): det_rows [m * R, SW], weights
+    [m * R] uint32, cand [m, C] int32, filler [m] int32 -> (rows [m * C * R, SW], forced [m * C * R], done [m * C * R] uint8,
+    n_played [m])."""
+    m, Cn = cand.shape
+    i, c, r = np.meshgrid(np.arange(m), np.arange(Cn), np.arange(R), indexing="ij")
+    played = (cand[i, c] >= 0) & (weights[i * R + r] != 0)
+    return (det_rows[(i * R + r).reshape(-1)], np.where(cand[i, c] >= 0, cand[i, c], filler[i]).reshape(-1),
+            np.where(played, 0, 0x80).astype(np.uint8).reshape(-1), played.reshape(m, -1).sum(1))
+
+
 @pytest.mark.parametrize("game,players,turns", [("Hanabi-Full", 2, 14), ("Hanabi-Full", 5, 17), ("Hanabi-Small", 2, 7)])
 def test_layout_of_short_candidate_lists(game, players, turns):
     """C = 1 and 2, hand-built lists, against a direct numpy gather."""
@@ -78,12 +89,9 @@ def test_layout_of_short_candidate_lists(game, players, turns):
                                                              torch.as_tensor(filler).cuda(), R)
                 dn, wn = det_rows.cpu().numpy(), _u32(w)
                 assert (wn.reshape(m, R)[2] == 0).all() and wn[R * (m - 1)] == 0 and (wn > 0).any()
-                i, c, r = np.meshgrid(np.arange(m), np.arange(Cn), np.arange(R), indexing="ij")
-                played = (cand[i, c] >= 0) & (wn[i * R + r] != 0)
-                assert np.array_equal(rows.cpu().numpy(), dn[(i * R + r).reshape(-1)])
-                assert np.array_equal(forced.cpu().numpy(), np.where(cand[i, c] >= 0, cand[i, c], filler[i]).reshape(-1))
-                assert np.array_equal(done.cpu().numpy(), np.where(played, 0, 0x80).astype(np.uint8).reshape(-1))
-                assert np.array_equal(n_played.cpu().numpy(), played.reshape(m, -1).sum(1))
+                want = layout_by_gather(dn, wn, cand, filler, R)
+                for got, exp in zip((rows, forced, done, n_played), want):
+                    assert np.array_equal(got.cpu().numpy(), exp)
                 assert n_played[0] == 0 and n_played[2] == 0
 
 
