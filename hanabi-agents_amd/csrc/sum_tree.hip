@@ -17,7 +17,8 @@
 //                  (last occurrence wins, the sequential order of sum_tree.h:38-44), writes the
 //                  leaves and re-sums their ancestors level by level. Optionally fuses
 //                  p = (|td|+1e-10)^alpha and the running max/min (priority_buffer.py:48-52).
-//   fill_chunks    ring insert of a contiguous (wrapping) leaf range at one value
+//   fill_chunks    ring insert of a contiguous leaf range at one value, wrapping at the replay ring's
+//                  capacity (hb_tree_set_ring; the tree's own size by default)
 //                  (priority_buffer.py:29-32): each workgroup owns an aligned 1024-leaf subtree,
 //                  rewrites its leaves and rebuilds its 10 levels through LDS.
 //   rebuild_top    one workgroup re-sums the levels above the 1024-leaf subtrees.
@@ -40,6 +41,7 @@ using hb::fail;
 
 struct hb_tree {
   long long cap;
+  long long ring;     // hb_tree_set_ring: slots of the replay ring this tree serves (default cap): the fill wraps here, PER samples stay below
   int depth;          // log2(cap)
   int chunk;          // leaves per rebuild workgroup = min(cap, 1024)
   float* nodes;       // 2*cap
@@ -126,13 +128,16 @@ __global__ __launch_bounds__(1024) void update_small_kernel(float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
-// chunk rebuild: workgroup b owns the aligned subtree of `chunk` leaves number chunk_id(b)
+// chunk rebuild: workgroup b owns the aligned subtree of `chunk` leaves number chunk_id(b). `ring` (<= cap): the leaves
+// [0, ring) are the slots of the replay ring; a fill wraps at `ring` (like the ring's own write pointer), walks only the
+// ceil(ring / chunk) subtrees that hold ring slots and never writes a leaf at or beyond `ring`.
 // ---------------------------------------------------------------------------------------------
 template <bool FILL>
 __global__ __launch_bounds__(256) void chunk_kernel(float* __restrict__ nodes, long long cap, int chunk, int first_chunk,
-                                                    long long start, long long n, const float* __restrict__ value_dev) {
+                                                    long long start, long long n, const float* __restrict__ value_dev,
+                                                    long long ring) {
   __shared__ float s[2048];  // heap of the subtree: s[1] root, leaves s[chunk .. 2chunk)
-  const long long nchunks = cap / chunk;
+  const long long nchunks = (ring + chunk - 1) / chunk;
   const long long c = (first_chunk + static_cast<long long>(blockIdx.x)) % nchunks;
   const long long leaf0 = c * chunk;
   float fillv = 0.f;
@@ -142,8 +147,8 @@ __global__ __launch_bounds__(256) void chunk_kernel(float* __restrict__ nodes, l
     float v;
     if (FILL) {
       long long rel = leaf - start;
-      if (rel < 0) rel += cap;
-      const bool in = rel < n;
+      if (rel < 0) rel += ring;
+      const bool in = rel < n && leaf < ring;
       v = in ? fillv : nodes[cap + leaf];
       if (in) nodes[cap + leaf] = v;
     } else {
@@ -385,7 +390,7 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ n
 __global__ __launch_bounds__(256) void per_sample_kernel(const float* __restrict__ nodes, long long cap, int depth,
                                                          const double* __restrict__ u, long long batch, int unit,
                                                          unsigned long long seed, const float* __restrict__ counter,
-                                                         int64_t* __restrict__ idx, double* __restrict__ prob) {
+                                                         int64_t* __restrict__ idx, double* __restrict__ prob, long long ring) {
   const int lane = threadIdx.x & 63;
   const long long i = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (i >= batch) return;
@@ -408,8 +413,11 @@ __global__ __launch_bounds__(256) void per_sample_kernel(const float* __restrict
   }
   const float query = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(static_cast<float>(lin - ui) * total)));
   float leaf;
-  const long long k = wave_descend(nodes, cap, depth, query, lane, &leaf);
+  long long k = wave_descend(nodes, cap, depth, query, lane, &leaf);
   if (lane == 0) {
+    // a key that rounds to the whole total ends on the tree's LAST leaf: on a ring that is no power of two
+    // that is no slot; the sample is the ring's last slot then
+    if (k >= ring) { k = ring - 1; leaf = nodes[cap + k]; }
     idx[i] = k;
     prob[i] = (static_cast<double>(leaf) + 1e-10) / static_cast<double>(total);  // priority_buffer.py:42
   }
@@ -429,6 +437,7 @@ struct SampleGatherArgs {
   int L, packed_words; void* x; int x_dtype, x_ld;
   int32_t* act; float* rew; float* term; float* disc;
   const long long* size_wp; long long ring_cap, n_ins; int n_step; float gamma;
+  long long tree_ring;   // hb_tree_set_ring: sampled indices stay below it
   int ntop;   // > 0: the tree keeps its top levels lazily; every workgroup re-sums them from the ntop subtree roots in LDS
 };
 template <typename T> __device__ __forceinline__ void sg_store(T* p, long long i, float v);
@@ -466,8 +475,9 @@ __global__ __launch_bounds__(256) void per_sample_gather_kernel(const SampleGath
     const double ui = static_cast<double>(bits) * 0x1.0p-53 / static_cast<double>(B);
     const float query = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(static_cast<float>(lin - ui) * total)));
     float leaf;
-    const long long k = wave_descend(a.nodes, a.cap, a.depth, query, lane, &leaf, s_top, 2 * a.ntop);
+    long long k = wave_descend(a.nodes, a.cap, a.depth, query, lane, &leaf, s_top, 2 * a.ntop);
     if (lane == 0) {
+      if (k >= a.tree_ring) { k = a.tree_ring - 1; leaf = a.nodes[a.cap + k]; }   // as in per_sample_kernel
       a.idx[i] = k;
       a.prob[i] = (static_cast<double>(leaf) + 1e-10) / static_cast<double>(total);
       // the n-step chain of this sample (gather_kernel, learner.hip): a handful of dependent 1-byte / 4-byte reads
@@ -535,7 +545,7 @@ void freshen_top(hb_tree* t, hipStream_t s) {
 
 int rebuild(hb_tree* t, int first_chunk, int nchunks_touched, hipStream_t s) {
   hipLaunchKernelGGL((chunk_kernel<false>), dim3(nchunks_touched), dim3(256), 0, s, t->nodes, t->cap, t->chunk,
-                     first_chunk, 0LL, 0LL, static_cast<const float*>(nullptr));
+                     first_chunk, 0LL, 0LL, static_cast<const float*>(nullptr), t->cap);
   const int ntop = static_cast<int>(t->cap / t->chunk);
   if (ntop > 1)
     hipLaunchKernelGGL(rebuild_top_kernel, dim3(1), dim3(ntop >= 2048 ? 1024 : (ntop / 2 < 64 ? 64 : ntop / 2)),
@@ -560,6 +570,7 @@ int hb_tree_create(int64_t capacity, hb_tree** out) {
   hb_tree* t = new (std::nothrow) hb_tree();
   if (!t) return fail(HB_ERR_NOMEM, "out of host memory");
   t->cap = cap;
+  t->ring = cap;
   t->depth = depth;
   t->chunk = cap < 1024 ? static_cast<int>(cap) : 1024;
   t->stamp = nullptr;
@@ -594,6 +605,13 @@ int hb_tree_destroy(hb_tree* t) {
 }
 
 int64_t hb_tree_capacity(const hb_tree* t) { return t ? t->cap : 0; }
+
+int hb_tree_set_ring(hb_tree* t, int64_t ring_capacity) {
+  if (!t) return fail(HB_ERR_INVALID, "null tree");
+  if (ring_capacity < 1 || ring_capacity > t->cap) return fail(HB_ERR_INVALID, "ring_capacity must be in [1, tree capacity]");
+  t->ring = ring_capacity;
+  return HB_OK;
+}
 float* hb_tree_nodes(hb_tree* t) { return t ? t->nodes : nullptr; }
 
 static int update_impl(hb_tree* t, const int64_t* idx, const float* val, int64_t n, int per_mode, double alpha,
@@ -667,15 +685,20 @@ int hb_tree_fill_range(hb_tree* t, int64_t start, int64_t n, const float* value_
   if (!t) return fail(HB_ERR_INVALID, "null tree");
   if (n <= 0) return HB_OK;
   if (!value_dev) return fail(HB_ERR_INVALID, "null value_dev");
-  if (start < 0 || start >= t->cap) return fail(HB_ERR_INVALID, "start out of range");
-  if (n > t->cap) n = t->cap;
+  if (start < 0 || start >= t->ring) return fail(HB_ERR_INVALID, "start out of range");
+  if (n > t->ring) n = t->ring;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const long long nchunks = t->cap / t->chunk;
-  long long touched = ((start % t->chunk) + n + t->chunk - 1) / t->chunk;
+  // the subtrees that hold ring slots, walked from the one that holds `start` round to the one that holds the last leaf
+  // filled; the ring may end inside its last subtree, so the walk after a wrap starts again at subtree 0
+  const long long nchunks = (t->ring + t->chunk - 1) / t->chunk;
+  const long long first = start / t->chunk;
+  long long touched;
+  if (start + n <= t->ring) touched = (start + n - 1) / t->chunk - first + 1;
+  else touched = (nchunks - first) + (start + n - t->ring - 1) / t->chunk + 1;
   if (touched > nchunks) touched = nchunks;
   hipLaunchKernelGGL((chunk_kernel<true>), dim3(static_cast<unsigned>(touched)), dim3(256), 0, s, t->nodes, t->cap,
-                     t->chunk, static_cast<int>(start / t->chunk), static_cast<long long>(start),
-                     static_cast<long long>(n), value_dev);
+                     t->chunk, static_cast<int>(first), static_cast<long long>(start),
+                     static_cast<long long>(n), value_dev, t->ring);
   if (!t->lazy_top) launch_top(t, s);
   HB_HIP(hipGetLastError());
   return HB_OK;
@@ -701,7 +724,7 @@ int hb_per_sample(hb_tree* t, const double* u_dev, int64_t batch, int32_t unit_u
   freshen_top(t, static_cast<hipStream_t>(stream));
   hipLaunchKernelGGL(per_sample_kernel, dim3(static_cast<unsigned>((batch + 3) / 4)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), t->nodes, t->cap, t->depth, u_dev, static_cast<long long>(batch),
-                     unit_uniforms != 0 ? 1 : 0, 0ull, static_cast<const float*>(nullptr), idx_dev, prob_dev);
+                     unit_uniforms != 0 ? 1 : 0, 0ull, static_cast<const float*>(nullptr), idx_dev, prob_dev, t->ring);
   HB_HIP(hipGetLastError());
   return HB_OK;
 }
@@ -714,7 +737,8 @@ int hb_per_sample_philox(hb_tree* t, uint64_t seed, const float* counter_dev, in
   freshen_top(t, static_cast<hipStream_t>(stream));
   hipLaunchKernelGGL(per_sample_kernel, dim3(static_cast<unsigned>((batch + 3) / 4)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), t->nodes, t->cap, t->depth, static_cast<const double*>(nullptr),
-                     static_cast<long long>(batch), 2, static_cast<unsigned long long>(seed), counter_dev, idx_dev, prob_dev);
+                     static_cast<long long>(batch), 2, static_cast<unsigned long long>(seed), counter_dev, idx_dev, prob_dev,
+                     t->ring);
   HB_HIP(hipGetLastError());
   return HB_OK;
 }
@@ -737,7 +761,7 @@ int hb_per_sample_gather(hb_tree* t, uint64_t seed, const float* counter_dev, in
   SampleGatherArgs a{t->nodes, t->cap, t->depth, static_cast<unsigned long long>(seed), counter_dev, static_cast<int>(batch),
                      idx_dev, prob_dev, ring_obs_tm1_dev, ring_obs_t_dev, ring_act_dev, ring_rew_dev, ring_term_dev, obs_len,
                      packed ? (obs_len + 31) / 32 : 0, x_dev, x_dtype, x_ld, act_dev, rew_dev, term_dev, disc_dev,
-                     reinterpret_cast<const long long*>(size_wp_dev), capacity, rows_per_insert, n_step, gamma, 0};
+                     reinterpret_cast<const long long*>(size_wp_dev), capacity, rows_per_insert, n_step, gamma, t->ring, 0};
   const int ntop = static_cast<int>(t->cap / t->chunk);
   if (t->lazy_top && ntop > 1) a.ntop = ntop;
   const size_t lds = static_cast<size_t>(2 * a.ntop) * sizeof(float);

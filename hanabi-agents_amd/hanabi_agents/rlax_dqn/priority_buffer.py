@@ -24,6 +24,9 @@ class PriorityBuffer(ExperienceBuffer):
         from hanabi_hip import SumTree  # HIP-only: raises without a GPU / the compiled library
 
         self.sum_tree = SumTree(capacity, device=self.device)
+        # the tree has 2^ceil(log2(capacity)) leaves; only the first `capacity` are ring slots: the insert's fill wraps where
+        # the ring's write pointer wraps and the sampler never returns a leaf past the ring
+        self.sum_tree.set_ring_capacity(capacity)
         self.alpha = alpha
         self._max_priority = torch.full((1,), alpha, dtype=torch.float32, device=self.device)
         self._min_priority = torch.full((1,), alpha, dtype=torch.float32, device=self.device)
@@ -53,13 +56,29 @@ class PriorityBuffer(ExperienceBuffer):
     def load_state_dict(self, sd):
         super().load_state_dict(sd)
         if sd["has_data"]:
-            self.sum_tree.import_nodes(sd["tree_nodes"])
+            self.sum_tree.import_nodes(self._ring_heap(sd["tree_nodes"]))
             self._max_priority.copy_(sd["max_priority"])
             self._min_priority.copy_(sd["min_priority"])
         else:
             self.sum_tree.import_nodes(torch.zeros(2 * self.sum_tree.capacity))
             self._max_priority.fill_(self.alpha)
             self._min_priority.fill_(self.alpha)
+
+    def _ring_heap(self, nodes):
+        """A saved heap with every leaf past the ring at zero. A heap written before the fill wrapped at the ring can carry
+        priorities there; they are dropped and every inner node is re-summed as fl(left + right), the tree's own invariant.
+        A heap that has none is returned as it is."""
+        T, ring = self.sum_tree.capacity, self.capacity
+        nodes = nodes.to(device="cpu", dtype=torch.float32)
+        if nodes.numel() != 2 * T or ring >= T or not bool((nodes[T + ring:] != 0).any()):
+            return nodes
+        nodes = nodes.clone()
+        nodes[T + ring:] = 0
+        w = T // 2
+        while w >= 1:
+            nodes[w:2 * w] = nodes[2 * w:4 * w:2] + nodes[2 * w + 1:4 * w:2]
+            w //= 2
+        return nodes
 
     # ---- device path ------------------------------------------------------------------------------
     def sample_batch_dev(self, batch_size, uniforms=None):

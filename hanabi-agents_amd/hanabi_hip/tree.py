@@ -25,7 +25,14 @@ class SumTree:
             K.check(self.L.hb_tree_create(int(capacity), C.byref(h)))
         self.h = h
         self.capacity = int(self.L.hb_tree_capacity(h))
+        self.ring_capacity = self.capacity
         self._total = torch.zeros(1, dtype=torch.float32, device=self.device)
+
+    def set_ring_capacity(self, ring_capacity):
+        """Leaves [0, ring_capacity) are the slots of the replay ring this tree serves (hb_tree_set_ring): fill_range_dev
+        wraps there and per_sample*_dev never return an index at or beyond it."""
+        K.check(self.L.hb_tree_set_ring(self.h, int(ring_capacity)))
+        self.ring_capacity = int(ring_capacity)
 
     def __del__(self):
         h = getattr(self, "h", None)

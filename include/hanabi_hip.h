@@ -341,9 +341,18 @@ int hb_tree_set_lazy_top(hb_tree* t, int32_t on);
  * Out-of-range indices are ignored and counted in hb_tree_error_count().                */
 int hb_tree_update(hb_tree* t, const int64_t* idx_dev, const float* val_dev, int64_t n, void* stream);
 
+/* The replay ring this tree serves has ring_capacity slots, 1 <= ring_capacity <= hb_tree_capacity (default: the tree's
+ * capacity, so a tree that is never told behaves as before). Leaf s stands for ring slot s; the leaves at and beyond
+ * ring_capacity are no slots: hb_tree_fill_range wraps at ring_capacity and never writes them, and hb_per_sample,
+ * hb_per_sample_philox and hb_per_sample_gather never return them (a key that ends beyond the ring, which only the key
+ * float(1 - u) == 1 on the last stratum can do, returns slot ring_capacity - 1 and that leaf's value).
+ * hb_tree_sample, hb_tree_update and hb_tree_get keep the tree's own range. Host-only: no launch, no synchronisation. */
+int hb_tree_set_ring(hb_tree* t, int64_t ring_capacity);
+
 /* Ring insert used by PriorityBuffer.add_transitions (priority_buffer.py:29-32): leaves
- * (start + i) mod cap for i in [0, n) take *value_dev (a device scalar, so the running
- * max priority never visits the host).                                                  */
+ * (start + i) mod ring_capacity (hb_tree_set_ring) for i in [0, n) take *value_dev (a device
+ * scalar, so the running max priority never visits the host). start must be below
+ * ring_capacity; n is clipped to it.                                                    */
 int hb_tree_fill_range(hb_tree* t, int64_t start, int64_t n, const float* value_dev, void* stream);
 
 /* get_indices + get_values (sum_tree.h:46-72): for each quantile q in [0,1]:

@@ -1481,7 +1481,7 @@ EXEMPT = {
     "hb_env_set_color_shuffle": _OWNED, "hb_env_set_color_perms": _OWNED, "hb_env_set_games_per_wave": _HOST,
     "hb_env_set_async_refill": _HOST, "hb_env_set_refill_period": _HOST, "hb_env_set_profile_events": _HOST,
     "hb_tree_create": _OWNED, "hb_tree_destroy": _OWNED, "hb_tree_import_nodes": _OWNED + " (the heap; seen through export_nodes)",
-    "hb_tree_set_lazy_top": _HOST, "hb_tree_update": _OWNED + " (the heap; seen through export_nodes)",
+    "hb_tree_set_lazy_top": _HOST, "hb_tree_set_ring": _HOST, "hb_tree_update": _OWNED + " (the heap; seen through export_nodes)",
     "hb_tree_fill_range": _OWNED + " (the heap; seen through export_nodes)",
     "hb_encode_rows": "every output guarded in tests/test_encode_rows_gpu.py",
     "hb_belief_score": "every output guarded in tests/test_belief_score_gpu.py",

@@ -130,4 +130,5 @@ def test_argument_validation_needs_no_gpu():
     assert L.hb_chain_run(cmds, 0, None, None) == 0
     assert L.hb_per_sample_philox(None, 1, one, 4, one, one, None) < 0
     assert L.hb_tree_import_nodes(None, one, None) < 0
+    assert L.hb_tree_set_ring(None, 8) < 0 and b"null tree" in L.hb_last_error()   # (its range check needs a tree: tests/test_per_ring_gpu.py)
     assert L.hb_env_state(None) is None
