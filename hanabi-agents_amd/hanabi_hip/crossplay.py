@@ -29,6 +29,12 @@ teams on the same deals and returns one `EvalResult` per team, each equal to wha
   per team) between the env step and the grouped tally. Every team's EvalResult carries its `responses`;
   `CrossPlayResult.responses` stacks them in team order and `convention_distance()` compares the teams' response rows. As in
   Evaluator, moves of colour-shuffled seats are in their mover's frame (hanabi_hip.symmetry).
+* `playout=True` (default False: the loop above, launch for launch): a run whose teams use `RulebasedAgent`s only, with
+  `responses` and `color_shuffle` off (`playout.crossplay_playout_supported`), plays each chunk with ONE launch of
+  hb_rule_playout_grouped (hanabi_hip.playout) on a scratch copy of the repeated deals — a block per team, id_stride 0, the padding
+  rows' `done` at 0x80 and therefore not played — instead of the loop, and builds no env for the chunk; any other run takes the
+  loop. `CrossPlay.last_path` says which ran: "playout" or "loop". Every EvalResult is the loop's field for field, except that
+  `turns` is the block's longest game and logged moves after a game's end are -1 (as Evaluator(playout=True)).
 """
 import ctypes as C
 import math
@@ -38,6 +44,7 @@ import numpy as np
 import torch
 
 from . import _capi as K
+from . import playout as _playout
 from .env import HanabiEnv
 from .evaluate import EvalResult, eval_config, max_turns, normalize_rows, shuffle_mask, uid_kinds
 from .grouped import TILE, MoveTable, RuleSets, classify
@@ -155,15 +162,18 @@ class CrossPlayResult:
 class _Chunk:
     """The env and buffers of `nb` team blocks of n_pad games (built once, reused by every run with that many blocks)."""
 
-    def __init__(self, cp, nb):
+    def __init__(self, cp, nb, env=True):
+        """env=False: the buffers of the playout path alone, which steps no env and asks no agent for moves."""
         n, n_pad, dev = cp.n, cp.n_pad, cp.device
         rows = nb * n_pad
         self.nb, self.rows = nb, rows
-        self.env = HanabiEnv(config=cp.cfg, n_games=rows, seed=cp.seed, first_game_id=cp.first_game_id, device=dev, packed=True)
-        dev = self.env.device
+        self.env = None
+        if env:
+            self.env = HanabiEnv(config=cp.cfg, n_games=rows, seed=cp.seed, first_game_id=cp.first_game_id, device=dev, packed=True)
+            dev = self.env.device
         self.rows0 = cp._deals.repeat(nb, 1)
         pad = torch.zeros(n_pad, dtype=torch.uint8, device=dev)
-        pad[n:] = 0x80   # padding rows start finished: stepped, never counted
+        pad[n:] = 0x80   # padding rows start finished: stepped (the playout: not played), never counted
         self.done0 = pad.repeat(nb)
         self.done = torch.empty_like(self.done0)
         self.final_score = torch.zeros(rows, dtype=torch.int8, device=dev)
@@ -172,6 +182,10 @@ class _Chunk:
         self.counters0[:, 0] = n
         self.counters = torch.empty_like(self.counters0)
         self.actions = torch.zeros(cp.max_turns if cp.record_actions else 1, rows, dtype=torch.int32, device=dev)
+        if not env:
+            self.play_rows = torch.empty_like(self.rows0)   # the scratch copy of the deals that the kernel plays
+            self.tail = (torch.empty(1, dtype=torch.int64, device=dev), torch.empty(nb, dtype=torch.int32, device=dev))
+            return
         self.q = torch.empty(rows, self.env.num_actions, dtype=torch.float32, device=dev)
         if cp.responses:
             A = self.env.num_actions
@@ -183,11 +197,16 @@ class CrossPlay:
     """Plays every team of a pool on the same `n_games` deals; see the module docstring.
 
     game / players / config / seed / first_game_id / record_actions / check_every / responses: as Evaluator. max_rows: games per chunk
-    (teams of one chunk run in lock-step; more teams than fit take several chunks one after another)."""
+    (teams of one chunk run in lock-step; more teams than fit take several chunks one after another). playout: a switch, see the
+    module docstring."""
 
     def __init__(self, game="Hanabi-Full", players=2, n_games=4096, seed=1, first_game_id=0, max_rows=262144, record_actions=False,
-                 device=None, config=None, check_every=8, color_shuffle=False, responses=False):
+                 device=None, config=None, check_every=8, color_shuffle=False, responses=False, playout=False):
         n_games = int(n_games)
+        if not isinstance(playout, bool):
+            raise TypeError(f"playout is a switch (True or False), got {playout!r}")
+        self.playout = playout
+        self.last_path = None   # "playout" or "loop": the path the last run() took
         self.color_shuffle = bool(color_shuffle)
         self.responses = bool(responses)
         if n_games < 1:
@@ -211,6 +230,7 @@ class CrossPlay:
         self._deals = None    # [n_pad, state words]: built by the first run (construction needs no GPU)
         self._perms = None    # color_shuffle: [n_pad, P, C] every seat's permutation of those deals
         self._chunks = {}     # block count -> _Chunk
+        self._play_chunks = {}   # block count -> _Chunk without an env (the playout path)
         # agent -> eval_moves scratch of the generic path: the block's n rows, and its padding rows
         self._scratch = weakref.WeakKeyDictionary()
         self._scratch_pad = weakref.WeakKeyDictionary()
@@ -219,7 +239,7 @@ class CrossPlay:
     def chunks(self, n_teams):
         return plan_chunks(n_teams, self.n_pad, self.max_rows)
 
-    def _chunk(self, nb):
+    def _chunk(self, nb, with_env=True):
         if self._deals is None:
             env = HanabiEnv(config=self.cfg, n_games=self.n_pad, seed=self.seed, first_game_id=self.first_game_id, device=self.device,
                             packed=True)
@@ -228,9 +248,10 @@ class CrossPlay:
                 env.set_color_shuffle(True, observe=False)
                 self._perms = env.color_perms()
             self.device = env.device
-        ch = self._chunks.get(nb)
+        store = self._chunks if with_env else self._play_chunks
+        ch = store.get(nb)
         if ch is None:
-            ch = self._chunks[nb] = _Chunk(self, nb)
+            ch = store[nb] = _Chunk(self, nb, with_env)
         return ch
 
     @torch.no_grad()
@@ -244,9 +265,21 @@ class CrossPlay:
         for a in pool:
             if not hasattr(a, "eval_moves"):
                 raise TypeError(f"{type(a).__name__} has no eval_moves()")
-        kinds, rule_sets = self.classify_pool(pool, grouped)
         results = [None] * len(teams)
         self.last_turns = []
+        if self.playout and _playout.crossplay_playout_supported(pool, teams, responses=self.responses, color_shuffle=self.color_shuffle):
+            self.last_path = "playout"
+            rule_sets = RuleSets(pool[i] for i in sorted({i for t in teams for i in t}))
+            for first, nb in self.chunks(len(teams)):
+                ch = self._chunk(nb, with_env=False)
+                if rule_sets.table_dev is None:   # once per run
+                    rule_sets.upload(self.device)
+                out = self._play_kernel(ch, [[rule_sets.index(pool[i]) for i in t] for t in teams[first:first + nb]], rule_sets)
+                for b, res in enumerate(out):
+                    results[first + b] = res
+            return CrossPlayResult(teams, results, k, self.players, default)
+        self.last_path = "loop"
+        kinds, rule_sets = self.classify_pool(pool, grouped)
         for first, nb in self.chunks(len(teams)):
             ch = self._chunk(nb)
             if len(rule_sets) and rule_sets.table_dev is None:   # once per run, shared by every seat's table
@@ -353,6 +386,38 @@ class CrossPlay:
                                                 actions=ch.actions[:tb, r0:r0 + n].clone() if self.record_actions else None, turns=tb,
                                                 perms=perms[r0:r0 + n] if perms is not None and masks[b] else None,
                                                 responses=resp[b] if resp is not None else None, kinds=kinds))
+        return out
+
+    def _play_kernel(self, ch, index, rule_sets):
+        """_play for a chunk of rule-list teams: one hb_rule_playout_grouped launch on a scratch copy of the repeated deals
+        (module docstring). index: the chunk's [nb][P] rule-set indices. The same counters, the same errors."""
+        cfg, P, n, n_pad, nb = self.cfg, self.players, self.n, self.n_pad, ch.nb
+        with torch.cuda.device(self.device):
+            ch.play_rows.copy_(ch.rows0)
+            ch.done.copy_(ch.done0)
+            ch.final_score.zero_()
+            ch.length.zero_()
+            ch.counters.copy_(ch.counters0)
+            team_of_block = torch.tensor(index, dtype=torch.int32, device=self.device).reshape(nb, P)
+            res = _playout._launch_grouped(cfg, ch.play_rows, nb, n_pad, 0, team_of_block, rule_sets, self.seed, 0, None, self.max_turns,
+                                           self.first_game_id, ch.done, ch.final_score, ch.length, ch.counters,
+                                           ch.actions if self.record_actions else None, tail=ch.tail)
+            c = ch.counters.cpu()
+            fs, ln = ch.final_score.cpu(), ch.length.cpu()
+            illegal, max_len = int(res.illegal), res.max_len.tolist()
+        live = int(c[:, 0].sum())
+        if live != 0:
+            raise RuntimeError(f"{live} cross-play games still live after max_turns = {self.max_turns} turns")
+        if illegal:
+            raise RuntimeError(f"cross-play agents chose {illegal} illegal moves")
+        self.last_turns.append(max(max_len))
+        kinds = uid_kinds(P, cfg.colors, cfg.hand_size, K.lib().hb_num_actions(C.byref(cfg)))
+        out = []
+        for b in range(nb):
+            r0 = b * n_pad
+            out.append(EvalResult.from_counters(fs[r0:r0 + n], ln[r0:r0 + n], self.max_score, c[b], P,
+                                                actions=ch.actions[:max_len[b], r0:r0 + n].clone() if self.record_actions else None,
+                                                turns=max_len[b], kinds=kinds))
         return out
 
     def _generic_moves(self, ch, b, agent, kind, t, act):

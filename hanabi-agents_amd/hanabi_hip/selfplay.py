@@ -470,11 +470,12 @@ class SelfPlaySession:
         return rs.run(self.env.export_state(), self.env.legal.clone(), self.agents if blueprint is None else blueprint,
                       self.env_steps if draw is None else int(draw), history=history)
 
-    def crossplay(self, pool, n_games=4096, seed=1, teams=None, color_shuffle=False, responses=False):
+    def crossplay(self, pool, n_games=4096, seed=1, teams=None, color_shuffle=False, responses=False, playout=False):
         """Cross-play of a pool of agents (the session's own and others, DQN and rule-based mixed) on `n_games` fresh deals keyed
         by `seed`: a hanabi_hip.crossplay.CrossPlayResult with one EvalResult per team. As evaluate(): updates in flight are
         completed first, the session and its agents are left exactly as they were, and the CrossPlay is kept for the next call.
-        responses=True: per-team partner-response counts and CrossPlayResult.convention_distance()."""
+        responses=True: per-team partner-response counts and CrossPlayResult.convention_distance(). playout (default False):
+        CrossPlay's — a run whose teams use rule lists only plays each chunk in one launch."""
         self.flush()
         from .crossplay import CrossPlay
 
@@ -484,6 +485,7 @@ class SelfPlaySession:
             rank = self.env.first_game_id // self.env.n if self.env.n else 0   # (data-parallel: each rank its own deals)
             cp = self._crossplays[key] = CrossPlay(config=self.env.cfg, n_games=n_games, seed=seed, first_game_id=rank * int(n_games),
                                                    device=self.env.device, color_shuffle=color_shuffle, responses=responses)
+        cp.playout = bool(playout)   # (the kept CrossPlay takes this call's)
         return cp.run(pool, teams=teams)
 
     def evaluate_pool(self, n_games=4096, seed=1, color_shuffle=False):

@@ -1,11 +1,13 @@
-/* hanabi_hip_playout.h — hb_rule_playout: games of rule-list teams played to the end in ONE kernel launch (csrc/playout.hip).
+/* hanabi_hip_playout.h — hb_rule_playout, hb_rule_playout_grouped: games of rule-list teams played to the end in ONE kernel launch
+ * (csrc/playout.hip); the grouped form, one team per block of games, is described above its prototype.
  *
  * Part of the C-ABI of hanabi_hip.h (same conventions: HB_OK or a negative HB_ERR_* code, hb_last_error() for the message,
  * arguments checked before the device is touched, `_dev` pointers are device memory, asynchronous on `stream`). It is declared
  * in a header of its own, and its ctypes signature is kept by hanabi_hip/playout.py, because hanabi_hip.h's prototypes and the
- * table of bounds cases that covers every one of them are pinned by tests that may not change with a feature; the entry point's
- * own guard-band test (tests/test_playout_gpu.py) holds it to what that table holds the others to. It belongs in hanabi_hip.h
- * and in that table as soon as those may change. HB_ABI_VERSION stays 1: nothing existing changed.
+ * table of bounds cases that covers every one of them are pinned by tests that may not change with a feature; the entry points'
+ * own guard-band tests (tests/test_playout_gpu.py, tests/test_playout_grouped_gpu.py) hold them to what that table holds the
+ * others to. They belong in hanabi_hip.h and in that table as soon as those may change. HB_ABI_VERSION stays 1: nothing existing
+ * changed.
  *
  * The loop it replaces (hanabi_hip.evaluate.Evaluator.run, hanabi_hip.search.rollout) issues, per turn t = 0 .. max_turns-1 with
  * seat = (first_seat + t) % P to act in every game: hb_rule_act (that seat's rule list, Philox seed `seed`, draw t + 1, game id
@@ -58,6 +60,44 @@ int hb_rule_playout(const hb_config* cfg, uint32_t* rows_dev, int64_t n, int64_t
                     const int32_t* n_rules, uint64_t seed, int32_t first_seat, const int32_t* first_moves_dev, int32_t max_turns,
                     uint8_t* done_dev, int8_t* final_score_dev, int16_t* length_dev, int64_t* counters_dev,
                     int32_t* actions_log_dev, int64_t* illegal_dev, int32_t* max_len_dev, void* stream);
+
+/* hb_rule_playout over n_blocks equal blocks of block_games games, ONE TEAM PER BLOCK, in one launch: the playout form of
+ * hb_rule_act_grouped / hb_rule_act_blocks and hb_eval_tally_grouped (cross-play's team blocks on repeated deals, a population of
+ * rule lists on common deals, the members of a partner pool on the distinct games of one env).
+ *
+ *   The per-game arrays (rows_dev, first_moves_dev, done_dev, final_score_dev, length_dev, every row of actions_log_dev) hold the
+ *   blocks one after another: n_blocks * block_games entries, block b at [b * block_games, (b + 1) * block_games).
+ *   Row r of block b has game id first_game_id + b * id_stride + r. id_stride is 0 (every block replays the same deals:
+ *   cross-play) or block_games (distinct games).
+ *   team_of_block_dev [n_blocks][P] int32   the rule set of every seat of every block: an index into
+ *   rules_dev [n_sets][HB_MAX_RULES], n_rules_dev [n_sets]   DEVICE tables, hb_rule_act_grouped's (n_rules clamped to
+ *                                     0 .. HB_MAX_RULES; the kinds are read on the device and not checked: an unknown kind never
+ *                                     fires)
+ *   counters_dev [n_blocks][hb_eval_counters(cfg)] int64: one row per block, prepared as hb_rule_playout's one row
+ *   actions_log_dev [max_turns, n_blocks * block_games] int32 or NULL
+ *   illegal_dev  one int64, ADDED to (all blocks)
+ *   max_len_dev [n_blocks] int32, each raised (atomic max) to its block's largest length written; the caller zeroes them
+ *
+ * For every block b, its rows, done, final_score, length, counter row, slice of the log and max_len are bit for bit what
+ * hb_rule_playout leaves on that block alone: with the block's team, first_game_id + b * id_stride, the same seed, first_seat,
+ * max_turns and the block's slice of first_moves_dev. A block with a seat whose index is negative or not below n_sets is skipped:
+ * nothing of it is written, except that its log entries are -1.
+ *
+ * No wavefront holds games of two blocks: a block takes ceil(block_games / 256) workgroups of a linear grid and its last wavefront
+ * may be partial; any block_games >= 1 is legal (a block's rows start 16-byte aligned whenever rows_dev does). The team of a
+ * workgroup is uniform: its P rule lists are copied to LDS once and read from there at a uniform address. The LDS counters are
+ * per workgroup and reach the block's counter row with one atomic per non-zero counter and workgroup. The turn loop keeps its
+ * host-checked bound; no wavefront waits on another workgroup, nothing spins.
+ * Rejected as hb_rule_playout rejects (config, NULL buffers, first_seat, max_turns, HB_ERR_ALIGN), and with HB_ERR_INVALID: a NULL
+ * team_of_block_dev / rules_dev / n_rules_dev, n_sets < 1, n_blocks < 0, block_games < 1, id_stride neither 0 nor block_games,
+ * n_blocks * block_games not below 2^31. n_blocks == 0 is a no-op; without a device: HB_ERR_NO_DEVICE (arguments are checked
+ * first).                                                                                                                    */
+int hb_rule_playout_grouped(const hb_config* cfg, uint32_t* rows_dev, int64_t n_blocks, int64_t block_games, int64_t first_game_id,
+                            int64_t id_stride, const int32_t* team_of_block_dev, const hb_rule* rules_dev,
+                            const int32_t* n_rules_dev, int32_t n_sets, uint64_t seed, int32_t first_seat,
+                            const int32_t* first_moves_dev, int32_t max_turns, uint8_t* done_dev, int8_t* final_score_dev,
+                            int16_t* length_dev, int64_t* counters_dev, int32_t* actions_log_dev, int64_t* illegal_dev,
+                            int32_t* max_len_dev, void* stream);
 
 #ifdef __cplusplus
 }
