@@ -800,7 +800,10 @@ int hb_actor_fused_act_grouped(const hb_fused_tile* tiles_dev, int64_t n_rows, c
  *     [2 + B + 4 * p + k]               moves of seat p of kind k: 0 discard, 1 play, 2 reveal colour, 3 reveal rank
  *                                       (decoded from the uid, App. A.2 order)
  *     [2 + B + 4 * P + p]               misplays of seat p (a play whose reward is <= 0)
- * A game counts on the turn it ends and only then; games already marked in done_dev are ignored. Counters are reduced per
+ * A game counts on the turn it ends and only then; games already marked in done_dev are ignored.
+ * A uid outside 0 .. A-1 is no move: it has no kind and is no misplay, whatever the reward; the turn still counts towards the
+ * length and a terminal still ends the game. A score outside 0 .. B-1 (no env reports one) is counted in the nearest end bin,
+ * and final_score_dev gets the raw value. (tests/test_tally_crafted_gpu.py pins both.) Counters are reduced per
  * wavefront (ballots) and per workgroup (LDS); each takes at most one global atomic per workgroup, from <= 128 workgroups. Without a device: HB_ERR_NO_DEVICE (arguments are checked first).                              */
 int hb_eval_counters(const hb_config* cfg); /* number of int64 counters: 2 + colors * ranks + 1 + 5 * players */
 int hb_eval_tally(const hb_config* cfg, int64_t n_games, int32_t seat, int32_t turn, const int32_t* actions_dev,
@@ -856,6 +859,10 @@ int hb_eval_response_tally_grouped(const hb_config* cfg, int64_t n_blocks, int64
  *     [3 + B] bomb-outs, [4 + B] sum of lengths, [5 + B] episodes counted in those two (deal seen),
  *     [6 + B + 4 * p + k] moves of seat p of kind k (App. A.2 order), [6 + B + 4 * P + p] misplays of seat p (a play whose reward
  *     is <= 0). Bomb-out and misplay rules are those of hb_eval_tally.
+ * As there, a uid outside 0 .. A-1 is no move (no kind, no misplay); the step still counts towards the length and a terminal
+ * still ends the episode. A score outside 0 .. B-1 is counted in the nearest end bin, and it is that clamped value that goes
+ * into the sums [1] and [2], so the sums always equal the histogram's. Moves and misplays count whether or not the deal was seen.
+ * Rows of a tile that nobody owns are neither read nor written, lost_dev and length_dev included.
  * Reduced per wavefront (ballots) and per workgroup (LDS); each counter takes at most one global atomic per workgroup, from
  * <= 128 workgroups. Without a device: HB_ERR_NO_DEVICE (arguments are checked first).
  * hb_train_tally_init arms game g (lost = 0, length = 0) when its state row is at the first move of a deal (every information
