@@ -277,3 +277,143 @@ def search_leaf_ref(done, final_score, score, q, legal, u, max_score):
     x = LEAF_SCALE * (sc + v)
     run = np.clip(np.floor(x + u), 0, LEAF_SCALE * int(max_score))
     return np.where((done & 0x80) != 0, LEAF_SCALE * fs, run.astype(np.int64)).astype(np.int8)
+
+
+def belief_enumerate_ref(cfg, rows, seat, hist_rows, hist_moves, hist_alive, hist_valid, draws, move_fn, max_hands, replicas, seed,
+                         draw, first_row_id=0, details=False):
+    """hb_belief_enumerate (include/hanabi_hip_exact.h) restated in plain loops over roots and hands, with nothing of the kernel's
+    layout: rows [m, SW] the states now, `seat` the observer, the history in PartnerHistory's layout (hist_rows [D, m, SW],
+    hist_moves [D, m], hist_alive / hist_valid [D, m] or None, draws a list of D ints; hist_rows None or empty: D = 0) -> a dict
+    of numpy arrays: status uint8 [m], space int64 [m], mass int64 [D + 1, m], n_hands int32 [D + 1, m], depth_used int32 [m],
+    fallback uint8 [m], marg and marg0 int64 [m, H, NC], hands uint32 [m, R].
+
+    The partners' moves are the caller's to supply (nothing here knows a rule): for each entry d, ONE call
+
+        move_fn(rows [k, SW] uint32, mover_seat [k] int64, draws[d], root [k] int64) -> uids [k]
+
+    with the hypothetical states of every hand that has reproduced the entries before d: row j is the state of root root[j] (the
+    partner's draws are keyed by its game id, first_game_id + root[j]: the caller's to apply) in which seat mover_seat[j] moves.
+    details=True appends, per root, the list of (cards, mass, pass) of every hand in enumeration order (None unless status 0)."""
+    import numpy as np
+
+    u32 = lambda x: (np.asarray(x).astype(np.int64) & _M32).astype(np.uint32)
+    cur = u32(rows)
+    (m, SW), R, st = cur.shape, int(replicas), int(seat)
+    D = 0 if hist_rows is None else len(hist_rows)
+    P, H, Rk, Cn = cfg.players, cfg.hand_size, cfg.ranks, cfg.colors
+    NC = Cn * Rk
+    deck_n = Cn * sum(3 if r == 0 else 1 if r == Rk - 1 else 2 for r in range(Rk))
+    assert 0 <= st < P and 0 <= D <= 8 and R >= 1 and int(max_hands) >= 1
+    if D:
+        hrows, hmoves = u32(hist_rows), np.asarray(hist_moves).astype(np.int64)
+        assert hrows.shape == (D, m, SW) and hmoves.shape == (D, m) and len(draws) == D
+        alive = None if hist_alive is None else np.asarray(hist_alive).astype(np.int64).reshape(D, m)
+        valid = None if hist_valid is None else np.asarray(hist_valid).astype(np.int64).reshape(D, m)
+    out = dict(status=np.zeros(m, np.uint8), space=np.zeros(m, np.int64), mass=np.zeros((D + 1, m), np.int64),
+               n_hands=np.zeros((D + 1, m), np.int32), depth_used=np.zeros(m, np.int32), fallback=np.zeros(m, np.uint8),
+               marg=np.zeros((m, H, NC), np.int64), marg0=np.zeros((m, H, NC), np.int64), hands=np.zeros((m, R), np.uint32))
+    hands = [None] * m    # per enumerated root: [cards tuple, mass, pass count, still matching]
+    depth_of = [0] * m    # L_i
+    for i in range(m):
+        w0, w1, own = int(cur[i, 0]), int(cur[i, 1]), int(cur[i, 10 + st])
+        out["hands"][i, :] = own
+        if (w0 >> 19) & 3 != 0:
+            out["status"][i] = 2
+            continue
+        n = min((w1 >> (15 + 3 * st)) & 7, H)
+        know = int(cur[i, 10 + P + 2 * st]) | int(cur[i, 10 + P + 2 * st + 1]) << 32
+        deck = np.ascontiguousarray(cur[i, 10 + 3 * P:], dtype="<u4").view(np.uint8)
+        pool = [(own >> (5 * s)) & 31 for s in range(n)] + [int(deck[q]) for q in range(deck_n - min(w0 & 63, deck_n), deck_n)]
+        cnt = [pool.count(c) for c in range(NC)]
+        allowed = []
+        for s in range(n):
+            kn = (know >> (12 * s)) & 0xFFF
+            allowed.append([c for c in range(NC) if cnt[c] > 0 and (kn >> (c // Rk)) & 1 and (kn >> (5 + c % Rk)) & 1])
+        N = 1
+        for a in allowed:
+            N *= len(a)
+        out["space"][i] = N
+        if N > int(max_hands):
+            out["status"][i] = 1
+            continue
+        L = 0
+        while L < D and (valid is None or valid[L, i] != 0):
+            L += 1
+        depth_of[i] = L
+        mine = hands[i] = []
+        for e in range(N):
+            cards, mass, x = [], 1, e
+            for s in range(n):
+                c = allowed[s][x % len(allowed[s])]
+                x //= len(allowed[s])
+                mass *= max(cnt[c] - cards.count(c), 0)
+                cards.append(c)
+            mine.append([tuple(cards), mass, 0, mass > 0])
+    for d in range(D):   # the hands that have reproduced every entry before d, of the roots that have an entry d
+        batch = []
+        for i in range(m):
+            if hands[i] is None or d >= depth_of[i]:
+                continue
+            prev = hrows[d, i]
+            mover = (int(prev[0]) >> 13) & 7
+            word, bits = int(prev[10 + st]), 0xFF if alive is None else int(alive[d, i])
+            for h in hands[i]:
+                if not h[3]:
+                    continue
+                if mover >= P:   # a row that names no seat reproduces nothing
+                    h[3] = False
+                    continue
+                w, t = word, 0   # hb_belief_splice_alive's rule: the alive occupied slots take the hand's cards as a prefix
+                for s in range(5):
+                    if (word >> (5 * s)) & 31 != 31 and (bits >> s) & 1 and t < len(h[0]):
+                        w = (w & ~(31 << (5 * s))) | (h[0][t] << (5 * s))
+                        t += 1
+                row = prev.copy()
+                row[10 + st] = w
+                batch.append((i, h, mover, row))
+        if not batch:
+            continue
+        uids = np.asarray(move_fn(np.stack([b[3] for b in batch]), np.array([b[2] for b in batch], np.int64), int(draws[d]),
+                                  np.array([b[0] for b in batch], np.int64))).astype(np.int64)
+        assert uids.shape == (len(batch),)
+        for (i, h, _, _), uid in zip(batch, uids):
+            h[3] = int(uid) == int(hmoves[d, i])
+            h[2] += 1 if h[3] else 0
+    seed, draw = int(seed) & _M64, int(draw) & _M64
+    for i in range(m):
+        if hands[i] is None:
+            continue
+        L, mine = depth_of[i], hands[i]
+        for k in range(L + 1):
+            out["mass"][k, i] = sum(h[1] for h in mine if h[2] >= k)
+            out["n_hands"][k, i] = sum(1 for h in mine if h[2] >= k and h[1] > 0)
+        used = max(k for k in range(L + 1) if k == 0 or out["mass"][k, i] > 0)
+        out["depth_used"][i] = used
+        out["fallback"][i] = 2 if L == 0 else 1 if used == 0 else 0
+        for cards, mass, passed, _ in mine:
+            for s, c in enumerate(cards):
+                out["marg0"][i, s, c] += mass
+                if passed >= used:
+                    out["marg"][i, s, c] += mass
+        T = int(out["mass"][used, i])
+        if T == 0:
+            continue
+        rid = (int(first_row_id) + i) & _M64
+        x = _philox_np(0x10000 + np.arange(R, dtype=np.uint64), draw & _M32, rid & _M32, rid >> 32, seed & _M32,
+                       ((seed >> 32) ^ (draw >> 32)) & _M32)
+        own = int(cur[i, 10 + st])
+        for r in range(R):
+            target = (((int(x[0][r]) << 32) | int(x[1][r])) * T) >> 64
+            run = 0
+            for cards, mass, passed, _ in mine:
+                if passed >= used:
+                    run += mass
+                    if run > target:
+                        w = own | 0x1FFFFFF
+                        for s, c in enumerate(cards):
+                            w = (w & ~(31 << (5 * s))) | (c << (5 * s))
+                        out["hands"][i, r] = w
+                        break
+    if details:
+        out["details"] = [None if h is None else [(x[0], x[1], x[2]) for x in h] for h in hands]
+    return out

@@ -1214,13 +1214,23 @@ class RolloutSearch:
     searched without a horizon, is rolled out by ONE hb_rule_playout launch (hanabi_hip.playout) on the
     laid-out rows, with the forced first moves and the preset `done` bytes; the rollout env is not touched. Every figure of the
     result is the loop's bit for bit except `turns`, the longest rollout's length instead of the next multiple of `check_every`.
-    Any other blueprint, or a horizon, takes the loop; `last_path` ("playout" or "loop") says what the last search did."""
+    Any other blueprint, or a horizon, takes the loop; `last_path` ("playout" or "loop") says what the last search did.
+    exact, max_hands (defaults False, None = hanabi_hip.exact.DEFAULT_MAX_HANDS; with exact=False every path issues the launches it
+    issued before): where `exact_supported` holds (a 2-player blueprint of `RulebasedAgent`s, no epsilon), the replicas of a search
+    with a `PartnerHistory` or a last-move history come from the exact, enumerated belief (hanabi_hip.exact.ExactDeterminizer;
+    DESIGN.md section 11f, "The exact belief") instead of filtered candidates. A root with more than max_hands hands takes the
+    sampled path above, which runs only when there is such a root, and is merged in root by root. Otherwise the whole call is
+    the sampled path. `last_belief` ("exact", "mixed" or "sampled") says which ran, `last_exact` is the search's `ExactBelief`."""
 
     def __init__(self, game="Hanabi-Full", players=2, replicas=32, seed=1, device=None, config=None, check_every=8, first_game_id=0,
-                 oversample=8, epsilon=None, score_belief=False, horizon=None, leaf=None, playout=False):
+                 oversample=8, epsilon=None, score_belief=False, horizon=None, leaf=None, playout=False, exact=False, max_hands=None):
         self.cfg = eval_config(game, players, config)
         self.players = self.cfg.players
         self.set_horizon(horizon, leaf)
+        self.set_exact(exact, max_hands)
+        self.edet = None          # hanabi_hip.exact.ExactDeterminizer, built by the first exact search
+        self.last_belief = None   # "exact", "mixed" (some roots over max_hands took the sampled path) or "sampled"
+        self.last_exact = None    # the ExactBelief of the last search that enumerated (None: it did not)
         if not isinstance(playout, bool):
             raise TypeError(f"playout is a switch (True or False), got {playout!r}")
         self.playout = playout
@@ -1261,6 +1271,46 @@ class RolloutSearch:
         elif leaf is not None:
             raise ValueError("leaf= values the games a horizon cuts short: it needs horizon=H")
         self.horizon, self.leaf = horizon, leaf
+
+    def set_exact(self, exact, max_hands=None):
+        """The exact-belief switch of the searches from here on (the constructor's arguments, and its checks)."""
+        from .exact import DEFAULT_MAX_HANDS
+
+        if not isinstance(exact, bool):
+            raise TypeError(f"exact is a switch (True or False), got {exact!r}")
+        max_hands = DEFAULT_MAX_HANDS if max_hands is None else int(max_hands)
+        if max_hands < 1:
+            raise ValueError(f"max_hands must be >= 1, got {max_hands}")
+        self.exact, self.max_hands = exact, max_hands
+
+    def _sample_exact(self, b, r, history, blueprint, cp, R, draw, first_row_id):
+        """The conditioned replicas of an exact search -> `BeliefSample` in b["det_rows"] / b["weights"]: every root from the
+        enumerated belief (hanabi_hip.exact), except those with more than max_hands hands (status 1), which take
+        `ConditionedDeterminizer`'s path, run only when there is such a root, and are merged in root by root."""
+        from .exact import ExactDeterminizer
+
+        m, dev, SW = r.shape[0], r.device, self.det.state_words
+        if self.edet is None:
+            self.edet = ExactDeterminizer(config=self.cfg)
+        out = (b["det_rows"], b["weights"])
+        sample, belief = self.edet.sample_history(r, history, blueprint, cp, R, self.seed, draw, history.partner_seed,
+                                                  history.first_game_id, first_row_id=first_row_id, max_hands=self.max_hands, out=out)
+        self.last_exact = belief
+        large = belief.status == 1
+        if not bool(large.any().item()):
+            self.last_belief = "exact"
+            return sample
+        self.last_belief = "mixed"
+        keep_rows, keep_w = sample.rows.clone(), sample.weights.clone()
+        if self.cdet is None:
+            self.cdet = ConditionedDeterminizer(config=self.cfg)
+        other = self.cdet.sample_history(r, history, blueprint[(cp - 1) % self.players], cp, R, self.oversample, self.seed, draw,
+                                         history.partner_seed, history.first_game_id, first_row_id=first_row_id, out=out)
+        pick = lambda a, x: torch.where(large.view((1,) * (a.dim() - 1) + (m,)), a, x)
+        b["det_rows"].copy_(torch.where(large.view(m, 1, 1), other.rows.view(m, R, SW), keep_rows.view(m, R, SW)).view(m * R, SW))
+        b["weights"].copy_(torch.where(large.view(m, 1), other.weights.view(m, R), keep_w.view(m, R)).view(m * R))
+        return BeliefSample(b["det_rows"], b["weights"], pick(other.n_surv, sample.n_surv), pick(other.depth_used, sample.depth_used),
+                            pick(other.fallback, sample.fallback), None)
 
     def _setup(self, m, Cn, R, first_game_id, dev):
         b = self._sized.get((m, Cn, R))
@@ -1330,6 +1380,7 @@ class RolloutSearch:
         if H is not None:   # (before anything is played: the agent that values a leaf must be able to)
             valuers = leaf_agents(blueprint, self.leaf, seats=((cp + H) % self.players,))
         n_surv = fallback = depth_used = ess = sample = None
+        self.last_belief, self.last_exact = "sampled", None
         with torch.cuda.device(dev):
             if history is None:
                 self.det.sample(r, seat=cp, replicas=R, seed=self.seed, draw=draw, first_row_id=first_row_id,
@@ -1338,11 +1389,16 @@ class RolloutSearch:
                 history.take(m, R, (b["det_rows"], b["weights"]))
                 n_surv, fallback, depth_used, ess = history.n_surv, history.fallback, history.depth_used, history.ess
             else:   # a PartnerHistory or a LastMove
-                if self.cdet is None:
-                    self.cdet = ConditionedDeterminizer(config=self.cfg)
-                sample = self.cdet.sample_history(
-                    r, history, blueprint[(cp - 1) % self.players], cp, R, self.oversample, self.seed, draw, history.partner_seed,
-                    history.first_game_id, first_row_id=first_row_id, out=(b["det_rows"], b["weights"]), epsilon=self.epsilon)
+                if self.exact:
+                    from .exact import exact_supported
+                if self.exact and exact_supported(blueprint, self.players, epsilon=self.epsilon):
+                    sample = self._sample_exact(b, r, history, blueprint, cp, R, draw, first_row_id)
+                else:
+                    if self.cdet is None:
+                        self.cdet = ConditionedDeterminizer(config=self.cfg)
+                    sample = self.cdet.sample_history(
+                        r, history, blueprint[(cp - 1) % self.players], cp, R, self.oversample, self.seed, draw, history.partner_seed,
+                        history.first_game_id, first_row_id=first_row_id, out=(b["det_rows"], b["weights"]), epsilon=self.epsilon)
                 # (the result of a last-move history keeps its public shapes: n_surv [m], no depth_used)
                 n_surv, depth_used = (sample.n_surv[0], None) if isinstance(history, LastMove) else (sample.n_surv, sample.depth_used)
                 fallback, ess = sample.fallback, sample.ess
@@ -1566,7 +1622,13 @@ class SearchPlayer:
 
     horizon, leaf (defaults None: rollouts to the end, the player above bit for bit): RolloutSearch's depth-limited rollouts, in
     both stages. The seat whose agent values the leaves is (seat + horizon) % P; with leaf=None it is the blueprint's own agent of
-    that seat and must have eval_q (TypeError here, at construction). `leaf_games` totals the rollout games valued at the horizon."""
+    that seat and must have eval_q (TypeError here, at construction). `leaf_games` totals the rollout games valued at the horizon.
+
+    exact, max_hands (defaults False, None: the player above bit for bit; exact=True needs condition=True): RolloutSearch's exact
+    belief, in both stages. With a blueprint of two `RulebasedAgent`s and neither epsilon nor track, every conditioned root's
+    replicas are drawn from the enumerated posterior given the partner's last `depth` moves; a root with more than max_hands hands
+    takes the sampled path. `last_belief` says which ran; depth_stats() gains `exact_roots`, `too_large_roots` (together the
+    first stage's conditioned roots) and `exact_hands` (the hands walked for the former)."""
 
     COUNTERS =("moves", "deviations", "confirmed", "rejected", "conditioned", "unconditioned", "survivors", "candidates", "fallbacks",
                 "depth_used")
@@ -1574,9 +1636,16 @@ class SearchPlayer:
 
     def __init__(self, blueprint, seat, replicas=32, threshold=0.0, seed=1, check_every=8, z=None, confirm_replicas=0,
                  condition=False, oversample=8, depth=1, epsilon=None, score_belief=False, track=False, horizon=None, leaf=None,
-                 playout=False):
+                 playout=False, exact=False, max_hands=None):
         self.blueprint = list(blueprint)
         self.seat = int(seat)
+        if not isinstance(exact, bool):
+            raise TypeError(f"exact is a switch (True or False), got {exact!r}")
+        if exact and not condition:
+            raise ValueError("exact=True needs condition=True")
+        if max_hands is not None and int(max_hands) < 1:
+            raise ValueError(f"max_hands must be >= 1, got {max_hands}")
+        self.exact, self.max_hands = exact, None if max_hands is None else int(max_hands)
         if not isinstance(playout, bool):
             raise TypeError(f"playout is a switch (True or False), got {playout!r}")
         self.playout = playout   # RolloutSearch's: rule-list blueprints without a horizon roll out in one launch per search
@@ -1635,7 +1704,8 @@ class SearchPlayer:
         self._history = None   # depth > 1: the PartnerHistory of the env of the last call
         self._search = None
         self.last_result = None   # the SearchResult of the last call's first stage
-        self._memory = None    # condition: (env, draw, rows, moves played) of the last call
+        self.last_belief = None   # RolloutSearch's, of the last call's first stage: "exact", "mixed" or "sampled"
+        self._memory = None   # condition: (env, draw, rows, moves played) of the last call
         self._prev_env = None  # condition: the scratch env that rebuilds the partner's state
         self.reset_stats()
 
@@ -1652,6 +1722,7 @@ class SearchPlayer:
         self._track_stats = None    # track: [len(TRACK_COUNTERS)] int64 on the device
         self._track_ess = None      # track: [2] float64 on the device, sum of ess and count over the tracked roots
         self._belief_track = None   # track and score_belief: the sums of _belief, split (tracked roots, restarted roots)
+        self._exact_stats = None    # exact: [3] int64 on the device, see depth_stats()
 
     def belief_stats(self):
         """score_belief: the first stage's beliefs against the real hands since reset_stats(), over every live root searched:
@@ -1682,6 +1753,9 @@ class SearchPlayer:
         if self.track:   # the mean effective sample size of the tracked roots' carried, weighed particles
             total, count = (0.0, 0.0) if self._track_ess is None else self._track_ess.tolist()
             out["carried_ess"] = total / count if count else 0.0
+        if self.exact:   # of the first stage's conditioned roots: enumerated, over max_hands (sampled instead), hands walked
+            ex = [0, 0, 0] if self._exact_stats is None else self._exact_stats.tolist()
+            out.update(exact_roots=int(ex[0]), too_large_roots=int(ex[1]), exact_hands=int(ex[2]))
         return out
 
     def _previous(self, env, rows, draw):
@@ -1753,7 +1827,7 @@ class SearchPlayer:
             self._search = RolloutSearch(config=env.cfg, replicas=self.replicas, seed=self.seed, device=env.device,
                                          check_every=self.check_every, oversample=self.oversample, epsilon=self.epsilon,
                                          score_belief=self.score_belief, horizon=self.horizon, leaf=self.leaf,
-                                         playout=self.playout)
+                                         playout=self.playout, exact=self.exact, max_hands=self.max_hands)
         rows = env.export_state()
         staged = self.z is not None or self.confirm_replicas > 0
         history = None
@@ -1768,6 +1842,13 @@ class SearchPlayer:
         res = self._search.run(rows, env.legal, self.blueprint, draw, seat=self.seat,
                                baseline=actions_out if self.z is not None else None, history=history)
         self.last_result = res
+        self.last_belief = self._search.last_belief
+        if self.exact and self._search.last_exact is not None and res.fallback is not None:
+            eb = self._search.last_exact   # (the first stage's: a confirming stage enumerates again)
+            cond = running(rows) & (res.fallback != 2)
+            done = cond & (eb.status == 0)
+            ex = torch.stack([done.sum(), (cond & (eb.status == 1)).sum(), (eb.space * done).sum()])
+            self._exact_stats = ex if self._exact_stats is None else self._exact_stats + ex
         if res.belief is not None:   # (None: the switch is off, or no root was running)
             filtered = res.fallback != 2 if self.condition and res.fallback is not None else torch.zeros_like(res.belief.scored)
             sums = torch.stack([res.belief.sums(where=filtered), res.belief.sums(where=~filtered)])

@@ -439,7 +439,7 @@ class SelfPlaySession:
         return ev.run(self.agents if partners is None else partners)
 
     def search(self, blueprint=None, replicas=32, seed=1, draw=None, history=None, oversample=8, horizon=None, leaf=None,
-               playout=False):
+               playout=False, exact=False, max_hands=None):
         """Belief-sampled rollout search (hanabi_hip.search) from the session env's current states: a
         SearchResult with the value of every move of the seat to act in every game, should it be played now and everybody follow
         `blueprint` (one agent per seat; default: the session's agents) afterwards. `draw` keys the determinization (default:
@@ -449,7 +449,9 @@ class SelfPlaySession:
         (RolloutSearch's docstring), with `oversample` candidates per replica; or a `PartnerHistory` of the env's games: on the
         partner's last `depth` moves. horizon, leaf (defaults None: rollouts to the end): RolloutSearch's depth-limited rollouts,
         the leaves valued by eval_q of the blueprint's own agents (leaf=None), of `leaf`'s, or not at all (leaf="score"). playout
-        (default False): RolloutSearch's — a blueprint of rule lists only, without a horizon, rolls out in one launch."""
+        (default False): RolloutSearch's — a blueprint of rule lists only, without a horizon, rolls out in one launch. exact, max_hands
+        (defaults False, None: the sampled belief, unchanged): RolloutSearch's — with a history and a 2-player blueprint of rule lists,
+        the replicas are drawn from the exact, enumerated belief (hanabi_hip.exact)."""
         if blueprint is None and self.pool is not None:
             raise ValueError("a session with a partner pool has no single team: pass the blueprint (one agent per seat)")
         if getattr(self.env, "color_shuffled", False):
@@ -467,6 +469,7 @@ class SelfPlaySession:
         rs.oversample = max(1, int(oversample))
         rs.set_horizon(horizon, leaf)   # (the kept search takes this call's)
         rs.playout = bool(playout)
+        rs.set_exact(exact, max_hands)
         return rs.run(self.env.export_state(), self.env.legal.clone(), self.agents if blueprint is None else blueprint,
                       self.env_steps if draw is None else int(draw), history=history)
 
